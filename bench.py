@@ -5,12 +5,15 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One "step" = one iteration of the train_mcl.py loop body (muscle_amd.mcl_step) on a synthetic batch that is
-already resident in HBM.  Rank 0 prints ONE JSON line.  Extra objects:
+already resident in HBM.  Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps, writes the
+last step's outputs if --dump-outputs DIR is given, and prints the line (metric, value, unit, ms_per_step, losses, ...).
+--full adds the extra objects below (each of them costs runs of its own):
   roofline     — dominant kernel family (the pointwise-conv GEMMs), timed live with HIP events on the launch stream; every
                  launch is priced against the peak of the pipe it ran on (fp32 MFMA, or bf16 MFMA / 6 for split arithmetic)
   fp32_mfma / split_mfma — the same K steps in the OTHER GEMM arithmetic (config.arithmetic names the one `value` was measured in)
   configs      — short runs of BASELINE.json configs[1] (B0 / 448 / batch 16) and of step-full (epoch-12 gates), N=1 only
   cpu_baseline — the CPU oracle (oracle/mcl_oracle.py, a port of the reference) timed on this host, N=1 only
+--no-other-arith / --no-configs / --no-cpu-baseline / --gemm-table refine a --full run.
 """
 import argparse
 import json
@@ -42,6 +45,25 @@ HBM_PEAK_GBPS = 8000.0                # same guide: HBM3E spec; 6290 GB/s is wha
 STEP_CEILING_MFMA_IMGS = 600.0
 STEP_CEILING_HBM_IMGS = 974.0
 DEFAULT_ARITH = "split"
+DUMP_PARAMS_MAX = 8 << 20             # --dump-outputs: parameters beyond this many floats (32 MB) are sampled
+DUMP_SEED = 0
+
+
+def dump_outputs(path, out, model):
+    """What the last timed step handed its caller: the loss terms (float64 scalars) and the model's parameters after the
+    optimizer step (float32, all of them concatenated in model.parameters() order, or a fixed seeded sample of at most
+    DUMP_PARAMS_MAX of them - sorted positions drawn with numpy's default_rng(DUMP_SEED))."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(path, f"{k}.npy"), np.asarray(float(v.detach()) if torch.is_tensor(v) else float(v), dtype=np.float64))
+    with torch.no_grad():
+        flat = torch.cat([p.detach().reshape(-1) for p in model.parameters()])
+        name = "params"
+        if flat.numel() > DUMP_PARAMS_MAX:
+            idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), DUMP_PARAMS_MAX))
+            flat, name = flat[torch.from_numpy(idx).to(flat.device)], "params_sample"
+        np.save(os.path.join(path, f"{name}.npy"), flat.float().cpu().numpy())
 
 
 def make_batch(n, size, view, seed, dev):
@@ -326,100 +348,10 @@ def short_run_infer(dev, steps=3):
     return out
 
 
-def main():
-    # host threads: the GPU boxes show 256 CPUs under a cgroup quota of 16; torch's default of 128 intra-op threads makes every CPU-side
-    # torch call that parallelises 10-30x slower there (profiles/r05_cpu_probe.txt).  Per rank: the quota shared by the ranks of the node.
-    torch.set_num_threads(max(1, min(16, cpu_share() // max(1, int(os.environ.get("LOCAL_WORLD_SIZE", "1"))))))
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--model", default="efficientnet-b7")
-    ap.add_argument("--batch", type=int, default=32, help="per-GPU batch")
-    ap.add_argument("--size", type=int, default=448)
-    ap.add_argument("--epoch", type=int, default=4, help="epoch gate semantics of train_mcl.py (4: cls+ER+IMC)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--arith", choices=["split", "fp32"], default=os.environ.get("MUSCLE_BENCH_ARITH", DEFAULT_ARITH),
-                    help="GEMM arithmetic of the timed steps (config.arithmetic); the other one is timed as well and reported beside it")
-    ap.add_argument("--no-split", "--no-other-arith", dest="no_other", action="store_true",
-                    help="skip the extra K steps in the other GEMM arithmetic")
-    ap.add_argument("--gemm-table", default=None, help="write the per-shape table of the pointwise GEMM launches (GemmTimer.table) here")
-    ap.add_argument("--no-configs", action="store_true", help="skip the short runs of configs[1] and step-full")
-    ap.add_argument("--graph", action="store_true",
-                    help="timed steps replay phase 1 from a captured hipGraph (muscle_amd.GraphedStep; one GPU, epoch < 8).  Not "
-                         "the default: measured on MI355X the replay saves 0.5 ms of 136 on B7 but serialises the weight-gradient "
-                         "side stream, which is worth 3.6 ms on B7 when launched eagerly; it is the better choice for B0-sized models")
-    ap.add_argument("--eager", action="store_true", help="(the default; kept for older command lines)")
-    a = ap.parse_args()
-
-    rank = int(os.environ.get("RANK", 0))
-    local = int(os.environ.get("LOCAL_RANK", 0))
-    world = int(os.environ.get("WORLD_SIZE", 1))
-    if world != a.gpus:
-        raise SystemExit(f"--gpus {a.gpus} but WORLD_SIZE={world}: launch N>1 with torch.distributed.run")
-    if not torch.cuda.is_available():
-        raise SystemExit("bench.py needs a ROCm GPU (the product path has no CPU fallback)")
-    import torch.distributed as dist
-    # MUSCLE_DIST_BACKEND=gloo + MUSCLE_SHARE_GPU=1: rehearsal of the N>1 flow with all ranks on one GPU (tests only)
-    backend = os.environ.get("MUSCLE_DIST_BACKEND", "nccl")
-    if os.environ.get("MUSCLE_SHARE_GPU"):
-        local = 0
-    torch.cuda.set_device(local)
-    dev = torch.device("cuda", local)
-    if world > 1:
-        if backend == "nccl":
-            dist.init_process_group("nccl", device_id=dev)
-        else:
-            dist.init_process_group(backend)
-
+def full_legs(a, timer, eager_step, barrier, cfg, other, rank, world, backend, dev):
+    """--full: the instrumented eager steps of the roofline and the other arithmetic's leg, right after the timed region."""
     import muscle_amd
-    from muscle_amd.dist import GradAverager, broadcast_parameters
-    cfg = arch.net_cfg(a.model, False)
-    torch.manual_seed(0)
-    model = muscle_amd.MuSCLe(21, a.model, layers=3, last_pooling=False).to(dev)
-    broadcast_parameters(model)
-    opt = muscle_amd.FusedAdam(model.parameters(), lr=1e-4, weight_decay=5e-5)
-    view = a.size // 2
-    batch = make_batch(a.batch, a.size, view, 1000 + rank, dev)
-    hook = GradAverager().attach(model) if world > 1 else None     # chunks go out as backward fills the arena
-    timer = GemmTimer()
-    timer.install()
-    other = "fp32" if a.arith == "split" else "split"
-    muscle_amd.set_gemm_mode(ARITH_MODE[a.arith])
-
-    def step():
-        # ER's top-k count int(0.2 * label.sum() * H * W) (train_mcl.py:178,188) is taken INSIDE the step, on the device (the
-        # reference reads it back every iteration; a count precomputed outside the timed region would be work skipped)
-        return muscle_amd.mcl_step(model, opt, batch, a.epoch, valid_channel=batch["label"].sum(), grad_hook=hook)
-
-    if a.graph and (world > 1 or a.epoch >= 8):
-        raise SystemExit("--graph covers phase 1 on one GPU (epoch < 8)")
-    eager_step = step
-    if a.graph:
-        gstep = muscle_amd.GraphedStep(model, opt, a.epoch)
-        for _ in range(gstep.warmup + 1):          # eager settling steps + the capturing call
-            gstep(batch)
-        step = lambda: gstep(batch)                # noqa: E731  (copies the batch into the static buffers, replays)
-
-    if a.epoch >= 8:
-        _calibrate_bn(model, batch["view1"])
-    for _ in range(a.warmup):
-        step()
-
-    def barrier():
-        torch.cuda.synchronize()
-        if world > 1:
-            dist.barrier()
-        torch.cuda.synchronize()
-
-    host_t0 = [0.0]
-
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(a.steps):
-        out = step()
-    barrier()
-    dt = time.perf_counter() - t0
+    import torch.distributed as dist
     # Per-launch HIP events for the roofline: the same work enqueued eagerly right after the timed region, with the
     # weight-gradient side stream off.  The timed steps cannot carry them: graph replays have no host-side launch to
     # bracket, and a weight-gradient GEMM that shares the chip with HBM-bound kernels has no duration of its own.
@@ -476,6 +408,118 @@ def main():
                                       "flop_share_split": o_share, "gemm_ms_per_step": o_ms / inst_steps,
                                       "avg_launch_us": o_ms * 1e3 / max(o_n, 1)}
         timer.pairs, timer.dw, timer.shapes = main_pairs, main_dw, main_shapes
+    return inst_steps, inst_dt, calls_main, beside
+
+
+def main():
+    # host threads: the GPU boxes show 256 CPUs under a cgroup quota of 16; torch's default of 128 intra-op threads makes every CPU-side
+    # torch call that parallelises 10-30x slower there (profiles/r05_cpu_probe.txt).  Per rank: the quota shared by the ranks of the node.
+    torch.set_num_threads(max(1, min(16, cpu_share() // max(1, int(os.environ.get("LOCAL_WORLD_SIZE", "1"))))))
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--model", default="efficientnet-b7")
+    ap.add_argument("--batch", type=int, default=32, help="per-GPU batch")
+    ap.add_argument("--size", type=int, default=448)
+    ap.add_argument("--epoch", type=int, default=4, help="epoch gate semantics of train_mcl.py (4: cls+ER+IMC)")
+    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--arith", choices=["split", "fp32"], default=os.environ.get("MUSCLE_BENCH_ARITH", DEFAULT_ARITH),
+                    help="GEMM arithmetic of the timed steps (config.arithmetic); with --full the other one is timed as well and reported beside it")
+    ap.add_argument("--no-split", "--no-other-arith", dest="no_other", action="store_true",
+                    help="skip the extra K steps in the other GEMM arithmetic")
+    ap.add_argument("--gemm-table", default=None, help="write the per-shape table of the pointwise GEMM launches (GemmTimer.table) here")
+    ap.add_argument("--no-configs", action="store_true", help="skip the short runs of configs[1] and step-full")
+    ap.add_argument("--graph", action="store_true",
+                    help="timed steps replay phase 1 from a captured hipGraph (muscle_amd.GraphedStep; one GPU, epoch < 8).  Not "
+                         "the default: measured on MI355X the replay saves 0.5 ms of 136 on B7 but serialises the weight-gradient "
+                         "side stream, which is worth 3.6 ms on B7 when launched eagerly; it is the better choice for B0-sized models")
+    ap.add_argument("--eager", action="store_true", help="(the default; kept for older command lines)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline (instrumented eager steps), the other GEMM "
+                         "arithmetic, configs and cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's loss terms and (a fixed sample of) the updated parameters "
+                         "to DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.gemm_table and not a.full:
+        ap.error("--gemm-table is part of the roofline measurement: add --full")
+
+    rank = int(os.environ.get("RANK", 0))
+    local = int(os.environ.get("LOCAL_RANK", 0))
+    world = int(os.environ.get("WORLD_SIZE", 1))
+    if world != a.gpus:
+        raise SystemExit(f"--gpus {a.gpus} but WORLD_SIZE={world}: launch N>1 with torch.distributed.run")
+    if not torch.cuda.is_available():
+        raise SystemExit("bench.py needs a ROCm GPU (the product path has no CPU fallback)")
+    import torch.distributed as dist
+    # MUSCLE_DIST_BACKEND=gloo + MUSCLE_SHARE_GPU=1: rehearsal of the N>1 flow with all ranks on one GPU (tests only)
+    backend = os.environ.get("MUSCLE_DIST_BACKEND", "nccl")
+    if os.environ.get("MUSCLE_SHARE_GPU"):
+        local = 0
+    torch.cuda.set_device(local)
+    dev = torch.device("cuda", local)
+    if world > 1:
+        if backend == "nccl":
+            dist.init_process_group("nccl", device_id=dev)
+        else:
+            dist.init_process_group(backend)
+
+    import muscle_amd
+    from muscle_amd.dist import GradAverager, broadcast_parameters
+    cfg = arch.net_cfg(a.model, False)
+    torch.manual_seed(0)
+    model = muscle_amd.MuSCLe(21, a.model, layers=3, last_pooling=False).to(dev)
+    broadcast_parameters(model)
+    opt = muscle_amd.FusedAdam(model.parameters(), lr=1e-4, weight_decay=5e-5)
+    view = a.size // 2
+    batch = make_batch(a.batch, a.size, view, 1000 + rank, dev)
+    hook = GradAverager().attach(model) if world > 1 else None     # chunks go out as backward fills the arena
+    timer = GemmTimer()
+    if a.full:
+        timer.install()
+    other = "fp32" if a.arith == "split" else "split"
+    muscle_amd.set_gemm_mode(ARITH_MODE[a.arith])
+
+    def step():
+        # ER's top-k count int(0.2 * label.sum() * H * W) (train_mcl.py:178,188) is taken INSIDE the step, on the device (the
+        # reference reads it back every iteration; a count precomputed outside the timed region would be work skipped)
+        return muscle_amd.mcl_step(model, opt, batch, a.epoch, valid_channel=batch["label"].sum(), grad_hook=hook)
+
+    if a.graph and (world > 1 or a.epoch >= 8):
+        raise SystemExit("--graph covers phase 1 on one GPU (epoch < 8)")
+    eager_step = step
+    if a.graph:
+        gstep = muscle_amd.GraphedStep(model, opt, a.epoch)
+        for _ in range(gstep.warmup + 1):          # eager settling steps + the capturing call
+            gstep(batch)
+        step = lambda: gstep(batch)                # noqa: E731  (copies the batch into the static buffers, replays)
+
+    if a.epoch >= 8:
+        _calibrate_bn(model, batch["view1"])
+    for _ in range(a.warmup):
+        step()
+
+    def barrier():
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize()
+
+    host_t0 = [0.0]
+
+    barrier()
+    t0 = time.perf_counter()
+    for _ in range(a.steps):
+        out = step()
+    barrier()
+    dt = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, out, model)
+    from muscle_amd import engine
+    overlap = engine.WGRAD_SIDE_STREAM
+    if a.full:
+        inst_steps, inst_dt, calls_main, beside = full_legs(a, timer, eager_step, barrier, cfg, other, rank, world, backend, dev)
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -486,36 +530,7 @@ def main():
         return
 
     imgs = a.batch * world * a.steps
-    gemm_ms, gemm_launches = timer.total_ms()
-    if a.gemm_table:
-        rows = timer.table(inst_steps)
-        with open(a.gemm_table, "w") as f:
-            f.write("# pointwise-GEMM launches of one %s step (%s, %dx%d, batch %d), side stream off, HIP events per launch; bound_us = max(flop / "
-                    "pipe peak, fp32 operand + result bytes / 5 TB/s); x_bound = us / bound_us\n" % (a.arith, a.model, a.size, a.size, a.batch))
-            f.write("%-26s %7s %5s %7s %5s %5s %8s %8s %7s %5s %8s %7s\n" % ("entry", "M", "N", "K", "split", "/step", "us", "ms/step", "TFLOP/s",
-                                                                          "bound", "bound_us", "x_bound"))
-            for r in rows:
-                f.write("%-26s %7d %5d %7d %5s %5.1f %8.1f %8.3f %7.1f %5s %8.1f %7.2f\n" % (
-                    r["entry"], r["M"], r["N"], r["K"], "y" if r["split"] else "n", r["per_step"], r["us"], r["ms_per_step"], r["tflops"],
-                    r["bound"], r["bound_us"], r["x_bound"]))
-            f.write("# total %.2f ms/step; at the bounds %.2f ms/step\n" % (sum(r["ms_per_step"] for r in rows),
-                                                                          sum(r["bound_us"] * r["per_step"] for r in rows) / 1e3))
     full = a.epoch >= 12
-    flops_img = pointwise_flops_per_image(cfg, a.size)
-    if full:
-        # phase 2 (train_mcl.py:196-229): two view forwards (one of them under no_grad) + one view backward
-        mv = arch.forward_macs(cfg, view)
-        sv = cfg.stem_out_size(view)
-        stem_v = 28 * cfg.stem_out * sv * sv
-        flops_img += 2 * 2 * mv["pointwise"] + 4 * mv["pointwise"] + 2 * 2 * stem_v + 2 * stem_v
-    flops = flops_img * a.batch * inst_steps
-    achieved = flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else None
-    peak, split_share = timer.blended_peak()
-    traffic, tj = None, {}
-    tpath = os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(tpath) and (a.model, a.size, a.batch, full) == ("efficientnet-b7", 448, 32, False):
-        tj = json.load(open(tpath))
-        traffic = tj.get("gemm_hbm_bytes_per_launch")     # measured for this workload only
     res = {
         "metric": "images/sec (whole node), MCL EfficientNet-B7 448x448 bs=32/GPU" if (a.model, a.size, a.batch) == ("efficientnet-b7", 448, 32)
         else f"images/sec (whole node), MCL {a.model} {a.size}x{a.size} bs={a.batch}/GPU",
@@ -532,62 +547,93 @@ def main():
                    "launch": ("hipGraph replay" if a.graph else "eager") + (", weight-gradient GEMMs on a second stream" if overlap else ""),
                    "arithmetic": f"{a.arith}: {ARITH_TEXT[a.arith]}"},
         "losses": {k: (float(v.detach()) if torch.is_tensor(v) else v) for k, v in out.items()},
-        "roofline": {"bound": "mfma",
-                     "kernel": "gemm_nt_split3_kernel<*> / gemm_nt_kernel<*> / wgrad_split_ws_kernel / wgrad_split_kernel<*> / wgrad_tile_kernel<*> / wgrad_small_kernel<*> / "
-                               "gemm_kernel<*> (the pointwise-conv GEMMs: forward, data gradient, weight gradient; stem)",
-                     "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
-                     "frac": (achieved / peak) if achieved else None, "traffic": traffic,
-                     "peak_is": f"flop-weighted over the timed launches: {split_share:.3f} of the flop ran in split arithmetic on the bf16 "
-                                f"pipe (peak {MFMA_BF16_PEAK_TFLOPS:.0f} / 6 = {SPLIT_PEAK_TFLOPS:.1f} TFLOP/s fp32-equivalent), the rest on "
-                                f"exact-fp32 MFMA (peak {MFMA_F32_PEAK_TFLOPS})",
-                     "flop_share_split": split_share,
-                     # not measured by this run: the in-kernel clock of the split forward / data-gradient kernel after 1.5 s of back-to-back
-                     # launches (tools/hip/gemm_lab stamps M K N 3, profiles/r04_planes_stamps.txt); `peak` above is quoted at 2.4 GHz
-                     "clock_held_under_load_GHz": [1.84, 2.01],
-                     "measured_over": f"{inst_steps} eager steps right after the timed region (HIP events per launch, weight-gradient "
-                                      f"side stream off; {inst_dt / inst_steps * 1e3:.1f} ms/step in that mode)",
-                     "launches_per_step": gemm_launches // max(inst_steps, 1),
-                     "avg_launch_us": gemm_ms * 1e3 / max(gemm_launches, 1),
-                     "time_share_of_step": gemm_ms * 1e-3 / inst_dt,
-                     "gemm_ms_per_step": gemm_ms / max(inst_steps, 1),
-                     "non_gemm_ms_per_step": (inst_dt * 1e3 - gemm_ms) / max(inst_steps, 1),
-                     "algorithmic_gflop_per_image": flops_img / 1e9},
     }
-    if (a.model, a.size, full) == ("efficientnet-b7", 448, False):
-        # whole-step fractions of the two ceilings of SURVEY.md section 8(d) (per GPU), and the slowest HBM-bound kernel
-        per_gpu = imgs / dt / world
-        res["roofline"]["step_frac_mfma"] = per_gpu / STEP_CEILING_MFMA_IMGS
-        res["roofline"]["step_frac_hbm"] = per_gpu / STEP_CEILING_HBM_IMGS
-        # whole-step traffic and launch count from the committed PMC / kernel-trace pass of this workload (profiles/traffic.json)
-        res["roofline"]["step_traffic_GB"] = tj.get("step_traffic_GB")
-        res["roofline"]["step_traffic_algorithmic_GB"] = 6.46 * a.batch            # minimum-materialisation schedule
-        res["roofline"]["launches_per_step_all"] = tj.get("launches_per_step_all")
-        res["roofline"]["mx_calls_per_step"] = calls_main // max(inst_steps, 1)
-    if beside is not None:
-        res["fp32_mfma" if other == "fp32" else "split_mfma"] = beside
-    dws = timer.dw_summary()
-    if dws:
-        worst = min(dws.items(), key=lambda kv: kv[1]["GBps"])
-        res["roofline"]["hbm_kernel"] = {"kernel": f"dw_bwd_fused_kernel<{worst[0][1:]}> (stride-1 depthwise backward, 3 reads + 1 write)",
-                                         "achieved": worst[1]["GBps"], "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                                         "frac": worst[1]["GBps"] / HBM_PEAK_GBPS,
-                                         "ms_per_step": worst[1]["ms"] / max(inst_steps, 1),
-                                         "all": {k: {"GBps": round(v["GBps"], 1), "ms_per_step": round(v["ms"] / max(inst_steps, 1), 3)} for k, v in dws.items()}}
-    if world == 1 and not a.no_configs and (a.model, a.size, a.batch, full) == ("efficientnet-b7", 448, 32, False):
-        del model, opt, out
-        torch.cuda.empty_cache()
-        res["configs"] = {"config2": short_run("efficientnet-b0", 16, 448, a.epoch, 10, 50, dev, 2000, graph=True)}      # BASELINE.json configs[1]
-        res["configs"]["config2"].update(ceiling_hbm=6550.0, frac_of_ceiling=res["configs"]["config2"]["value"] / 6550.0)
-        torch.cuda.empty_cache()
-        res["configs"]["stepfull"] = short_run("efficientnet-b7", 32, 448, 12, 2, 10, dev, 1000)       # epoch >= 12 gates, headline model
-        torch.cuda.empty_cache()
-        res["configs"]["config4_1gpu"] = short_run_dec(dev)                                            # BASELINE.json configs[3], one GPU
-        torch.cuda.empty_cache()
-        res["configs"]["config5"] = short_run_infer(dev)                                               # BASELINE.json configs[4]
-        torch.cuda.empty_cache()
-    muscle_amd.set_gemm_mode(0)
-    if world == 1 and not a.no_cpu_baseline:
-        res["cpu_baseline"] = cpu_baseline(a.model, a.size, view, a.epoch)
+    if a.full:
+        gemm_ms, gemm_launches = timer.total_ms()
+        if a.gemm_table:
+            rows = timer.table(inst_steps)
+            with open(a.gemm_table, "w") as f:
+                f.write("# pointwise-GEMM launches of one %s step (%s, %dx%d, batch %d), side stream off, HIP events per launch; bound_us = max(flop / "
+                        "pipe peak, fp32 operand + result bytes / 5 TB/s); x_bound = us / bound_us\n" % (a.arith, a.model, a.size, a.size, a.batch))
+                f.write("%-26s %7s %5s %7s %5s %5s %8s %8s %7s %5s %8s %7s\n" % ("entry", "M", "N", "K", "split", "/step", "us", "ms/step", "TFLOP/s",
+                                                                              "bound", "bound_us", "x_bound"))
+                for r in rows:
+                    f.write("%-26s %7d %5d %7d %5s %5.1f %8.1f %8.3f %7.1f %5s %8.1f %7.2f\n" % (
+                        r["entry"], r["M"], r["N"], r["K"], "y" if r["split"] else "n", r["per_step"], r["us"], r["ms_per_step"], r["tflops"],
+                        r["bound"], r["bound_us"], r["x_bound"]))
+                f.write("# total %.2f ms/step; at the bounds %.2f ms/step\n" % (sum(r["ms_per_step"] for r in rows),
+                                                                              sum(r["bound_us"] * r["per_step"] for r in rows) / 1e3))
+        full = a.epoch >= 12
+        flops_img = pointwise_flops_per_image(cfg, a.size)
+        if full:
+            # phase 2 (train_mcl.py:196-229): two view forwards (one of them under no_grad) + one view backward
+            mv = arch.forward_macs(cfg, view)
+            sv = cfg.stem_out_size(view)
+            stem_v = 28 * cfg.stem_out * sv * sv
+            flops_img += 2 * 2 * mv["pointwise"] + 4 * mv["pointwise"] + 2 * 2 * stem_v + 2 * stem_v
+        flops = flops_img * a.batch * inst_steps
+        achieved = flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else None
+        peak, split_share = timer.blended_peak()
+        traffic, tj = None, {}
+        tpath = os.path.join(ROOT, "profiles", "traffic.json")
+        if os.path.exists(tpath) and (a.model, a.size, a.batch, full) == ("efficientnet-b7", 448, 32, False):
+            tj = json.load(open(tpath))
+            traffic = tj.get("gemm_hbm_bytes_per_launch")     # measured for this workload only
+        res["roofline"] = {"bound": "mfma",
+                           "kernel": "gemm_nt_split3_kernel<*> / gemm_nt_kernel<*> / wgrad_split_ws_kernel / wgrad_split_kernel<*> / wgrad_tile_kernel<*> / wgrad_small_kernel<*> / "
+                                     "gemm_kernel<*> (the pointwise-conv GEMMs: forward, data gradient, weight gradient; stem)",
+                           "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
+                           "frac": (achieved / peak) if achieved else None, "traffic": traffic,
+                           "peak_is": f"flop-weighted over the timed launches: {split_share:.3f} of the flop ran in split arithmetic on the bf16 "
+                                      f"pipe (peak {MFMA_BF16_PEAK_TFLOPS:.0f} / 6 = {SPLIT_PEAK_TFLOPS:.1f} TFLOP/s fp32-equivalent), the rest on "
+                                      f"exact-fp32 MFMA (peak {MFMA_F32_PEAK_TFLOPS})",
+                           "flop_share_split": split_share,
+                           # not measured by this run: the in-kernel clock of the split forward / data-gradient kernel after 1.5 s of back-to-back
+                           # launches (tools/hip/gemm_lab stamps M K N 3, profiles/r04_planes_stamps.txt); `peak` above is quoted at 2.4 GHz
+                           "clock_held_under_load_GHz": [1.84, 2.01],
+                           "measured_over": f"{inst_steps} eager steps right after the timed region (HIP events per launch, weight-gradient "
+                                            f"side stream off; {inst_dt / inst_steps * 1e3:.1f} ms/step in that mode)",
+                           "launches_per_step": gemm_launches // max(inst_steps, 1),
+                           "avg_launch_us": gemm_ms * 1e3 / max(gemm_launches, 1),
+                           "time_share_of_step": gemm_ms * 1e-3 / inst_dt,
+                           "gemm_ms_per_step": gemm_ms / max(inst_steps, 1),
+                           "non_gemm_ms_per_step": (inst_dt * 1e3 - gemm_ms) / max(inst_steps, 1),
+                           "algorithmic_gflop_per_image": flops_img / 1e9}
+        if (a.model, a.size, full) == ("efficientnet-b7", 448, False):
+            # whole-step fractions of the two ceilings of SURVEY.md section 8(d) (per GPU), and the slowest HBM-bound kernel
+            per_gpu = imgs / dt / world
+            res["roofline"]["step_frac_mfma"] = per_gpu / STEP_CEILING_MFMA_IMGS
+            res["roofline"]["step_frac_hbm"] = per_gpu / STEP_CEILING_HBM_IMGS
+            # whole-step traffic and launch count from the committed PMC / kernel-trace pass of this workload (profiles/traffic.json)
+            res["roofline"]["step_traffic_GB"] = tj.get("step_traffic_GB")
+            res["roofline"]["step_traffic_algorithmic_GB"] = 6.46 * a.batch            # minimum-materialisation schedule
+            res["roofline"]["launches_per_step_all"] = tj.get("launches_per_step_all")
+            res["roofline"]["mx_calls_per_step"] = calls_main // max(inst_steps, 1)
+        if beside is not None:
+            res["fp32_mfma" if other == "fp32" else "split_mfma"] = beside
+        dws = timer.dw_summary()
+        if dws:
+            worst = min(dws.items(), key=lambda kv: kv[1]["GBps"])
+            res["roofline"]["hbm_kernel"] = {"kernel": f"dw_bwd_fused_kernel<{worst[0][1:]}> (stride-1 depthwise backward, 3 reads + 1 write)",
+                                             "achieved": worst[1]["GBps"], "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                                             "frac": worst[1]["GBps"] / HBM_PEAK_GBPS,
+                                             "ms_per_step": worst[1]["ms"] / max(inst_steps, 1),
+                                             "all": {k: {"GBps": round(v["GBps"], 1), "ms_per_step": round(v["ms"] / max(inst_steps, 1), 3)} for k, v in dws.items()}}
+        if world == 1 and not a.no_configs and (a.model, a.size, a.batch, full) == ("efficientnet-b7", 448, 32, False):
+            del model, opt, out
+            torch.cuda.empty_cache()
+            res["configs"] = {"config2": short_run("efficientnet-b0", 16, 448, a.epoch, 10, 50, dev, 2000, graph=True)}      # BASELINE.json configs[1]
+            res["configs"]["config2"].update(ceiling_hbm=6550.0, frac_of_ceiling=res["configs"]["config2"]["value"] / 6550.0)
+            torch.cuda.empty_cache()
+            res["configs"]["stepfull"] = short_run("efficientnet-b7", 32, 448, 12, 2, 10, dev, 1000)       # epoch >= 12 gates, headline model
+            torch.cuda.empty_cache()
+            res["configs"]["config4_1gpu"] = short_run_dec(dev)                                            # BASELINE.json configs[3], one GPU
+            torch.cuda.empty_cache()
+            res["configs"]["config5"] = short_run_infer(dev)                                               # BASELINE.json configs[4]
+            torch.cuda.empty_cache()
+        muscle_amd.set_gemm_mode(0)
+        if world == 1 and not a.no_cpu_baseline:
+            res["cpu_baseline"] = cpu_baseline(a.model, a.size, view, a.epoch)
     print(json.dumps(res))
     if world > 1:
         dist.destroy_process_group()

@@ -86,7 +86,7 @@ def test_bench_two_ranks_on_one_gpu_prints_the_contract_line():
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--model", "efficientnet-b3", "--batch", "8", "--size", "224"]
+           "--model", "efficientnet-b3", "--batch", "8", "--size", "224", "--full"]
     r = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
