@@ -311,6 +311,22 @@ int mx_infer_accum(const float* src, float* acc, int h, int w, int lds, int K, i
  * v = (v - min - 1e-6) / (max - min + 1e-6) */
 int mx_infer_norm(float* acc, int channels, long HW, void* stream);
 
+/* ---- semantic-segmentation inference (infer_seg.py:101-133 without the dense CRF; src/evaluation.py:36-68) ------------
+ * mx_seg_infer: one image, ALL passes of its multi-scale / flip list in one launch.  passes: device int64 [npass][8]
+ * {address of the pass's NHWC logits [h,w,lds] (cam='seg_lr', one sample), h, w, Hs, Ws, flip, 0, 0}, in the order of
+ * VOC12ClsDatasetMSF; every pass has row stride lds (a multiple of 4; the rows are read 16 bytes at a time, so each
+ * address is 16-byte aligned).  The table is trusted device data.  Per output pixel (Y, X) and pass:
+ *   p = softmax_K(upsample_align_corners(logits, Hs x Ws))            (MuSCLe.forward(cam='seg') + torch.softmax, :104-106)
+ *   v = resize_halfpixel(p, H x W)[Y, flip ? W-1-X : X]               (cv2.resize + np.flip of the odd passes, :109-112)
+ * then mean = sum over passes in table order / npass (:117), mean[1..K-1] *= cls_scale[1..K-1] if cls_scale (:125),
+ * pred[Y,X] = argmax_k mean (uint8, first maximum as np.argmax, :133), prob[k,Y,X] = mean (fp32 [K,H,W], NULL = not
+ * written).  1 <= K <= min(lds, 24).  No atomics: the same bits every run.
+ * mx_seg_confusion: over pixels with gt < 255 (uint8 [H,W] both), counts[k] += (TP, P, T) with P counting pred == k,
+ * T gt == k, TP both; counts int64 [K][3], accumulated across calls. */
+int mx_seg_infer(const long* passes, int npass, int lds, int K, int H, int W, const float* cls_scale, unsigned char* pred,
+                 float* prob, void* stream);
+int mx_seg_confusion(const unsigned char* pred, const unsigned char* gt, int K, int H, int W, long long* counts, void* stream);
+
 /* ---- input stage (src/data.py:215-332, src/imutils.py:143-181,376-388) ------------------------------
  * dst[n,3,Hd,Wd] (fp32, fully written) = RandomCrop container of color_norm(uint8 HWC crop n) at (top,left), CHW, zeros
  * elsewhere; src = packed crops, jobs = n x 8 int32 {src_off, sh, sw, top, left, ey | ex<<16, eh | ew<<16, source row

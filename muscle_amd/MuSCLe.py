@@ -9,7 +9,8 @@ Same constructor, same `forward(x, cam=...)` return tuples, same `state_dict()` 
   * it only runs on a ROCm GPU: on CPU tensors forward() raises (there is no fallback path);
   * parameter gradients are written to `p.grad` by the module's own backward (they are views of
     one flat fp32 arena, which is what the DP all-reduce and the fused Adam consume).
-`mode='dec'` builds the BiFPN decoder of train_muscle.py (muscle_amd/dec.py): forward(x, cam='seg'|'vis').
+`mode='dec'` builds the BiFPN decoder of train_muscle.py (muscle_amd/dec.py): forward(x, cam='seg'|'vis'), and the
+no-grad cam='seg_lr' of segmentation inference (muscle_amd/infer.py::infer_seg).
 """
 from __future__ import annotations
 
@@ -185,7 +186,7 @@ class MuSCLe(nn.Module):
 
     # ---- forward ------------------------------------------------------------------------------------
     def forward(self, x, cam="cam", drop_u: Optional[Dict[int, torch.Tensor]] = None):
-        if cam in ("seg", "vis", "seg_p3"):
+        if cam in ("seg", "vis", "seg_p3", "seg_lr"):
             if self.mode == "enc":
                 raise AttributeError("forward(cam='seg') needs MuSCLe(mode='dec') (the encoder model has no BIFPN)")
         elif cam in ("logits", "cam", "pix", "cam_lr"):
@@ -197,6 +198,14 @@ class MuSCLe(nn.Module):
             raise MuscleHipError("MuSCLe.forward runs on the HIP kernels only: move the model and input to a ROCm GPU")
         x = x.contiguous().float()
         self._save_for_backward = torch.is_grad_enabled() and cam != "vis"
+        if cam == "seg_lr":
+            # the 1/8-resolution NHWC logits [N,h,w,24] (fuse_dec before the upsample of cam='seg'; no dense_ft): the input
+            # of the fused post-processing of infer_seg.  Inference only: there is no backward through it.
+            if torch.is_grad_enabled():
+                raise RuntimeError("forward(cam='seg_lr') is inference only: call it under torch.no_grad()")
+            (seg_lr,), _, _ = self._run_forward_dec(x, "seg_lr", drop_u)
+            ops.flush_batch_counters()
+            return seg_lr
         if cam == "vis":                                   # MuSCLe.py:290-298: no_grad seg forward, returns (seg_map, p7)
             with torch.no_grad():
                 seg_map, p7 = _Forward.apply(x, self._anchor, self, "vis", drop_u)
@@ -236,6 +245,8 @@ class MuSCLe(nn.Module):
         ht.h, ht.w, ht.H, ht.W, ht.mode, ht.fcw = h, w, H, W, mode, w24
         ht.f, ht.T, ht.fs = tp, seg_lr, feats           # reuse slots: BiFPN tape, low-res logits, tap tensors
         ht.cam = p3
+        if mode == "seg_lr":
+            return (seg_lr,), tape, ht
         seg_map = ops.upsample_to_nchw(seg_lr, K, H, W)
         if mode == "vis":
             return (seg_map, tape.blocks[t[6]].out.permute(0, 3, 1, 2).contiguous()), tape, ht

@@ -258,6 +258,121 @@ __global__ __launch_bounds__(256) void infer_accum_kernel(const float* src, floa
   }
 }
 
+// ---------------------------------------------------------------------------
+// infer_seg.py:101-133 (minus the dense CRF) for one image, every pass of the multi-scale / flip list in ONE launch:
+// per pass the model's F.interpolate(align_corners=True) of the 1/8 logits to the pass's input size Hs x Ws (the
+// seg_map of cam='seg', :104), torch.softmax over the classes (:106), cv2.resize to the original H x W (half-pixel
+// centres, edge clamp, :109), np.flip of the odd passes (:112); then np.mean over the passes (:117), the optional
+// cls_label scale of channels 1..K-1 (:125) and np.argmax (:133, the first maximum wins).
+// One thread per output pixel with the K running sums in registers.  The softmax couples the channels between the two
+// resizes, so it is evaluated at each of the <= 4 source pixels of the pixel's half-pixel footprint, on the
+// align_corners logits of bil_lr's / mx_upsample_to_nchw's formula, with 16-byte loads of the NHWC rows.
+// A footprint corner of weight exactly 0 is skipped (it would add 0 * p).  The sum runs over passes in table order, then
+// over corners (fixed order, no atomics: the same bits every run).  prob is stored channel-major, coalesced per channel.
+// Measured bound by its arithmetic (<= 4 x npass softmaxes per output pixel), not by memory: 243 us for 12 passes of a
+// 500 x 375 image with or without prob (profiles/seg_infer_bench.txt).
+// ---------------------------------------------------------------------------
+#define SEG_MAXK 24
+
+// p[k] = softmax over k < K of the align_corners bilinear of src[:, :, k] at pixel (sy, sx) of the Hs x Ws map; 0 for k >= K
+__device__ __forceinline__ void seg_softmax_at(const float* src, int h, int w, int lds, int K, int Hs, int Ws, int sy, int sx,
+                                               float (&p)[SEG_MAXK]) {
+  int y0, y1, x0, x1;
+  float wy, wx;
+  bil_coord(sy, h, Hs, y0, y1, wy);
+  bil_coord(sx, w, Ws, x0, x1, wx);
+  const float *r00 = src + ((long)y0 * w + x0) * lds, *r01 = src + ((long)y0 * w + x1) * lds;
+  const float *r10 = src + ((long)y1 * w + x0) * lds, *r11 = src + ((long)y1 * w + x1) * lds;
+#pragma unroll
+  for (int q = 0; q < SEG_MAXK / 4; ++q) {
+    float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (q * 4 < K) {                         // quad q lies inside the row: K <= lds and lds % 4 == 0
+      float4 a00 = ld4(r00 + q * 4), a01 = ld4(r01 + q * 4), a10 = ld4(r10 + q * 4), a11 = ld4(r11 + q * 4);
+#define BIL(f) o.f = (1.f - wy) * ((1.f - wx) * a00.f + wx * a01.f) + wy * ((1.f - wx) * a10.f + wx * a11.f)
+      BIL(x); BIL(y); BIL(z); BIL(w);
+#undef BIL
+    }
+    p[q * 4 + 0] = o.x; p[q * 4 + 1] = o.y; p[q * 4 + 2] = o.z; p[q * 4 + 3] = o.w;
+  }
+  float m = p[0];
+#pragma unroll
+  for (int k = 1; k < SEG_MAXK; ++k)
+    if (k < K) m = fmaxf(m, p[k]);
+  float s = 0.f;
+#pragma unroll
+  for (int k = 0; k < SEG_MAXK; ++k) {
+    p[k] = (k < K) ? expf(p[k] - m) : 0.f;
+    s += p[k];
+  }
+#pragma unroll
+  for (int k = 0; k < SEG_MAXK; ++k) p[k] = p[k] / s;
+}
+
+// tab: npass x 8 int64 {address of the pass's [h,w,lds] logits, h, w, Hs, Ws, flip, 0, 0}
+__global__ __launch_bounds__(256) void seg_infer_kernel(const long* tab, int npass, int lds, int K, int H, int W,
+                                                        const float* cls, unsigned char* pred, float* prob) {
+  const long HW = (long)H * W;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < HW; i += (long)gridDim.x * 256) {
+    const int X = (int)(i % W), Y = (int)(i / W);
+    float acc[SEG_MAXK];
+#pragma unroll
+    for (int k = 0; k < SEG_MAXK; ++k) acc[k] = 0.f;
+    for (int n = 0; n < npass; ++n) {
+      const long* e = tab + n * 8;
+      const float* src = reinterpret_cast<const float*>(e[0]);
+      const int h = (int)e[1], w = (int)e[2], Hs = (int)e[3], Ws = (int)e[4];
+      const int Xr = e[5] ? (W - 1 - X) : X;          // np.flip(axis=1) after the resize
+      int y0, y1, x0, x1;
+      float wy, wx;
+      hp_coord(Y, Hs, H, y0, y1, wy);
+      hp_coord(Xr, Ws, W, x0, x1, wx);
+      for (int c = 0; c < 4; ++c) {
+        const float f = ((c & 2) ? wy : 1.f - wy) * ((c & 1) ? wx : 1.f - wx);
+        if (f == 0.f) continue;
+        float p[SEG_MAXK];
+        seg_softmax_at(src, h, w, lds, K, Hs, Ws, (c & 2) ? y1 : y0, (c & 1) ? x1 : x0, p);
+#pragma unroll
+        for (int k = 0; k < SEG_MAXK; ++k) acc[k] += f * p[k];
+      }
+    }
+    const float fn = (float)npass;
+    float best = 0.f;
+    int bk = 0;
+#pragma unroll
+    for (int k = 0; k < SEG_MAXK; ++k) {
+      if (k < K) {
+        float v = acc[k] / fn;
+        if (cls && k > 0) v *= cls[k];
+        if (prob) prob[(long)k * HW + i] = v;
+        if (k == 0 || v > best) { best = v; bk = k; }
+      }
+    }
+    pred[i] = (unsigned char)bk;
+  }
+}
+
+// src/evaluation.py:36-50 (input_type='png') for one image: over pixels with gt < 255, P[pred]++ (pred < K), T[gt]++ and
+// TP[gt] += (pred == gt) (gt < K).  counts int64 [K][3] = (TP, P, T), accumulated across images; per workgroup in LDS,
+// flushed with one integer atomic per non-zero entry.
+__global__ __launch_bounds__(256) void seg_confusion_kernel(const unsigned char* pred, const unsigned char* gt, int K, long HW,
+                                                            long long* counts) {
+  extern __shared__ int sc[];                   // [K][3]
+  for (int i = threadIdx.x; i < K * 3; i += 256) sc[i] = 0;
+  __syncthreads();
+  for (long p = blockIdx.x * 256L + threadIdx.x; p < HW; p += (long)gridDim.x * 256) {
+    const int g = gt[p], pr = pred[p];
+    if (g >= 255) continue;
+    if (pr < K) atomicAdd(&sc[pr * 3 + 1], 1);
+    if (g < K) {
+      atomicAdd(&sc[g * 3 + 2], 1);
+      if (pr == g) atomicAdd(&sc[g * 3 + 0], 1);
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < K * 3; i += 256)
+    if (sc[i]) atomicAdd((unsigned long long*)&counts[i], (unsigned long long)sc[i]);
+}
+
 // infer_mcl.py:153-158 per channel (one workgroup each): clamp at 0, min / max over the image, zero what is below
 // min + 1e-6, then (v - min - 1e-6) / (max - min + 1e-6).  In place.
 __global__ __launch_bounds__(256) void infer_norm_kernel(float* acc, long HW) {
@@ -425,6 +540,28 @@ int mx_eval_confusion(const float* pred, const float* label, const unsigned char
   if (blocks > 1024) blocks = 1024;
   hipLaunchKernelGGL(eval_confusion_kernel, dim3(blocks), dim3(256), sizeof(int) * nt * K * 3, (hipStream_t)stream, pred, label, gt,
                      thresholds, nt, K, HW, counts);
+  MX_LAUNCH_CHECK();
+  return MX_OK;
+}
+
+int mx_seg_infer(const long* passes, int npass, int lds, int K, int H, int W, const float* cls_scale, unsigned char* pred,
+                 float* prob, void* stream) {
+  MX_CHECK_ARG(passes && pred && npass > 0 && K >= 1 && K <= SEG_MAXK && K <= lds && lds % 4 == 0 && H > 0 && W > 0,
+               "seg_infer: bad args npass=%d K=%d lds=%d H=%d W=%d", npass, K, lds, H, W);
+  hipLaunchKernelGGL(seg_infer_kernel, dim3(gs((long)H * W)), dim3(256), 0, (hipStream_t)stream, passes, npass, lds, K, H, W,
+                     cls_scale, pred, prob);
+  MX_LAUNCH_CHECK();
+  return MX_OK;
+}
+
+int mx_seg_confusion(const unsigned char* pred, const unsigned char* gt, int K, int H, int W, long long* counts, void* stream) {
+  MX_CHECK_ARG(pred && gt && counts && K >= 1 && K <= 255 && H > 0 && W > 0, "seg_confusion: bad args K=%d H=%d W=%d", K, H, W);
+  const long HW = (long)H * W;
+  int blocks = (int)((HW + 256 * 8 - 1) / (256 * 8));
+  if (blocks < 1) blocks = 1;
+  if (blocks > 1024) blocks = 1024;
+  hipLaunchKernelGGL(seg_confusion_kernel, dim3(blocks), dim3(256), sizeof(int) * K * 3, (hipStream_t)stream, pred, gt, K, HW,
+                     counts);
   MX_LAUNCH_CHECK();
   return MX_OK;
 }

@@ -5,6 +5,9 @@ forks 8 processes that reload every file, argmax against the threshold, and coun
 Here each image's SGC goes `cam_maxnorm -> * label -> fp16 -> argmax vs all thresholds -> counts` in one kernel that
 accumulates an int64 [thresholds, 21, 3] table on the device; the table is read once per epoch.  Same integers, same
 `loglist` dict (per-category IoU in percent + 'mIoU').
+
+`SegEval` is the same table for segmentation maps (do_python_eval with input_type='png', the evaluation of infer_seg.py's
+PNGs): one integer confusion kernel per image over the uint8 prediction and ground truth.
 """
 from __future__ import annotations
 
@@ -20,6 +23,17 @@ categories = ['background', 'aeroplane', 'bicycle', 'bird', 'boat', 'bottle', 'b
               'diningtable', 'dog', 'horse', 'motorbike', 'person', 'pottedplant', 'sheep', 'sofa', 'train', 'tvmonitor']
 
 RAPID_THRESHOLDS = tuple(t / 100.0 for t in range(20, 52, 2))          # train_mcl.py:308-309
+
+
+def miou_loglist(counts) -> Dict[str, float]:
+    """src/evaluation.py:56-68 on an integer (TP, P, T) table [num_cls, 3]: per-category IoU in percent + 'mIoU'."""
+    c = np.asarray(counts).astype(np.int64)
+    num_cls = c.shape[0]
+    TP, P, T = c[:, 0], c[:, 1], c[:, 2]
+    iou = [TP[i] / (T[i] + P[i] - TP[i] + 1e-10) for i in range(num_cls)]
+    out = {categories[i] if i < len(categories) else str(i): iou[i] * 100 for i in range(num_cls)}
+    out['mIoU'] = np.mean(np.array(iou)) * 100
+    return out
 
 
 class RapidEval:
@@ -57,15 +71,35 @@ class RapidEval:
 
     def loglist(self, ti: int) -> Dict[str, float]:
         """do_python_eval's return value for threshold index ti (src/evaluation.py:56-68)."""
-        c = self.counts[ti].cpu().numpy().astype(np.int64)
-        TP, P, T = c[:, 0], c[:, 1], c[:, 2]
-        iou = [TP[i] / (T[i] + P[i] - TP[i] + 1e-10) for i in range(self.num_cls)]
-        out = {categories[i] if i < len(categories) else str(i): iou[i] * 100 for i in range(self.num_cls)}
-        out['mIoU'] = np.mean(np.array(iou)) * 100
-        return out
+        return miou_loglist(self.counts[ti].cpu().numpy())
 
     def best(self):
         """(max_miou, max_t) exactly as train_mcl.py:311-312 (first maximum; max_t = index*0.02 + 0.2 there)."""
         mious: List[float] = [self.loglist(i)['mIoU'] for i in range(len(self.thresholds))]
         max_miou = max(mious)
         return max_miou, self.thresholds[mious.index(max_miou)], mious
+
+
+class SegEval:
+    """do_python_eval(input_type='png') (src/evaluation.py:10-68) over segmentation maps: accumulates the int64 (TP, P, T)
+    table [num_cls, 3] on the device, one mx_seg_confusion launch per image; loglist() reads it once."""
+
+    def __init__(self, device, num_cls: int = 21):
+        self.num_cls = num_cls
+        self.counts = torch.zeros(num_cls, 3, dtype=torch.int64, device=device)
+
+    def add(self, pred: torch.Tensor, gt: torch.Tensor) -> None:
+        """pred: uint8 [H,W] class indices (infer.infer_seg); gt: uint8 [H,W] SegmentationClass png (255 = ignore)."""
+        if not self.counts.is_cuda:
+            raise MuscleHipError("SegEval.add runs on the HIP kernels only: create it with a ROCm device")
+        if pred.dim() != 2 or pred.dtype != torch.uint8 or gt.dtype != torch.uint8 or tuple(gt.shape) != tuple(pred.shape):
+            raise ValueError(f"pred and gt must be uint8 [H,W] of one shape (got {pred.dtype} {tuple(pred.shape)}, "
+                             f"{gt.dtype} {tuple(gt.shape)})")
+        H, W = pred.shape
+        dev = self.counts.device
+        call("mx_seg_confusion", ptr(pred.to(dev).contiguous()), ptr(gt.to(dev).contiguous()), self.num_cls, H, W,
+             ptr(self.counts), stream())
+
+    def loglist(self) -> Dict[str, float]:
+        """do_python_eval's return value (src/evaluation.py:56-68)."""
+        return miou_loglist(self.counts.cpu().numpy())

@@ -1,4 +1,5 @@
-"""CAM generation for one image, the loop body of infer_mcl.py:107-182, on the HIP path.
+"""CAM generation (infer_mcl.py:107-182) and semantic-segmentation inference (infer_seg.py:88-136) for one image, on the
+HIP path.
 
 Per forward pass of the multi-scale / flip list the reference moves the [1,21,Hs,Ws] maps to the host, transposes,
 cv2.resize()s them to the original image size, flips the odd passes back, drops the background channel and appends to a
@@ -9,10 +10,17 @@ normalises in place.  Only the kept channels leave the GPU.
 
 The file layout of the result is the reference's: `np.save(path, {class_index: float32[H,W]})`, read back with
 `np.load(path, allow_pickle=True).item()` by src/evaluation.py:25-33 and infer_irn.py:68-73.
+
+Segmentation inference (`infer_seg`): per pass the reference runs the decoder's cam='seg' forward, a softmax, moves the
+map to the host, cv2.resize()s it to the image size, flips the odd passes back, and after the list takes the mean, scales
+the foreground channels by the image's class scores (--cls_dir) and argmaxes.  Here the decoder is asked for its
+1/8-resolution logits (cam='seg_lr': no full-resolution seg_map and no 256-channel dense_ft), and ONE kernel over all
+passes does the upsample, softmax, resize, un-flip, mean, class scale and argmax (mx_seg_infer).  The dense CRF of
+--crf 1 is not built; `return_prob=True` hands the mean probability map to a caller that has one.
 """
 from __future__ import annotations
 
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -78,3 +86,55 @@ def save_cam_dict(path: str, d: Dict[int, np.ndarray]) -> None:
 def load_cam_dict(path: str) -> Dict[int, np.ndarray]:
     """src/evaluation.py:27: np.load(...).item()"""
     return np.load(path, allow_pickle=True).item()
+
+
+def infer_seg(model, img_list: List[torch.Tensor], H: int, W: int, cls_label=None, return_prob: bool = False
+              ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """infer_seg.py:88-133 without the CRF.  model: MuSCLe(mode='dec'); img_list: [1,3,Hs,Ws] device tensors in the order
+    of VOC12ClsDatasetMSF (scale-major, plain then flipped; data.MSFStager builds it); cls_label: optional [K] class scores
+    (entry 0, the background, is not used: :125).  Returns (pred uint8 [H,W], the fp32 mean probability map [K,H,W] if
+    return_prob else None), both on the device."""
+    if not img_list:
+        raise ValueError("infer_seg needs at least one pass")
+    model.eval()
+    if getattr(model.backbone, "_eval_fold", None) is None and hasattr(model, "fold_eval_bn"):
+        model.fold_eval_bn()              # eval BatchNorm folded into the 1x1 weights once, not per pass (train() drops it)
+    dev = img_list[0].device
+    K = model.classes
+    maps, rows = [], []                   # the low-res logits stay referenced until the one launch below is enqueued
+    lds = _CPAD
+    with torch.no_grad():
+        i = 0
+        while i < len(img_list):
+            img = img_list[i]
+            if img.dim() != 4 or img.shape[0] != 1:
+                raise ValueError("each entry of img_list is one image [1,3,Hs,Ws]")
+            # a scale and its flipped copy have the same size: one batch-2 forward (eval mode is per-sample)
+            pair = i % 2 == 0 and i + 1 < len(img_list) and img_list[i + 1].shape == img.shape
+            x = torch.cat([img, img_list[i + 1]], dim=0).float() if pair else img.float()
+            seg_lr = model(x, cam="seg_lr")                                          # NHWC [b,h,w,24]
+            _, h, w, lds = seg_lr.shape
+            for b in range(x.shape[0]):
+                rows.append([seg_lr[b].data_ptr(), h, w, img.shape[2], img.shape[3], (i + b) % 2, 0, 0])
+            maps.append(seg_lr)
+            i += x.shape[0]
+        tab = torch.tensor(rows, dtype=torch.int64).to(dev)
+        cls = None
+        if cls_label is not None:
+            cls = torch.as_tensor(np.asarray(cls_label, dtype=np.float32).reshape(-1)).to(dev)
+            if cls.numel() != K:
+                raise ValueError(f"cls_label has {cls.numel()} entries, the model {K} classes")
+        pred = torch.empty(H, W, dtype=torch.uint8, device=dev)
+        prob = torch.empty(K, H, W, dtype=torch.float32, device=dev) if return_prob else None
+        call("mx_seg_infer", ptr(tab), len(rows), lds, K, H, W, ptr(cls), ptr(pred), ptr(prob), stream())
+    return pred, prob
+
+
+def save_seg_png(path: str, pred) -> None:
+    """infer_seg.py:129-131: the class-index map as an 8-bit single-channel PNG, the file src/evaluation.py:24-25 reads
+    back with np.array(Image.open(path))."""
+    import PIL.Image
+    a = pred.cpu().numpy() if torch.is_tensor(pred) else np.asarray(pred)
+    if a.ndim != 2 or a.dtype != np.uint8:
+        raise ValueError(f"pred must be uint8 [H,W] (got {a.dtype} {a.shape})")
+    PIL.Image.fromarray(a, mode="L").save(path)

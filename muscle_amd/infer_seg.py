@@ -1,0 +1,101 @@
+"""`python -m muscle_amd.infer_seg`: the reference's infer_seg.py (semantic-segmentation inference of the trained decoder)
+on the HIP path.  Same arguments, same output files: one 8-bit class-index PNG per image of --infer_list under --out_seg.
+
+Differences a caller can see:
+  * the dense CRF (--crf 1, pydensecrf on the CPU) is not built: --crf 1 is refused with a message, and --crf defaults
+    to 0 (the reference defaults to 1);
+  * --gt_dir (new, optional): the SegmentationClass directory; prints do_python_eval's IoU table for the written maps;
+  * --num_workers and --tblog are accepted and unused (the multi-scale list is built on the device, nothing is logged).
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+from typing import List, Optional
+
+import numpy as np
+
+DEFAULT_SCALES = (0.5, 0.75, 1, 1.25, 1.5, 1.75)          # infer_seg.py:75
+
+
+def parse_args(argv: Optional[List[str]] = None):
+    ap = argparse.ArgumentParser(prog="python -m muscle_amd.infer_seg", description=__doc__.split("\n")[0])
+    ap.add_argument("--weights", required=True, type=str, help="decoder weights: a .ckpt with 'state_dict' or a state dict")
+    ap.add_argument("--infer_list", default="data/val.txt", type=str)
+    ap.add_argument("--num_workers", default=8, type=int, help="unused")
+    ap.add_argument("--num_classes", default=21, type=int)
+    ap.add_argument("--tblog", default="logs/infer", type=str, help="unused")
+    ap.add_argument("--voc12_root", default="data/VOC2012", type=str)
+    ap.add_argument("--cls_dir", default=None, type=str, help="per-image class scores <name>.npy scaling channels 1..K-1")
+    ap.add_argument("--out_seg", default=None, type=str)
+    ap.add_argument("--crf", default=0, type=int, help="0 only: the dense CRF is not built")
+    ap.add_argument("--bifpn", default=3, type=int)
+    ap.add_argument("--pretrained", default="b7", type=str)
+    ap.add_argument("--gt_dir", default=None, type=str, help="SegmentationClass directory: print the IoU table")
+    ap.add_argument("--scales", default=",".join(str(s) for s in DEFAULT_SCALES), type=str)
+    args = ap.parse_args(argv)
+    if args.crf:
+        ap.error("--crf 1: the dense CRF (pydensecrf, CPU) is not built on the HIP path; run with --crf 0, or call "
+                 "muscle_amd.infer.infer_seg(..., return_prob=True) and apply a CRF to the returned mean probability map")
+    return args
+
+
+def load_weights(model, path: str):
+    """infer_seg.py:67-70: a '.ckpt' file holds {'state_dict': ...}, anything else is the state dict; strict=False."""
+    import torch
+    sd = torch.load(path, map_location="cpu")
+    if ".ckpt" in path:
+        sd = sd["state_dict"]
+    return model.load_state_dict(sd, strict=False)
+
+
+def read_names(list_path: str) -> List[str]:
+    """src/data.py:load_img_name_list."""
+    return [ln.split(" ")[0].split("/")[-1].split(".")[0] for ln in open(list_path).read().splitlines()]
+
+
+def main(argv: Optional[List[str]] = None) -> int:
+    args = parse_args(argv)
+    import PIL.Image
+    import torch
+    import muscle_amd
+    from muscle_amd.data import MSFStager
+    from muscle_amd.evaluation import SegEval, categories
+    from muscle_amd.infer import infer_seg, save_seg_png
+
+    dev = torch.device("cuda:0")
+    model = muscle_amd.MuSCLe(num_classes=args.num_classes, pretrained="efficientnet-" + args.pretrained, layers=args.bifpn,
+                              MemoryEfficient=True, last_pooling=True, mode="dec")
+    load_weights(model, args.weights)
+    model = model.to(dev).eval()
+    scales = tuple(float(s) for s in args.scales.split(","))
+    stager = MSFStager(dev)
+    ev = SegEval(dev, args.num_classes) if args.gt_dir else None
+    if args.out_seg is not None:
+        os.makedirs(args.out_seg, exist_ok=True)
+    for it, name in enumerate(read_names(args.infer_list)):
+        img = PIL.Image.open(os.path.join(args.voc12_root, "JPEGImages", name + ".jpg")).convert("RGB")
+        W, H = img.size
+        cls = None
+        if args.cls_dir:
+            cls = np.load(os.path.join(args.cls_dir, name + ".npy"), allow_pickle=True).squeeze()
+        pred, _ = infer_seg(model, stager(img, scales), H, W, cls_label=cls)
+        if args.out_seg is not None:
+            save_seg_png(os.path.join(args.out_seg, name + ".png"), pred)
+        if ev is not None:
+            gt = np.array(PIL.Image.open(os.path.join(args.gt_dir, name + ".png")))
+            ev.add(pred, torch.from_numpy(gt).to(dev))
+        print(name, it, flush=True)
+    if ev is not None:                                    # do_python_eval(printlog=True), src/evaluation.py:72-83
+        log = ev.loglist()
+        for i in range(args.num_classes):
+            nm = categories[i] if i < len(categories) else str(i)
+            print('%11s:%7.3f%%' % (nm, log[nm]), end='\t' if i % 2 != 1 else '\n')
+        print('\n======================================================')
+        print('%11s:%7.3f%%' % ('mIoU', log['mIoU']), flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
