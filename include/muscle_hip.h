@@ -507,6 +507,28 @@ int mx_field_terms(const float* sim, const float* simm, int nslots, int k, float
 int mx_field_scatter(const float* feat, const float* gfeat, const int* pts, int npts, int mode, int h, int w, const float* gup,
                      float* gdense, float* gpt /* mode 1: npts*CH floats of scratch */, int nsamples, int CH, int H, int W, void* stream);
 
+/* ---- dense CRF of segmentation inference (src/imutils.py:439-456, crf_inference) ---------------------------------- */
+
+/* Mean-field inference of the fully connected CRF that src/imutils.py:439-456 hands to pydensecrf (Gaussian + bilateral
+ * Potts terms, diagonal kernels, symmetric normalisation), with the sums over j evaluated EXACTLY over a square window
+ * instead of on the permutohedral lattice:
+ *   k_m(i,j) = exp(-0.5 |f_m(i) - f_m(j)|^2)   for |x_i-x_j| <= R_m and |y_i-y_j| <= R_m (j == i included), else 0
+ *   f_gauss = (x, y) / sxy_g;   f_bilateral = (x / sxy_b, y / sxy_b, r / srgb, g / srgb, b / srgb)
+ *   R_m = ceil(trunc * sxy_m);  trunc <= 0, or R_m >= max(H, W) - 1: all pairs
+ *   n_m(i) = 1 / sqrt(sum_j k_m(i,j) + 1e-20)
+ *   U[l,i] = -log(clip(confidence * prob[l,i] + (1 - confidence) / L, 1e-5, 1));   Q_0 = softmax_l(-U)
+ *   Q_{s+1} = softmax_l(-U + sum_m w_m n_m(i) sum_j k_m(i,j) n_m(j) Q_s[l,j])      s = 0 .. t-1
+ * fp32, no atomics, fixed summation order.  1 <= L <= 24.  workspace: mx_crf_workspace_bytes(L, H, W) bytes, 16-byte
+ * aligned, contents need not survive between calls.  Nothing synchronises with the host. */
+long mx_crf_workspace_bytes(int L, int H, int W);                       /* < 0: bad arguments */
+/* src/imutils.py:439-456: the two normalisers n_gauss, n_bilateral [H,W] of the uint8 image rgb [H,W,3] */
+int mx_crf_normalizers(const unsigned char* rgb, int H, int W, float sxy_g, float sxy_b, float srgb, float trunc, void* workspace,
+                       float* n_g, float* n_b, void* stream);
+/* src/imutils.py:439-456: the whole inference; t = 0 returns Q_0.  q_out: Q_t fp32 [L,H,W] or NULL; pred: argmax_l Q_t uint8
+ * [H,W] (first maximum wins) or NULL; at least one of the two */
+int mx_crf_inference(const unsigned char* rgb, const float* prob, int L, int H, int W, int t, float confidence, float sxy_g, float w_g,
+                     float sxy_b, float srgb, float w_b, float trunc, void* workspace, float* q_out, unsigned char* pred, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

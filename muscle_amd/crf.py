@@ -1,0 +1,88 @@
+"""Dense CRF refinement of a probability map (src/imutils.py:439-456, `crf_inference`) on the HIP path.
+
+The reference hands the model below to pydensecrf (Kraehenbuehl & Koltun 2011, pydensecrf defaults: diagonal kernels,
+symmetric normalisation, Potts compatibility):
+
+    U[l,i]   = -log(clip(confidence * probs[l,i] + (1 - confidence) / L, 1e-5, 1))
+    k_m(i,j) = exp(-0.5 * |f_m(i) - f_m(j)|^2)                  m in {gauss, bilateral}; j == i included
+               f_gauss = (x, y) / (3 / scale_factor),  weight 1
+               f_bilateral = (x / s, y / s, r / 10, g / 10, b / 10) with s = 32 / scale_factor,  weight 10
+    n_m(i)   = 1 / sqrt(sum_j k_m(i,j) + 1e-20)
+    Q_0      = softmax_l(-U)
+    Q_{s+1}  = softmax_l(-U + sum_m w_m n_m(i) sum_j k_m(i,j) n_m(j) Q_s[l,j])         s = 0 .. t-1
+
+pydensecrf evaluates the sums over j approximately, on a permutohedral lattice.  Here they are evaluated exactly over a
+square window: j contributes to i iff |x_i - x_j| <= R_m and |y_i - y_j| <= R_m with R_m = ceil(trunc * sxy_m); trunc <= 0,
+or a window that covers the image, means all pairs.  The window is part of the model (it enters n_m too).  Label maps are
+therefore not bit-identical with pydensecrf's; what is pinned is this model against an fp64 restatement
+(tests/crf_ref.py).  With the default trunc = 4 the windowed result differs from the all-pairs one by less than 1e-4.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional, Tuple
+
+import numpy as np
+import torch
+
+from ._lib import MuscleHipError, call, lib, ptr, stream
+
+# imutils.py:452-453: addPairwiseGaussian(sxy=3/scale_factor, compat=1), addPairwiseBilateral(sxy=32/scale_factor, srgb=10, compat=10)
+GAUSS_SXY, GAUSS_W = 3.0, 1.0
+BILATERAL_SXY, BILATERAL_SRGB, BILATERAL_W = 32.0, 10.0, 10.0
+
+_ws: Dict[Tuple[int, int, int], torch.Tensor] = {}
+
+
+def _workspace(dev: torch.device, H: int, W: int) -> torch.Tensor:
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(), H, W)
+    ws = _ws.get(key)
+    if ws is None:
+        nbytes = lib().mx_crf_workspace_bytes(1, H, W)
+        if nbytes < 0:
+            raise MuscleHipError(f"mx_crf_workspace_bytes failed: {lib().mx_last_error().decode()}")
+        if len(_ws) >= 4:                                      # a few image sizes at most stay resident
+            _ws.pop(next(iter(_ws)))
+        ws = _ws[key] = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    return ws
+
+
+def _device_image(img, dev: torch.device) -> torch.Tensor:
+    t = img if torch.is_tensor(img) else torch.from_numpy(np.array(img))       # a copy: PIL-backed arrays are read-only
+    if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:
+        raise ValueError(f"img must be uint8 [H,W,3] (got {t.dtype} {tuple(t.shape)})")
+    return t.to(dev).contiguous()
+
+
+def crf_run(img, probs, t: int, scale_factor: float, labels: int, confidence: float, trunc: float, want_q: bool = True,
+            want_pred: bool = False) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """One enqueue of mx_crf_inference on the current stream; returns (Q fp32 [L,H,W] or None, argmax uint8 [H,W] or None)."""
+    if torch.is_tensor(probs):
+        p = probs
+        dev = p.device if p.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    else:
+        p = torch.as_tensor(np.ascontiguousarray(probs, dtype=np.float32))
+        dev = torch.device("cuda", torch.cuda.current_device())
+    if p.dim() != 3 or p.shape[0] != labels:
+        raise ValueError(f"probs must be [labels={labels},H,W] (got {tuple(p.shape)})")
+    p = p.to(dev, torch.float32).contiguous()
+    L, H, W = p.shape
+    im = _device_image(img, dev)
+    if tuple(im.shape[:2]) != (H, W):
+        raise ValueError(f"img is {tuple(im.shape[:2])}, probs {(H, W)}")
+    if not scale_factor > 0:
+        raise ValueError("scale_factor must be positive")
+    with torch.cuda.device(dev):
+        ws = _workspace(dev, H, W)
+        q = torch.empty(L, H, W, dtype=torch.float32, device=dev) if want_q else None
+        pred = torch.empty(H, W, dtype=torch.uint8, device=dev) if want_pred else None
+        call("mx_crf_inference", ptr(im), ptr(p), L, H, W, int(t), float(confidence), GAUSS_SXY / scale_factor, GAUSS_W,
+             BILATERAL_SXY / scale_factor, BILATERAL_SRGB, BILATERAL_W, float(trunc), ptr(ws), ptr(q), ptr(pred), stream())
+    return q, pred
+
+
+def crf_inference(img, probs, t: int = 2, scale_factor: float = 1.5, labels: int = 21, confidence: float = 0.5, *,
+                  trunc: float = 4.0) -> torch.Tensor:
+    """src/imutils.py:439 (same name, arguments and defaults).  img: uint8 [H,W,3] numpy array or tensor; probs: [labels,H,W]
+    numpy array or tensor (it may be un-normalised: the formula is applied as it stands).  Returns Q_t fp32 [labels,H,W] on
+    the device."""
+    return crf_run(img, probs, t, scale_factor, labels, confidence, trunc)[0]

@@ -15,8 +15,13 @@ Segmentation inference (`infer_seg`): per pass the reference runs the decoder's 
 map to the host, cv2.resize()s it to the image size, flips the odd passes back, and after the list takes the mean, scales
 the foreground channels by the image's class scores (--cls_dir) and argmaxes.  Here the decoder is asked for its
 1/8-resolution logits (cam='seg_lr': no full-resolution seg_map and no 256-channel dense_ft), and ONE kernel over all
-passes does the upsample, softmax, resize, un-flip, mean, class scale and argmax (mx_seg_infer).  The dense CRF of
---crf 1 is not built; `return_prob=True` hands the mean probability map to a caller that has one.
+passes does the upsample, softmax, resize, un-flip, mean, class scale and argmax (mx_seg_infer).
+
+The dense CRF of infer_seg.py:128-129 (`crf_img=`): the reference hands the mean map and the original image to pydensecrf
+(imutils.crf_inference, t=4), a lattice-filter approximation of the fully connected CRF on the CPU.  Here the same model
+runs on the device with its pairwise sums evaluated exactly over a square window of half-width ceil(trunc * sxy)
+(muscle_amd/crf.py states the model; mx_crf_inference).  Label maps are therefore not bit-identical with pydensecrf's; at
+trunc = 4 the windowed result is within 1e-4 of the all-pairs one.
 """
 from __future__ import annotations
 
@@ -88,12 +93,15 @@ def load_cam_dict(path: str) -> Dict[int, np.ndarray]:
     return np.load(path, allow_pickle=True).item()
 
 
-def infer_seg(model, img_list: List[torch.Tensor], H: int, W: int, cls_label=None, return_prob: bool = False
-              ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
-    """infer_seg.py:88-133 without the CRF.  model: MuSCLe(mode='dec'); img_list: [1,3,Hs,Ws] device tensors in the order
+def infer_seg(model, img_list: List[torch.Tensor], H: int, W: int, cls_label=None, return_prob: bool = False, crf_img=None,
+              crf_t: int = 4, crf_trunc: float = 4.0) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """infer_seg.py:88-133.  model: MuSCLe(mode='dec'); img_list: [1,3,Hs,Ws] device tensors in the order
     of VOC12ClsDatasetMSF (scale-major, plain then flipped; data.MSFStager builds it); cls_label: optional [K] class scores
     (entry 0, the background, is not used: :125).  Returns (pred uint8 [H,W], the fp32 mean probability map [K,H,W] if
-    return_prob else None), both on the device."""
+    return_prob else None), both on the device.
+    crf_img: the original uint8 image [H,W,3] (numpy or tensor).  With it the dense CRF of :128-129 runs on the mean map
+    (crf.crf_inference with crf_t iterations, scale_factor 1.5, window crf_trunc): pred is argmax Q and the returned map
+    is Q.  Without it nothing of the CRF runs and the result is what it was before the CRF existed, bit for bit."""
     if not img_list:
         raise ValueError("infer_seg needs at least one pass")
     model.eval()
@@ -125,8 +133,11 @@ def infer_seg(model, img_list: List[torch.Tensor], H: int, W: int, cls_label=Non
             if cls.numel() != K:
                 raise ValueError(f"cls_label has {cls.numel()} entries, the model {K} classes")
         pred = torch.empty(H, W, dtype=torch.uint8, device=dev)
-        prob = torch.empty(K, H, W, dtype=torch.float32, device=dev) if return_prob else None
+        prob = torch.empty(K, H, W, dtype=torch.float32, device=dev) if return_prob or crf_img is not None else None
         call("mx_seg_infer", ptr(tab), len(rows), lds, K, H, W, ptr(cls), ptr(pred), ptr(prob), stream())
+        if crf_img is not None:
+            from .crf import crf_run
+            prob, pred = crf_run(crf_img, prob, crf_t, 1.5, K, 0.5, crf_trunc, want_q=return_prob, want_pred=True)
     return pred, prob
 
 

@@ -2,8 +2,10 @@
 on the HIP path.  Same arguments, same output files: one 8-bit class-index PNG per image of --infer_list under --out_seg.
 
 Differences a caller can see:
-  * the dense CRF (--crf 1, pydensecrf on the CPU) is not built: --crf 1 is refused with a message, and --crf defaults
-    to 0 (the reference defaults to 1);
+  * the dense CRF: --crf 2 [--crf_trunc 4.0] runs the reference's CRF model (imutils.crf_inference, t=4) on the GPU with
+    its pairwise sums evaluated exactly over a square window (muscle_amd/crf.py).  --crf 1 in the reference means
+    pydensecrf's lattice filter on the CPU, whose label maps are not reproduced bit for bit: it stays refused, with a
+    message that points to --crf 2, and --crf defaults to 0 (the reference defaults to 1);
   * --gt_dir (new, optional): the SegmentationClass directory; prints do_python_eval's IoU table for the written maps;
   * --num_workers and --tblog are accepted and unused (the multi-scale list is built on the device, nothing is logged).
 """
@@ -29,15 +31,17 @@ def parse_args(argv: Optional[List[str]] = None):
     ap.add_argument("--voc12_root", default="data/VOC2012", type=str)
     ap.add_argument("--cls_dir", default=None, type=str, help="per-image class scores <name>.npy scaling channels 1..K-1")
     ap.add_argument("--out_seg", default=None, type=str)
-    ap.add_argument("--crf", default=0, type=int, help="0 only: the dense CRF is not built")
+    ap.add_argument("--crf", default=0, type=int, help="0: none; 2: the dense CRF on the GPU, exact windowed kernels (1 = pydensecrf: refused)")
+    ap.add_argument("--crf_trunc", default=4.0, type=float, help="--crf 2: window half-width in units of sxy (<= 0: all pairs)")
     ap.add_argument("--bifpn", default=3, type=int)
     ap.add_argument("--pretrained", default="b7", type=str)
     ap.add_argument("--gt_dir", default=None, type=str, help="SegmentationClass directory: print the IoU table")
     ap.add_argument("--scales", default=",".join(str(s) for s in DEFAULT_SCALES), type=str)
     args = ap.parse_args(argv)
-    if args.crf:
-        ap.error("--crf 1: the dense CRF (pydensecrf, CPU) is not built on the HIP path; run with --crf 0, or call "
-                 "muscle_amd.infer.infer_seg(..., return_prob=True) and apply a CRF to the returned mean probability map")
+    if args.crf not in (0, 2):
+        ap.error(f"--crf {args.crf}: pydensecrf's lattice-filter CRF (--crf 1 of the reference, CPU) is not built on the HIP "
+                 "path; --crf 2 runs the same CRF model with exact windowed kernels on the GPU (label maps close to, not "
+                 "bit-identical with, pydensecrf's), --crf 0 runs none")
     return args
 
 
@@ -80,7 +84,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         cls = None
         if args.cls_dir:
             cls = np.load(os.path.join(args.cls_dir, name + ".npy"), allow_pickle=True).squeeze()
-        pred, _ = infer_seg(model, stager(img, scales), H, W, cls_label=cls)
+        crf_img = np.asarray(img, dtype=np.uint8) if args.crf == 2 else None                # infer_seg.py:128-129, t=4
+        pred, _ = infer_seg(model, stager(img, scales), H, W, cls_label=cls, crf_img=crf_img, crf_t=4, crf_trunc=args.crf_trunc)
         if args.out_seg is not None:
             save_seg_png(os.path.join(args.out_seg, name + ".png"), pred)
         if ev is not None:
