@@ -529,6 +529,48 @@ int mx_crf_normalizers(const unsigned char* rgb, int H, int W, float sxy_g, floa
 int mx_crf_inference(const unsigned char* rgb, const float* prob, int L, int H, int W, int t, float confidence, float sxy_g, float w_g,
                      float sxy_b, float srgb, float w_b, float trunc, void* workspace, float* q_out, unsigned char* pred, void* stream);
 
+/* ---- the IRN edge / displacement network of infer_irn.py:66 (src/backbones/resnet50_irn.py:215-232 on src/backbones/resnet50.py),
+ * inference only.  Its 1x1 convolutions are mx_pw_fwd calls; these are the pieces the EfficientNet path has no use for.
+ * fp32, fixed summation order, no atomics. */
+
+/* resnet50.py:24-25 (`conv2` of a bottleneck), forward: Y[N,Ho,Wo,Co] = [relu](conv3x3(X[N,H,W,Ci], padding 1, stride 1|2) + bias[co]),
+ * Ho = (H-1)/stride + 1.  Implicit GEMM on v_mfma_f32_16x16x4_f32 over an LDS-staged halo tile; EXACT fp32 always (does not follow
+ * mx_set_gemm_mode).  Wp = the packed weight [9][Co][Ci] (tap = ky*3+kx major, Cin contiguous) that mx_conv3x3_pack writes from the
+ * state_dict layout W[Co,Ci,3,3], each output channel multiplied by scale[co] if scale (the folded BatchNorm; pack once per
+ * checkpoint load).  Ci % 4 == 0, Co % 4 == 0; bias may be NULL. */
+int mx_conv3x3_pack(const float* W, const float* scale, float* Wp, int Co, int Ci, void* stream);
+int mx_conv3x3_fwd(const float* X, const float* Wp, const float* bias, float* Y, int N, int H, int W, int Ci, int Co, int stride,
+                   int relu, void* stream);
+
+/* resnet50.py:62 (7x7 stride-2 pad-3 stem) as patches for mx_pw_fwd: out[(n,oy,ox), ci*49+ky*7+kx] = img[n,ci,2oy-3+ky,2ox-3+kx]
+ * (NCHW image [N,3,H,W]), zero outside the image, rows of 148 floats (147 + 0).  Ho x Wo is the stem's output grid for the
+ * crop_size frame the image sits in: the zero padding of resnet50_irn.py:225 is the same bounds test, no padded copy exists. */
+int mx_stem7_im2col(const float* img, float* out, int N, int H, int W, int Ho, int Wo, void* stream);
+/* resnet50.py:66: MaxPool2d(3, 2, 1) on NHWC, y [N,(H-1)/2+1,(W-1)/2+1,C]; padding never wins.  C % 4 == 0. */
+int mx_maxpool3s2(const float* x, float* y, int N, int H, int W, int C, void* stream);
+/* resnet50.py:80-84: the rows a stride-2 1x1 convolution reads, y[n,oy,ox,:] = x[n,2oy,2ox,:], y [N,(H-1)/2+1,(W-1)/2+1,C] */
+int mx_gather_s2(const float* x, float* y, int N, int H, int W, int C, void* stream);
+
+/* resnet50_irn.py:22-92, nn.GroupNorm(G, C): stat[n][g] = {mean, 1/sqrt(biased var + eps)} over the HW x C/G values of each
+ * (sample, group) of X [N,HW,ldx]; fp64 sums in a fixed order.  ws: mx_gn_stats_ws bytes of plain scratch.  (C/G) % 4 == 0. */
+long mx_gn_stats_ws(int N, int HW, int G);
+int mx_gn_stats(const float* X, int N, int HW, int C, int ldx, int G, float eps, void* ws, long ws_bytes, float* stat, void* stream);
+/* The rest of a head in the reference's order GroupNorm -> Upsample -> crop -> ReLU (resnet50_irn.py:32-37,118-120), into a channel
+ * slice of the concatenation (:121,129,130):
+ * dst[n,y,x,coff+c] = [relu] bilinear_halfpixel(gamma[c]*(src[n,:,:,c] - mean)*rstd + beta[c], x scale)[y,x],  y < Hd <= Hs*scale,
+ * x < Wd <= Ws*scale; scale in {1,2,4} (align_corners=False); src [N,Hs,Ws,C] dense, dst rows of ldd floats. */
+int mx_gn_resize(const float* src, const float* stat, const float* gamma, const float* beta, float* dst, int N, int Hs, int Ws, int C,
+                 int G, int scale, int Hd, int Wd, int ldd, int coff, int relu, void* stream);
+
+/* infer_irn.py:76: dst[c] = F.interpolate(src[c], size=(Hd,Wd), mode='bilinear', align_corners=False) on planar [C,H,W] maps */
+int mx_resize_planar_halfpixel(const float* src, float* dst, int C, int Hs, int Ws, int Hd, int Wd, void* stream);
+
+/* resnet50_irn.py:227-230 + :107: e [2,Hf,Wf,lde] (channel 0 = fc_edge6's output), d [2,Hf,Wf,ldd] (channels 0,1 = fc_dp7's last
+ * convolution), mean [2] = mean_shift.running_mean: edge[y,x] = sigmoid(e[0,y,x]/2 + e[1,y,w-1-x]/2), dp[c,y,x] = d[0,y,x,c] - mean[c]
+ * for the top-left h x w crop; edge [h,w], dp [2,h,w]. */
+int mx_irn_net_finish(const float* e, int lde, const float* d, int ldd, const float* mean, int Hf, int Wf, int h, int w, float* edge,
+                      float* dp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,7 @@
 Public names mirror the reference's `src/__init__.py:1-6` for the path that is built: the MuSCLe model (CAM-encoder
 and decoder modes), the MCL loss callables, `edge.FieldLoss`, the loop bodies (`mcl_step`, `muscle_step`) and the fused
 optimiser; `muscle_amd.infer` (CAM generation), `muscle_amd.evaluation` (per-epoch mIoU sweep) and
-`muscle_amd.indexing` (IRN random walk) cover the scripts around the training loop.  Importing the package never needs
+`muscle_amd.indexing` (IRN random walk) and `muscle_amd.irn` (the IRN network, `EdgeDisplacement`, and `infer_irn`) cover the scripts around the training loop.  Importing the package never needs
 a GPU; running anything does.
 """
 from .MuSCLe import MuSCLe  # noqa: F401
@@ -21,3 +21,4 @@ __all__ = ["MuSCLe", "FocalLoss", "Log_Sum_Exp_Pairwise_Loss", "MultiLabelSoftMa
 from .graph import GraphedStep  # noqa: F401,E402
 from .ops import get_gemm_mode, set_gemm_mode  # noqa: F401,E402
 from . import data  # noqa: F401,E402  (input path: two-view sampler + device-side color_norm / crop stage)
+from .irn import EdgeDisplacement  # noqa: F401,E402  (the IRN edge / displacement network of infer_irn.py)

@@ -1,0 +1,71 @@
+"""`python -m muscle_amd.infer_irn`: the reference's infer_irn.py (IRN boundary map + random walk -> pseudo labels) on the
+HIP path.  Same arguments, same output files: `<sem_seg_out_dir>_png/<name>.png`, the label map as a palette PNG with the VOC
+colour map, and with --soft_output 1 instead `<sem_seg_out_dir>/<name>.npy`, float16 [H,W,21].
+
+Differences a caller can see:
+  * --irn_network is accepted and ignored: the one network the reference ships (src.backbones.resnet50_irn) is built in;
+  * nothing is downloaded: --irn_weights_name must name a checkpoint (the reference fetches ImageNet weights first and then
+    overwrites them with the checkpoint).
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+from typing import List, Optional
+
+import numpy as np
+
+
+def parse_args(argv: Optional[List[str]] = None):
+    ap = argparse.ArgumentParser(prog="python -m muscle_amd.infer_irn", description=__doc__.split("\n")[0])
+    ap.add_argument("--beta", default=8, type=int)
+    ap.add_argument("--exp_times", default=6, type=int, help="the random walk is performed 2^exp_times times")
+    ap.add_argument("--sem_seg_bg_thres", default=0.35, type=float)
+    ap.add_argument("--irn_network", default="src.backbones.resnet50_irn", type=str, help="ignored (see the note)")
+    ap.add_argument("--irn_weights_name", required=True, type=str, help="IRN checkpoint (a state dict)")
+    ap.add_argument("--cam_dir", required=True, type=str)
+    ap.add_argument("--sem_seg_out_dir", default="./irn_rw", type=str)
+    ap.add_argument("--voc12_root", default="data/VOC2012", type=str)
+    ap.add_argument("--infer_list", default="data/train.txt", type=str)
+    ap.add_argument("--soft_output", default=0, type=int, help="write float16 soft pseudo labels instead of the PNG")
+    args = ap.parse_args(argv)
+    if args.irn_network != ap.get_default("irn_network"):
+        print(f"[muscle_amd] note: --irn_network {args.irn_network} ignored; the ResNet-50 IRN is the one network built here",
+              file=sys.stderr)
+    return args
+
+
+def main(argv: Optional[List[str]] = None) -> int:
+    args = parse_args(argv)
+    import PIL.Image
+    import torch
+    from muscle_amd.data import MSFStager
+    from muscle_amd.infer import load_cam_dict
+    from muscle_amd.infer_seg import read_names
+    from muscle_amd.irn import EdgeDisplacement, infer_irn, save_palette_png
+
+    dev = torch.device("cuda:0")
+    model = EdgeDisplacement()
+    model.load_state_dict(torch.load(args.irn_weights_name, map_location="cpu"), strict=False)        # infer_irn.py:41
+    model = model.to(dev).eval()
+    stager = MSFStager(dev)
+    if args.soft_output:
+        os.makedirs(args.sem_seg_out_dir, exist_ok=True)
+    os.makedirs(args.sem_seg_out_dir + "_png", exist_ok=True)
+    for it, name in enumerate(read_names(args.infer_list)):
+        img = PIL.Image.open(os.path.join(args.voc12_root, "JPEGImages", name + ".jpg")).convert("RGB")
+        pair = torch.cat(stager(img, (1.0,)), dim=0)                                                 # image + flip, color_norm'ed
+        cam = load_cam_dict(os.path.join(args.cam_dir, name + ".npy"))
+        res = infer_irn(model, pair, cam, beta=args.beta, exp_times=args.exp_times, bg_thres=args.sem_seg_bg_thres,
+                        soft_output=bool(args.soft_output))
+        if args.soft_output:
+            np.save(os.path.join(args.sem_seg_out_dir, name + ".npy"), res[1].cpu().numpy())
+        else:
+            save_palette_png(os.path.join(args.sem_seg_out_dir + "_png", name + ".png"), res)
+        print(name, it, flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

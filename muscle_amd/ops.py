@@ -702,3 +702,81 @@ def ew(op, a, b=None, y=None, alpha=1.0, out=None):
 def bcast_add(X2d, v, alpha, rows_per_sample):
     rows, C = X2d.shape
     call("mx_bcast_add", ptr(X2d), ptr(v), float(alpha), rows, C, rows_per_sample, stream())
+
+
+# ---- IRN edge / displacement network (csrc/irn_net.hip) -------------------------------------------------------
+def conv3x3_pack(W, scale=None):
+    """W [Co,Ci,3,3] (state_dict layout) -> the packed [9,Co,Ci] weight of conv3x3, rows multiplied by scale[co] if given."""
+    Co, Ci = W.shape[:2]
+    Wp = _f32(9, Co, Ci, device=W.device)
+    call("mx_conv3x3_pack", ptr(W.contiguous()), ptr(scale), ptr(Wp), Co, Ci, stream())
+    return Wp
+
+
+def conv3x3(X, Wp, *, bias=None, stride=1, relu=False):
+    """X [N,H,W,Ci] NHWC, Wp from conv3x3_pack -> [N,Ho,Wo,Co]; padding 1, exact fp32 on the matrix pipe."""
+    N, H, W, Ci = X.shape
+    Co = Wp.shape[1]
+    if Wp.shape[0] != 9 or Wp.shape[2] != Ci:
+        raise ValueError(f"conv3x3: packed weight {tuple(Wp.shape)} does not fit {Ci} input channels")
+    Y = _f32(N, (H - 1) // stride + 1, (W - 1) // stride + 1, Co, device=X.device)
+    call("mx_conv3x3_fwd", ptr(X), ptr(Wp), ptr(bias), ptr(Y), N, H, W, Ci, Co, int(stride), int(relu), stream())
+    return Y
+
+
+def stem7_im2col(img, Ho, Wo):
+    """img [N,3,H,W] NCHW -> [N*Ho*Wo, 148] patches of the 7x7 stride-2 pad-3 stem, zero outside the image."""
+    N, _, H, W = img.shape
+    out = _f32(N * Ho * Wo, 148, device=img.device)
+    call("mx_stem7_im2col", ptr(img), ptr(out), N, H, W, Ho, Wo, stream())
+    return out
+
+
+def maxpool3s2(X):
+    N, H, W, C = X.shape
+    Y = _f32(N, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C, device=X.device)
+    call("mx_maxpool3s2", ptr(X), ptr(Y), N, H, W, C, stream())
+    return Y
+
+
+def gather_s2(X):
+    N, H, W, C = X.shape
+    Y = _f32(N, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C, device=X.device)
+    call("mx_gather_s2", ptr(X), ptr(Y), N, H, W, C, stream())
+    return Y
+
+
+def gn_stats(X, G, eps=1e-5):
+    """X [N,H,W,C] -> [N,G,2] (mean, rstd) of nn.GroupNorm(G, C)."""
+    N, H, W, C = X.shape
+    nbytes = int(lib().mx_gn_stats_ws(N, H * W, G))
+    ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=X.device)
+    stat = _f32(N, G, 2, device=X.device)
+    call("mx_gn_stats", ptr(X), N, H * W, C, C, G, float(eps), ptr(ws), nbytes, ptr(stat), stream())
+    return stat
+
+
+def gn_resize(X, stat, gamma, beta, dst, coff, scale, relu=True):
+    """GroupNorm apply -> x `scale` half-pixel bilinear -> crop to dst's H x W -> ReLU, into channels [coff, coff+C) of dst."""
+    N, Hs, Ws, C = X.shape
+    _, Hd, Wd, ldd = dst.shape
+    call("mx_gn_resize", ptr(X), ptr(stat), ptr(gamma), ptr(beta), ptr(dst), N, Hs, Ws, C, stat.shape[1], int(scale), Hd, Wd, ldd,
+         int(coff), int(relu), stream())
+    return dst
+
+
+def resize_planar_halfpixel(src, Hd, Wd):
+    """src [C,H,W] -> [C,Hd,Wd], F.interpolate(mode='bilinear', align_corners=False)."""
+    C, Hs, Ws = src.shape
+    dst = _f32(C, Hd, Wd, device=src.device)
+    call("mx_resize_planar_halfpixel", ptr(src), ptr(dst), C, Hs, Ws, Hd, Wd, stream())
+    return dst
+
+
+def irn_net_finish(e, d, mean, h, w):
+    """e [2,Hf,Wf,lde], d [2,Hf,Wf,ldd] -> (edge [1,h,w], dp [2,h,w]) (resnet50_irn.py:227-230)."""
+    _, Hf, Wf, lde = e.shape
+    edge = _f32(1, h, w, device=e.device)
+    dp = _f32(2, h, w, device=e.device)
+    call("mx_irn_net_finish", ptr(e), lde, ptr(d), d.shape[3], ptr(mean), Hf, Wf, h, w, ptr(edge), ptr(dp), stream())
+    return edge, dp

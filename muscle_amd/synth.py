@@ -214,3 +214,145 @@ def synth_soft_mask(label: np.ndarray, size: int, seed: int = 0) -> np.ndarray:
             d = np.sqrt((yy - cy) ** 2 + (xx - cx) ** 2)
             m[i, c + 1] = np.clip(1.0 - d / r, 0.0, 1.0).astype(np.float32)
     return m
+
+
+# ---------------------------------------------------------------------------
+# IRN edge / displacement network (src/backbones/resnet50_irn.py on src/backbones/resnet50.py)
+# ---------------------------------------------------------------------------
+_IRN_LAYERS = ((64, 3, 1), (128, 4, 2), (256, 6, 2), (512, 3, 1))       # planes, blocks, stride of layer1..4 (strides (2,2,2,1))
+_IRN_EDGE = ((64, 32, 4), (256, 32, 4), (512, 32, 4), (1024, 32, 4), (2048, 32, 4))                  # Cin, Cout, groups
+_IRN_DP = ((64, 64, 8), (256, 128, 16), (512, 256, 16), (1024, 256, 16), (2048, 256, 16), (768, 256, 16), (448, 256, 16))
+
+
+def irn_canonical_spec() -> Dict[str, Tuple[int, ...]]:
+    """{key: shape} of every DISTINCT tensor of the reference's EdgeDisplacement, under its first name."""
+    spec: Dict[str, Tuple[int, ...]] = {}
+
+    def bn(prefix, c):
+        for leaf in ("weight", "bias", "running_mean", "running_var"):
+            spec[f"{prefix}.{leaf}"] = (c,)
+        spec[prefix + ".num_batches_tracked"] = ()
+
+    spec["resnet50.conv1.weight"] = (64, 3, 7, 7)
+    bn("resnet50.bn1", 64)
+    inplanes = 64
+    for li, (planes, blocks, stride) in enumerate(_IRN_LAYERS, 1):
+        for b in range(blocks):
+            p = f"resnet50.layer{li}.{b}."
+            spec[p + "conv1.weight"] = (planes, inplanes, 1, 1)
+            bn(p + "bn1", planes)
+            spec[p + "conv2.weight"] = (planes, planes, 3, 3)
+            bn(p + "bn2", planes)
+            spec[p + "conv3.weight"] = (planes * 4, planes, 1, 1)
+            bn(p + "bn3", planes * 4)
+            if b == 0:
+                spec[p + "downsample.0.weight"] = (planes * 4, inplanes, 1, 1)
+                bn(p + "downsample.1", planes * 4)
+            inplanes = planes * 4
+    spec["mean_shift.running_mean"] = (2,)
+    for i, (ci, co, _g) in enumerate(_IRN_EDGE, 1):
+        spec[f"fc_edge{i}.0.weight"] = (co, ci, 1, 1)
+        spec[f"fc_edge{i}.1.weight"] = (co,)
+        spec[f"fc_edge{i}.1.bias"] = (co,)
+    spec["fc_edge6.weight"] = (1, 160, 1, 1)
+    spec["fc_edge6.bias"] = (1,)
+    for i, (ci, co, _g) in enumerate(_IRN_DP, 1):
+        spec[f"fc_dp{i}.0.weight"] = (co, ci, 1, 1)
+        spec[f"fc_dp{i}.1.weight"] = (co,)
+        spec[f"fc_dp{i}.1.bias"] = (co,)
+    spec["fc_dp7.3.weight"] = (2, 256, 1, 1)
+    return spec
+
+
+def irn_aliases(key: str):
+    """Every other name the reference's state_dict() carries the tensor `key` under: the same sub-modules are registered as
+    resnet50.* and stage1..5.* and backbone.*, fc_edge* and edge_layers.*, fc_dp* and dp_layers.*, mean_shift and fc_dp7.4
+    (resnet50_irn.py:14-19,91-96)."""
+    out = []
+    if key.startswith("resnet50."):
+        rest = key[len("resnet50."):]
+        head, tail = rest.split(".", 1)
+        if head == "conv1":
+            st = "stage1.0." + tail
+        elif head == "bn1":
+            st = "stage1.1." + tail
+        else:
+            st = f"stage{int(head[len('layer'):]) + 1}.0.{tail}"
+        out.append(st)
+        si, stail = st.split(".", 1)
+        out.append(f"backbone.{int(si[len('stage'):]) - 1}.{stail}")
+    elif key.startswith("fc_edge"):
+        head, tail = key.split(".", 1)
+        out.append(f"edge_layers.{int(head[len('fc_edge'):]) - 1}.{tail}")
+    elif key.startswith("fc_dp"):
+        head, tail = key.split(".", 1)
+        out.append(f"dp_layers.{int(head[len('fc_dp'):]) - 1}.{tail}")
+    elif key == "mean_shift.running_mean":
+        out += ["fc_dp7.4.running_mean", "dp_layers.6.4.running_mean"]
+    return out
+
+
+def irn_state_dict_spec() -> Dict[str, Tuple[int, ...]]:
+    """{key: shape} of the reference's EdgeDisplacement().state_dict(): every tensor under all of its names."""
+    spec: Dict[str, Tuple[int, ...]] = {}
+    for k, shape in irn_canonical_spec().items():
+        spec[k] = shape
+        for a in irn_aliases(k):
+            spec[a] = shape
+    return spec
+
+
+def irn_state_dict(seed: int = 0) -> Dict[str, np.ndarray]:
+    """Synthetic IRN weights, every alias holding its tensor's values.  Scales are chosen so that sixteen residual blocks with
+    frozen BatchNorm statistics neither blow up nor die and the edge sigmoid stays off its rails: He-scaled convolutions, BatchNorm
+    weight in [0.5, 0.9] (the block-closing bn3 and the down-sample BatchNorm in [0.3, 0.5]), running_var in [0.8, 1.25],
+    small running_mean / bias."""
+    out: Dict[str, np.ndarray] = {}
+    for key, shape in irn_canonical_spec().items():
+        leaf = key.rsplit(".", 1)[-1]
+        is_bn = ".bn" in key or ".downsample.1" in key
+        if leaf == "num_batches_tracked":
+            v = np.zeros((), dtype=np.int64)
+        elif key == "mean_shift.running_mean":
+            v = (0.05 * normal(seed, key, shape)).astype(np.float32)
+        elif leaf == "running_mean":
+            v = (0.1 * normal(seed, key, shape)).astype(np.float32)
+        elif leaf == "running_var":
+            v = (0.8 + 0.45 * uniform(seed, key, shape)).astype(np.float32)
+        elif len(shape) == 1 and leaf == "weight" and is_bn:
+            closing = ".bn3." in key or ".downsample.1." in key
+            lo, span = (0.3, 0.2) if closing else (0.5, 0.4)
+            v = (lo + span * uniform(seed, key, shape)).astype(np.float32)
+        elif len(shape) == 1 and leaf == "weight":           # GroupNorm weight
+            v = (0.75 + 0.5 * uniform(seed, key, shape)).astype(np.float32)
+        elif len(shape) == 1:                                 # BatchNorm / GroupNorm bias, fc_edge6.bias
+            v = (0.1 * normal(seed, key, shape)).astype(np.float32)
+        else:
+            fan_in = int(np.prod(shape[1:]))
+            gain = 4.0 if key == "fc_edge6.weight" else 1.0 if key == "fc_dp7.3.weight" else np.sqrt(2.0)   # (4: spreads the edge logits)
+            v = (gain / np.sqrt(fan_in) * normal(seed, key, shape)).astype(np.float32)
+        out[key] = v
+        for a in irn_aliases(key):
+            out[a] = v
+    return out
+
+
+def irn_image_pair(h: int, w: int, seed: int = 0) -> np.ndarray:
+    """[2,3,h,w] float32: a smooth colour-normalised image and its horizontal flip (VOC12ClsDatasetMSF at scale 1)."""
+    img = normal(seed, "irn_img", (3, h, w))
+    for _ in range(2):                                        # a little spatial correlation, like a photograph
+        img = (img + np.roll(img, 1, 1) + np.roll(img, 1, 2) + np.roll(np.roll(img, 1, 1), 1, 2)) / 4.0
+    img = (img / img.std()).astype(np.float32)
+    return np.ascontiguousarray(np.stack([img, img[:, :, ::-1]]))
+
+
+def irn_cam_dict(h: int, w: int, seed: int = 0, classes=(2, 7, 14)) -> Dict[int, np.ndarray]:
+    """{class: float32 [h,w]} CAMs as infer_mcl.py stores them: one soft blob per class, maximum 1."""
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
+    out: Dict[int, np.ndarray] = {}
+    for i, c in enumerate(classes):
+        u = uniform(seed, f"irn_cam:{c}", (3,))
+        cy, cx = (0.2 + 0.6 * ((i + u[0]) / len(classes))) * h, (0.15 + 0.7 * u[1]) * w
+        r = (0.22 + 0.12 * u[2]) * min(h, w)
+        out[int(c)] = np.clip(1.0 - np.sqrt((yy - cy) ** 2 + (xx - cx) ** 2) / (2.0 * r), 0.0, 1.0).astype(np.float32)
+    return out
