@@ -349,6 +349,24 @@ int mx_color_jitter(unsigned char* src, const int* jobs, unsigned long long* sum
 int mx_resample(const unsigned char* src, const int* jobs, const int* tabs, unsigned char* tmp, unsigned char* dst, int n,
                 int max_pixels, void* stream);
 
+/* ---- input stage of decoder training (VOC12SegDataset.__getitem__, src/data.py:93-123) ----------------------------------
+ * mx_mask_stage: dst[n,C,S,S] (fp32, fully written) = the soft pseudo-label of item n after RandomResizeLongWithMask's
+ * skimage.transform.resize (src/imutils.py:52: Gaussian anti-alias filter + bilinear warp, 'mirror' boundary),
+ * RandomCropWithMask's zero container (src/imutils.py:114-116), RandomHorizontalFlipWithMask (src/imutils.py:288-290) and
+ * HWC_to_CHW (src/data.py:122).  The resize is evaluated only inside the crop window, from one weight row per output row
+ * and column that the host folds from both operators (muscle_amd/segdata.py:mask_axis_table).
+ * src: the shipped source rows of every item, channel-last [sh,sw,C], float16 (what infer_irn --soft_output 1 writes) or
+ * float32; jobs: n x 16 int32 {byte offset into src, sh, sw, 1 = float32 source, top, left, ch, cw (the window inside the
+ * container), flip, ky, kx (taps per row / column), ty_off, tx_off (int32 words into tabs), 0, 0, 0}; tabs at t*_off:
+ * start[ch | cw] (first source row / column, relative to the shipped rows) then [ch | cw][k] float32 weights.
+ * span_cap >= the longest run of source columns 64 neighbouring window columns read (start[x+63] + kx - start[x]); it
+ * sizes the LDS tile.  fp32 accumulation in a fixed order, no atomics. */
+int mx_mask_stage(const void* src, const int* jobs, const int* tabs, float* dst, int n, int C, int S, int span_cap, void* stream);
+/* mx_input_stage (color_norm src/imutils.py:383-388, crop container src/imutils.py:110-112, CHW, fp32) plus the flip of
+ * src/imutils.py:288-289; jobs: n x 8 int32 {src_off, sh, sw, top, left, source row stride in pixels or 0 = sw, flip, 0}.
+ * Bit-exact with the numpy expressions. */
+int mx_seg_input_stage(const unsigned char* src, const int* jobs, float* dst, int n, int Hd, int Wd, void* stream);
+
 /* ---- IRN random-walk propagation (src/indexing.py:77-142 as called by infer_irn.py:76).
  * mx_irn_affinity: dense[n4][ld] (zero-filled here) <- symmetric affinity 1 - max(edge along the straight path) for every
  *   pixel pair joined by one of the nd search directions, unit diagonal; edge [h,w]; pcoord = int32 (dy,dx) pairs of all

@@ -1,0 +1,129 @@
+// Input stage of the decoder-training loop (reference: src/data.py:93-123, src/imutils.py:35-53, :80-118, :283-292, :383-388):
+// what VOC12SegDataset.__getitem__ does per item on the host - skimage.transform.resize of the [H,W,21] soft label (a Gaussian
+// anti-alias filter + a bilinear warp over the WHOLE rescaled label in float64), RandomCropWithMask's zero container,
+// RandomHorizontalFlipWithMask, HWC -> CHW - as one batched kernel that computes the resized label only inside the crop
+// window, and the image half of the same transforms (color_norm, container, flip, CHW, fp32 cast).
+//
+// The resize is separable and linear: per axis the host folds `bilinear o gaussian` (both with ndimage's 'mirror' boundary)
+// into one row of K = 2 + 2 * radius weights per output coordinate (muscle_amd/segdata.py:mask_axis_table), so
+//   out[c, y, x] = sum_i wy[y][i] * sum_j wx[x][j] * src[sy[y] + i, sx[x] + j, c].
+// The source is channel-last (a 42-byte pixel for 21 float16 channels) and the output channel-first: a workgroup takes 64
+// output pixels of one output row, runs the vertical pass over the contiguous run of source pixels they need (whole pixel
+// rows, consecutive lanes on consecutive elements) into LDS, and the horizontal pass reads LDS pixel-major and writes 64
+// consecutive floats per channel.  fp32 accumulation in a fixed order, no atomics: the same bits every run.
+#include "common.h"
+#include <hip/hip_fp16.h>
+
+// src_off: byte offset of the shipped source rows [sh, sw, C] (float16, or float32 when f32 != 0); the crop window
+// [ch, cw] of the resized label goes to (top, left) of the [S, S] container, mirrored along X when flip != 0;
+// ty_off / tx_off (int32 words into tabs): start[n] (first source row / column of each window row / column, relative to
+// the shipped rows) followed by n * k float32 weights.
+struct MaskJob { int src_off, sh, sw, f32, top, left, ch, cw, flip, ky, kx, ty_off, tx_off, pad0, pad1, pad2; };
+
+__device__ __forceinline__ float mask_ld(const unsigned char* base, long i, int f32) {
+  return f32 ? ((const float*)base)[i] : __half2float(((const __half*)base)[i]);
+}
+
+__global__ __launch_bounds__(256) void mask_stage_kernel(const unsigned char* __restrict__ src, const MaskJob* __restrict__ jobs,
+                                                         const int* __restrict__ tabs, float* __restrict__ dst, int C, int S,
+                                                         int span_cap) {
+  extern __shared__ float v[];                              // [span][C | 1]: the vertically filtered source pixels of this tile
+  const MaskJob jb = jobs[blockIdx.z];
+  const int y = blockIdx.y, x0 = blockIdx.x * 64, tid = threadIdx.x;
+  const int stride = C | 1;
+  const long plane = (long)S * S;
+  float* out = dst + (long)blockIdx.z * C * plane + (long)y * S;
+  const int ty = y - jb.top;
+  const int xa = max(x0, jb.left), xb = min(min(x0 + 64, S), jb.left + jb.cw);       // window columns inside this tile
+  const bool live = ty >= 0 && ty < jb.ch && xa < xb;       // uniform over the workgroup
+  const int* sx = tabs + jb.tx_off;
+  int span0 = 0, span = 0;
+  if (live) {
+    span0 = min(max(sx[xa - jb.left], 0), jb.sw);
+    const int span1 = min(max(sx[xb - 1 - jb.left] + jb.kx, span0), jb.sw);
+    span = min(span1 - span0, span_cap);
+    const int* sy = tabs + jb.ty_off;
+    const float* wy = (const float*)(sy + jb.ch) + (long)ty * jb.ky;
+    const int ys = sy[ty];
+    const unsigned char* base = src + jb.src_off;
+    for (int e = tid; e < span * C; e += 256) {
+      float acc = 0.f;
+      for (int i = 0; i < jb.ky; ++i) {
+        const int r = min(max(ys + i, 0), jb.sh - 1);
+        acc += wy[i] * mask_ld(base, ((long)r * jb.sw + span0) * C + e, jb.f32);
+      }
+      const int px = e / C;
+      v[px * stride + (e - px * C)] = acc;
+    }
+    __syncthreads();
+  }
+  const int xo = x0 + (tid & 63);
+  if (xo >= S) return;
+  const int xw = jb.flip ? S - 1 - xo : xo;                 // np.fliplr of the CONTAINER (src/imutils.py:289-290)
+  const int tx = xo - jb.left;
+  const bool in = live && tx >= 0 && tx < jb.cw;
+  int rel = 0;
+  const float* wx = nullptr;
+  if (in) {
+    rel = sx[tx] - span0;
+    wx = (const float*)(sx + jb.cw) + (long)tx * jb.kx;
+  }
+  for (int c = tid >> 6; c < C; c += 4) {
+    float acc = 0.f;                                        // RandomCropWithMask's container is zero outside the window
+    if (in)
+      for (int j = 0; j < jb.kx; ++j) {
+        const int p = rel + j;
+        if (p >= 0 && p < span) acc += wx[j] * v[p * stride + c];
+      }
+    out[c * plane + xw] = acc;
+  }
+}
+
+// mx_input_stage's job plus the flip bit of RandomHorizontalFlipWithMask
+struct SegInputJob { int src_off, sh, sw, top, left, sstride, flip, pad; };
+
+__global__ __launch_bounds__(256) void seg_input_stage_kernel(const unsigned char* __restrict__ src, const SegInputJob* __restrict__ jobs,
+                                                              float* __restrict__ dst, int Hd, int Wd) {
+  const SegInputJob jb = jobs[blockIdx.y];
+  const long plane = (long)Hd * Wd;
+  float* out = dst + (long)blockIdx.y * 3 * plane;
+  const double mean[3] = {0.485, 0.456, 0.406}, stdv[3] = {0.229, 0.224, 0.225};
+  for (long p = blockIdx.x * 256L + threadIdx.x; p < plane; p += (long)gridDim.x * 256) {
+    const int y = (int)(p / Wd), x = (int)(p - (long)y * Wd);
+    const int sy = y - jb.top, sx = (jb.flip ? Wd - 1 - x : x) - jb.left;
+    float v[3] = {0.f, 0.f, 0.f};
+    if (sy >= 0 && sy < jb.sh && sx >= 0 && sx < jb.sw) {
+      const unsigned char* px = src + jb.src_off + ((long)sy * (jb.sstride > 0 ? jb.sstride : jb.sw) + sx) * 3;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) v[c] = (float)(((double)px[c] / 255.0 - mean[c]) / stdv[c]);   // imutils.py:383-388
+    }
+    out[p] = v[0]; out[plane + p] = v[1]; out[2 * plane + p] = v[2];
+  }
+}
+
+extern "C" {
+
+int mx_mask_stage(const void* src, const int* jobs, const int* tabs, float* dst, int n, int C, int S, int span_cap, void* stream) {
+  MX_CHECK_ARG(src && jobs && tabs && dst, "mask_stage: null pointer");
+  MX_CHECK_ARG(n > 0 && n <= 65535 && C > 0 && S > 0 && S <= 65535, "mask_stage: bad extents n=%d C=%d S=%d", n, C, S);
+  const long lds = (long)span_cap * (C | 1) * 4;
+  MX_CHECK_ARG(span_cap > 0 && lds <= 65536, "mask_stage: span_cap=%d x C=%d does not fit 64 KiB of LDS (a stronger downscale than the stage is built for)",
+               span_cap, C);
+  hipLaunchKernelGGL(mask_stage_kernel, dim3(cdiv(S, 64), S, n), dim3(256), (size_t)lds, (hipStream_t)stream, (const unsigned char*)src,
+                     (const MaskJob*)jobs, tabs, dst, C, S, span_cap);
+  MX_LAUNCH_CHECK();
+  return MX_OK;
+}
+
+int mx_seg_input_stage(const unsigned char* src, const int* jobs, float* dst, int n, int Hd, int Wd, void* stream) {
+  MX_CHECK_ARG(src && jobs && dst, "seg_input_stage: null pointer");
+  MX_CHECK_ARG(n > 0 && Hd > 0 && Wd > 0, "seg_input_stage: bad extents n=%d Hd=%d Wd=%d", n, Hd, Wd);
+  const long plane = (long)Hd * Wd;
+  int bx = cdiv(plane, 256);
+  if (bx > 64) bx = 64;
+  hipLaunchKernelGGL(seg_input_stage_kernel, dim3(bx, n), dim3(256), 0, (hipStream_t)stream, src, (const SegInputJob*)jobs, dst, Hd, Wd);
+  MX_LAUNCH_CHECK();
+  return MX_OK;
+}
+
+}  // extern "C"

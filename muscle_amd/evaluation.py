@@ -8,6 +8,8 @@ accumulates an int64 [thresholds, 21, 3] table on the device; the table is read 
 
 `SegEval` is the same table for segmentation maps (do_python_eval with input_type='png', the evaluation of infer_seg.py's
 PNGs): one integer confusion kernel per image over the uint8 prediction and ground truth.
+
+`SegValidation` / `validate_seg` are the per-epoch validation of train_muscle.py:224-283 on top of `infer.infer_seg` and `SegEval`.
 """
 from __future__ import annotations
 
@@ -103,3 +105,53 @@ class SegEval:
     def loglist(self) -> Dict[str, float]:
         """do_python_eval's return value (src/evaluation.py:56-68)."""
         return miou_loglist(self.counts.cpu().numpy())
+
+
+class SegValidation:
+    """The per-epoch validation of train_muscle.py:224-283 on the device: per image the single scale-1, un-flipped pass of
+    the eval list (`img_list[:1]`), softmax, resize to the ground truth's size, optional class-score scaling (--cls_dir,
+    :262-264), optional dense CRF with t=1 (:266-267; the exact windowed CRF of muscle_amd.crf), argmax, and the (TP, P, T)
+    counts of :270-276 in a `SegEval` table.  `miou()` is :278-280: mean over classes of TP / (T + P - TP + 1e-10), a
+    fraction (the value ReduceLROnPlateau is stepped with), not a percentage."""
+
+    def __init__(self, device, num_cls: int = 21, cls_dir=None, crf: bool = False, crf_trunc: float = 4.0):
+        from .data import MSFStager
+        self.dev, self.cls_dir, self.crf, self.crf_trunc = device, cls_dir, bool(crf), crf_trunc
+        self.stager = MSFStager(device)
+        self.table = SegEval(device, num_cls)
+
+    def reset(self) -> None:
+        self.table.counts.zero_()
+
+    def add(self, model, pil_img, gt, name=None) -> torch.Tensor:
+        """pil_img: the RGB image; gt: uint8 [H,W] SegmentationClass map (255 = ignore); name: the image's name, needed
+        with cls_dir (`<cls_dir>/<name>.npy`).  Returns the uint8 prediction [H,W] on the device."""
+        import os
+        from .infer import infer_seg
+        gt = np.asarray(gt)
+        H, W = gt.shape
+        cls = None
+        if self.cls_dir:
+            cls = np.load(os.path.join(self.cls_dir, name + '.npy'), allow_pickle=True).squeeze()
+        crf_img = np.asarray(pil_img, dtype=np.uint8) if self.crf else None
+        pred, _ = infer_seg(model, self.stager(pil_img, (1,))[:1], H, W, cls_label=cls, crf_img=crf_img, crf_t=1,
+                            crf_trunc=self.crf_trunc)
+        self.table.add(pred, torch.from_numpy(np.ascontiguousarray(gt, dtype=np.uint8)).to(self.dev))
+        return pred
+
+    def miou(self) -> float:
+        return float(miou_loglist(self.table.counts.cpu().numpy())['mIoU']) / 100.0
+
+
+def validate_seg(model, names: Sequence[str], voc12_root: str, device, num_cls: int = 21, cls_dir=None, crf: bool = False) -> float:
+    """train_muscle.py:224-283 over the images `names` of a VOC tree; leaves the model in eval mode (as the script does
+    until the next epoch's model.train())."""
+    import os
+    import PIL.Image
+    model.eval()
+    val = SegValidation(device, num_cls, cls_dir=cls_dir, crf=crf)
+    for name in names:
+        img = PIL.Image.open(os.path.join(voc12_root, 'JPEGImages', name + '.jpg')).convert('RGB')
+        gt = np.array(PIL.Image.open(os.path.join(voc12_root, 'SegmentationClass', name + '.png')))
+        val.add(model, img, gt, name)
+    return val.miou()

@@ -1,0 +1,321 @@
+"""Input path of the decoder-training loop: the reference's `VOC12SegDataset` (src/data.py:69-123) as `train_muscle.py:119-130`
+uses it (`mask_type='soft'`), with the per-pixel work moved to the GPU on the host-plan / stager pattern of `muscle_amd.data`.
+
+What the reference does per item in a DataLoader worker:
+    img  = ColorJitter(0.1, 0.1, 0.1, 0.05)(PIL image)                                  torch RNG          data.py:81,105
+    scale = random.uniform(min_scale, max_scale); target = (round(w*scale), round(h*scale))               imutils.py:43-46
+    img  = img.resize(target, BILINEAR);  mask = skimage.transform.resize(float64 [H,W,21], target[::-1])  imutils.py:48-52
+    img  = color_norm(np.asarray(img))                                                                    data.py:108
+    img, mask = RandomCropWithMask(crop)(img, mask)       random.randrange: width first, then height      imutils.py:85-118
+    img, mask = RandomHorizontalFlipWithMask()(img, mask) random.getrandbits(1), np.fliplr of both        imutils.py:287-292
+    CHW                                                                                                   data.py:121-122
+The skimage resize alone filters and warps 21 channels of the WHOLE rescaled label in float64 (up to 875 x 656 x 21 at scale
+1.75) of which the crop keeps 448 x 448.
+
+Here `plan_seg_item` makes the same draws from the same generators in the same order and computes geometry and weight tables
+only; `SegStager` ships the decoded uint8 image and the source rows of the label the crop window reads (float16 as
+`muscle_amd.infer_irn --soft_output 1` writes them) in ONE pinned copy per batch, and the device does the pixel work:
+`mx_color_jitter` -> `mx_resample` (Pillow's bilinear, bit-exact) -> `mx_seg_input_stage` for the image, `mx_mask_stage` for
+the label.
+
+skimage.transform.resize (0.16.2, defaults order=1, mode='reflect', anti_aliasing=True, clip=True) is restated from its
+published source: `scipy.ndimage.gaussian_filter(mask, sigma, mode='mirror')` with sigma = max(0, (in/out - 1)/2) per spatial
+axis, then a bilinear sample at (Y + 0.5) * in/out - 0.5 with out-of-range taps mirrored about the edge pixel's centre; the
+final clip is a no-op for a convex combination.  Both operators are separable and linear, so per axis they fold into one row
+of 2 + 2 * radius weights per output coordinate (`mask_axis_table`).  skimage is not installed where this was built: the
+tables are pinned against scipy.ndimage (tests/segdata_ref.py), not against skimage itself.
+"""
+from __future__ import annotations
+
+import os
+import random
+from typing import Dict, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from ._lib import call, stream
+from .data import _keep, color_jitter_params, random_crop_box, resample_tables
+
+JITTER = (0.1, 0.1, 0.1, 0.05)          # src/data.py:81
+
+
+def _mirror(i, n: int):
+    """scipy.ndimage's 'mirror' (skimage's 'reflect'): reflection about the centre of the edge pixels, period 2n - 2."""
+    if n == 1:
+        return np.zeros_like(i)
+    p = 2 * n - 2
+    i = np.abs(i) % p
+    return np.where(i >= n, p - i, i)
+
+
+def mask_axis_table(n_in: int, n_out: int, lo: int = 0, cnt: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """One axis of skimage.transform.resize(order=1, mode='reflect', anti_aliasing=True) for the output coordinates
+    lo .. lo + cnt - 1 of n_out, as (start int32 [cnt], weights float64 [cnt, K]):
+        out[lo + t] = sum_j weights[t, j] * in[start[t] + j],   0 <= start[t], start[t] + K <= n_in.
+    K = min(n_in, 2 + 2 * radius): the two bilinear taps, each widened by scipy's Gaussian window (truncate 4.0), the mirror
+    boundary of both folded in.  start is non-decreasing."""
+    cnt = n_out - lo if cnt is None else cnt
+    factor = n_in / n_out
+    sigma = max(0.0, (factor - 1.0) / 2.0)
+    if sigma > 1e-15:                                       # scipy.ndimage.gaussian_filter skips an axis below that
+        radius = int(4.0 * sigma + 0.5)
+        x = np.arange(-radius, radius + 1, dtype=np.float64)
+        phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+        phi = phi / phi.sum()
+    else:
+        radius, phi = 0, np.ones(1)
+    r = (np.arange(lo, lo + cnt, dtype=np.float64) + 0.5) * factor - 0.5
+    f = np.floor(r)
+    t = r - f
+    f = f.astype(np.int64)
+    k = np.arange(-radius, radius + 1, dtype=np.int64)
+    # tap b of the bilinear sample reads the filtered signal at mirror(f + b), which is sum_k phi[k] * in[mirror(. + k)]
+    idx = np.concatenate([_mirror(_mirror(f + b, n_in)[:, None] + k[None, :], n_in) for b in (0, 1)], axis=1)
+    wgt = np.concatenate([(1.0 - t)[:, None] * phi[None, :], t[:, None] * phi[None, :]], axis=1)
+    K = min(n_in, 2 + 2 * radius)
+    start = np.clip(np.minimum(idx.min(axis=1), n_in - K), 0, None)
+    rel = idx - start[:, None]
+    if rel.min() < 0 or rel.max() >= K:
+        raise AssertionError("mask_axis_table: taps outside their window")
+    start = np.maximum.accumulate(start)                    # (already monotone; states the contract)
+    w = np.zeros((cnt, K), dtype=np.float64)
+    np.add.at(w, (np.repeat(np.arange(cnt), idx.shape[1]), rel.reshape(-1)), wgt.reshape(-1))
+    return start.astype(np.int32), w
+
+
+class SegItemPlan:
+    """Sources + geometry of one decoder-training item, ready for `SegStager`."""
+    __slots__ = ("img_u8", "jitter", "scale", "resize_to", "tables", "img_crop", "place", "flip",
+                 "mask_src", "mask_y", "mask_x", "span_cap")
+    # img_u8: the ORIGINAL decoded image [h,w,3]; jitter: ColorJitter parameters or None; resize_to: (W, H) of the rescale;
+    # tables: Pillow's bilinear coefficient tables for it; img_crop = (top, left, ch, cw): RandomCropWithMask's window inside
+    # the rescaled image / label; place = (top, left) of the window inside the [crop, crop] container; flip: fliplr of the
+    # containers; mask_src: the source rows [r0:r1] of the label the window reads (float16 / float32, [rows, W, C]);
+    # mask_y / mask_x = (start, weights float32) of mask_axis_table for the window, start_y relative to r0;
+    # span_cap: the longest run of source columns 64 neighbouring window columns read.
+
+
+def plan_seg_item(pil_img, soft_mask: np.ndarray, min_scale: float = 0.5, max_scale: float = 1.5, crop_size: int = 448,
+                  augment: bool = True) -> SegItemPlan:
+    """Host side of VOC12SegDataset.__getitem__ (src/data.py:104-112) for one decoded RGB image and its soft label [H,W,C]:
+    the draws in the reference's order - ColorJitter parameters (torch), scale (random.uniform), crop box (random.randrange,
+    width then height), flip (random.getrandbits) - and the tables of both resizes.  No pixel is touched.
+    augment=False leaves the ColorJitter (and its draws) out; scale, crop and flip stay."""
+    if soft_mask.ndim != 3:
+        raise ValueError(f"soft mask must be [H,W,C] (got {soft_mask.shape})")
+    p = SegItemPlan()
+    w, h = pil_img.size
+    p.jitter = color_jitter_params(*JITTER) if augment else None
+    p.scale = random.uniform(min_scale, max_scale)
+    tw, th = round(w * p.scale), round(h * p.scale)
+    if tw < 1 or th < 1:
+        raise ValueError(f"scale {p.scale} leaves nothing of a {w}x{h} image")
+    p.resize_to = (tw, th)
+    ct, cl, it, il, ch, cw = random_crop_box(th, tw, crop_size)
+    p.flip = bool(random.getrandbits(1))
+    p.img_crop, p.place = (it, il, ch, cw), (ct, cl)
+    p.img_u8 = np.ascontiguousarray(np.asarray(pil_img))
+    p.tables = resample_tables(w, h, tw, th, "bilinear")
+    hm, wm = soft_mask.shape[:2]
+    sy, wy = mask_axis_table(hm, th, it, ch)
+    sx, wx = mask_axis_table(wm, tw, il, cw)
+    r0, r1 = int(sy.min()), int(sy.max()) + wy.shape[1]
+    src = soft_mask[r0:r1]
+    if src.dtype not in (np.float16, np.float32):           # float64 files: rounded to fp32 (6e-8 relative)
+        src = src.astype(np.float32)
+    p.mask_src = np.ascontiguousarray(src)
+    p.mask_y, p.mask_x = (sy - r0, wy.astype(np.float32)), (sx, wx.astype(np.float32))
+    p.span_cap = int((sx[np.minimum(np.arange(cw) + 63, cw - 1)] + wx.shape[1] - sx).max())
+    return p
+
+
+def _al(n: int, a: int = 16) -> int:
+    return (n + a - 1) // a * a
+
+
+class SegStager:
+    """Packs the sources, jobs and tables of a batch of `SegItemPlan`s into one pinned buffer, copies it once and runs the
+    device half: mx_color_jitter (ColorJitter on the original image) -> mx_resample (the bilinear rescale) ->
+    mx_seg_input_stage (color_norm, crop container, flip, CHW, fp32), and mx_mask_stage for the label.  Two pinned buffers
+    alternate so that packing batch t+1 does not wait for the copy of batch t; buffers grow to the largest batch seen.
+    Returns {"img" [n,3,S,S], "mask" [n,C,S,S]} (+ "label" [n,20]) on the device: the batch `muscle_step` takes."""
+
+    def __init__(self, device, batch: int, crop_size: int = 448):
+        self.dev, self.n, self.crop = device, batch, crop_size
+        self._pin = [None, None]
+        self._evt = [None, None]
+        self._dev_buf = None
+        self._dev_tmp = self._dev_rs = None
+        self._dev_sums = None                               # ColorJitter's per-image luminance sums (device scratch)
+        self._k = 0
+        self.last_bytes = 0                                 # bytes of the last batch's one host-to-device copy
+
+    def _pinned(self, k: int, nbytes: int) -> np.ndarray:
+        if self._pin[k] is None or self._pin[k].numel() < nbytes:
+            t = torch.empty(_al(nbytes * 5 // 4, 4096), dtype=torch.uint8)
+            self._pin[k] = t.pin_memory() if torch.cuda.is_available() else t
+        return self._pin[k].numpy()
+
+    @staticmethod
+    def _grow(t, nbytes: int, device):
+        if t is None or t.numel() < nbytes:
+            return torch.empty(_al(nbytes * 5 // 4, 4096), dtype=torch.uint8, device=device)
+        return t
+
+    def __call__(self, plans: Sequence[SegItemPlan], labels: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        from .data import InputStager
+        n, S = len(plans), self.crop
+        assert 0 < n <= self.n
+        C = plans[0].mask_src.shape[2]
+        if any(p.mask_src.shape[2] != C for p in plans):
+            raise ValueError("every soft mask of a batch must have the same number of channels")
+        # ---- layout of the one buffer: [image jobs | jitter jobs | resample jobs | mask jobs | tables | images | masks]
+        o_jobs, o_jit, o_rs, o_mj = 0, 32 * n, 64 * n, 96 * n
+        o_tab = off = 160 * n
+        tab_at, mtab_at = [], []
+        for p in plans:
+            tab_at.append(off)
+            off += 4 * p.tables.size
+        for p in plans:
+            mtab_at.append(off)
+            off += 4 * sum(s.size + w.size for s, w in (p.mask_y, p.mask_x))
+        off = _al(off)
+        img_at, msk_at = [], []
+        for p in plans:
+            img_at.append(off)
+            off = _al(off + p.img_u8.size)
+        for p in plans:
+            msk_at.append(off)
+            off = _al(off + p.mask_src.nbytes)
+        total = off
+        if total >= 2 ** 31:
+            raise ValueError("batch sources exceed 2 GiB")
+        k = self._k
+        self._k ^= 1
+        if self._evt[k] is not None:
+            self._evt[k].synchronize()                      # the copy out of this pinned buffer two batches ago is done
+        buf = self._pinned(k, total)
+        words = buf[:o_tab].view(np.int32).reshape(-1, 8)
+        words[:] = 0
+        jobs, jit, rsj = words[:n], words[n:2 * n], words[2 * n:3 * n]
+        mj = words[3 * n:5 * n].reshape(n, 16)
+        jit_f = jit.view(np.float32)
+        jit[:, 3] = 0xFFFF                                  # order nibbles: nothing to do
+        tmp_off = rs_off = 0
+        any_jit, jit_px, rs_px, span_cap = False, 1, 1, 1
+        for i, p in enumerate(plans):
+            h, w = p.img_u8.shape[:2]
+            tw, th = p.resize_to
+            it, il, ch, cw = p.img_crop
+            buf[img_at[i]:img_at[i] + p.img_u8.size] = p.img_u8.reshape(-1)
+            buf[tab_at[i]:tab_at[i] + 4 * p.tables.size] = p.tables.view(np.uint8)
+            rsj[i] = (img_at[i], h, w, tmp_off, rs_off, tw, th, (tab_at[i] - o_tab) // 4)
+            jobs[i] = (rs_off + (it * tw + il) * 3, ch, cw, p.place[0], p.place[1], tw, int(p.flip), 0)
+            tmp_off += h * tw * 3
+            rs_off += th * tw * 3
+            rs_px = max(rs_px, h * tw, th * tw)
+            if p.jitter is not None:
+                code, facs, hue = InputStager._jitter_words(p.jitter)
+                jit[i, :4] = (img_at[i], h, w, code)
+                jit_f[i, 4:7] = facs
+                jit[i, 7] = hue
+                any_jit, jit_px = True, max(jit_px, h * w)
+            m = p.mask_src
+            buf[msk_at[i]:msk_at[i] + m.nbytes] = m.reshape(-1).view(np.uint8)
+            (sy, wy), (sx, wx) = p.mask_y, p.mask_x
+            o = mtab_at[i]
+            ty_off = (o - o_tab) // 4
+            for a in (sy, wy):
+                buf[o:o + a.nbytes] = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+                o += a.nbytes
+            tx_off = (o - o_tab) // 4
+            for a in (sx, wx):
+                buf[o:o + a.nbytes] = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+                o += a.nbytes
+            mj[i, :13] = (msk_at[i], m.shape[0], m.shape[1], int(m.dtype == np.float32), p.place[0], p.place[1], ch, cw,
+                          int(p.flip), wy.shape[1], wx.shape[1], ty_off, tx_off)
+            span_cap = max(span_cap, p.span_cap)
+        self._dev_buf = self._grow(self._dev_buf, total, self.dev)
+        self._dev_tmp = self._grow(self._dev_tmp, tmp_off, self.dev)
+        self._dev_rs = self._grow(self._dev_rs, rs_off, self.dev)
+        if self._dev_sums is None:
+            self._dev_sums = torch.empty(self.n, dtype=torch.int64, device=self.dev)
+        self._dev_buf[:total].copy_(self._pin[k][:total], non_blocking=True)
+        self.last_bytes = total
+        evt = torch.cuda.Event()
+        evt.record()
+        self._evt[k] = evt
+        base = self._dev_buf.data_ptr()
+        st = stream()
+        if any_jit:
+            call("mx_color_jitter", base, base + o_jit, self._dev_sums.data_ptr(), n, int(jit_px), st)
+        call("mx_resample", base, base + o_rs, base + o_tab, self._dev_tmp.data_ptr(), self._dev_rs.data_ptr(), n, int(rs_px), st)
+        img = torch.empty(n, 3, S, S, dtype=torch.float32, device=self.dev)
+        mask = torch.empty(n, C, S, S, dtype=torch.float32, device=self.dev)
+        call("mx_seg_input_stage", self._dev_rs.data_ptr(), base + o_jobs, img.data_ptr(), n, S, S, st)
+        call("mx_mask_stage", base, base + o_mj, base + o_tab, mask.data_ptr(), n, C, S, int(span_cap), st)
+        out = {"img": img, "mask": mask}
+        if labels is not None:
+            out["label"] = labels.to(self.dev, non_blocking=True)
+        return out
+
+
+class VOC12SegDataset:
+    """The reference dataset's role (src/data.py:69-123, `inference=False`): `plan(idx)` is the host half of `__getitem__`
+    (JPEG decode, np.load of the soft label, the draws, the tables); a batch of plans goes through a `SegStager`.
+    Reads `<mask_root>/<name>.npy` as `muscle_amd.infer_irn --soft_output 1` writes it (float16 [H,W,21]); float32 files
+    are shipped as they are and float64 files rounded to float32.  mask_type='hard' (PNG labels; train_muscle.py does not use
+    it) is refused."""
+
+    def __init__(self, img_name_list_path: str, voc12_root: str, mask_root: str, min_scale: float = 0.5, max_scale: float = 1.5,
+                 crop_size: int = 448, mask_type: str = "soft", labels: Optional[Dict[str, np.ndarray]] = None,
+                 augment: bool = True):
+        if mask_type != "soft":
+            raise NotImplementedError(f"mask_type={mask_type!r}: only the soft pseudo-labels train_muscle.py trains on "
+                                      "(mask_type='soft', <name>.npy) are built on the HIP path")
+        self.names = [ln.split(" ")[0].split("/")[-1].split(".")[0] for ln in open(img_name_list_path).read().splitlines()]
+        self.root, self.mask_root, self.crop = voc12_root, mask_root, crop_size
+        self.min_scale, self.max_scale, self.augment = min_scale, max_scale, augment
+        if labels is None and os.path.exists("data/cls_labels.npy"):
+            labels = np.load("data/cls_labels.npy", allow_pickle=True).item()          # src/data.py:53-56
+        self.labels = labels
+
+    def __len__(self):
+        return len(self.names)
+
+    def plan(self, idx: int) -> Tuple[str, SegItemPlan, Optional[np.ndarray]]:
+        import PIL.Image
+        name = self.names[idx]
+        img = PIL.Image.open(os.path.join(self.root, "JPEGImages", name + ".jpg")).convert("RGB")
+        mask = np.load(os.path.join(self.mask_root, name + ".npy"), allow_pickle=True)
+        lab = None if self.labels is None else np.asarray(self.labels[name], dtype=np.float32)
+        return name, plan_seg_item(img, mask, self.min_scale, self.max_scale, self.crop, self.augment), lab
+
+    __getitem__ = plan          # a torch.utils.data map-style dataset: DataLoader workers run the host half
+
+
+class SegLoader:
+    """The reference's `DataLoader(train_dataset, batch_size, num_workers, pin_memory=True, drop_last=True, shuffle=True,
+    prefetch_factor=4)` (train_muscle.py:128-130) for this input path: torch's DataLoader runs `VOC12SegDataset.plan` in
+    its worker processes with torch's own per-worker seeding of `torch` / `random` (base seed + worker id, as in the
+    reference), and each batch of plans goes through the `SegStager` in the training process.
+    Iterating yields `(names, batch)`, `batch` being the dict `muscle_step` takes."""
+
+    def __init__(self, dataset: VOC12SegDataset, batch_size: int, device, num_workers: int = 0, shuffle: bool = True,
+                 drop_last: bool = True, generator=None, prefetch_factor: int = 4):
+        from torch.utils.data import DataLoader
+        self.dataset, self.stager = dataset, SegStager(device, batch_size, dataset.crop)
+        self.loader = DataLoader(dataset, batch_size=batch_size, shuffle=shuffle, num_workers=num_workers, drop_last=drop_last,
+                                 collate_fn=_keep, generator=generator, persistent_workers=bool(num_workers),
+                                 prefetch_factor=prefetch_factor if num_workers else None)
+
+    def __len__(self):
+        return len(self.loader)
+
+    def __iter__(self):
+        for items in self.loader:
+            labels = None
+            if items[0][2] is not None:
+                labels = torch.from_numpy(np.stack([it[2] for it in items]))
+            yield [it[0] for it in items], self.stager([it[1] for it in items], labels=labels)

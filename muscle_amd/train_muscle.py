@@ -1,0 +1,110 @@
+"""`python -m muscle_amd.train_muscle`: the reference's train_muscle.py (decoder training on soft pseudo-labels) on the HIP
+path.  Same arguments, same files: `<session_name>/_<epoch>.pth` after every epoch.
+
+Differences a caller can see:
+  * the input path runs on the device (`muscle_amd.segdata`): DataLoader workers decode and plan, the GPU resizes, crops and
+    flips image and label; --mask_root holds what `python -m muscle_amd.infer_irn --soft_output 1` writes;
+  * --val_list (new, default data/val.txt: the list the reference hard-codes) names the images of the per-epoch validation;
+  * --crf 1 runs the dense CRF of the validation on the GPU with t=1 (the exact windowed CRF of muscle_amd/crf.py, not
+    pydensecrf's lattice filter);
+  * --tblog_dir is created and otherwise unused (the reference opens a tensorboardX writer and never writes to it).
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import random
+import sys
+import time
+from typing import List, Optional
+
+import numpy as np
+
+
+def parse_args(argv: Optional[List[str]] = None):
+    ap = argparse.ArgumentParser(prog="python -m muscle_amd.train_muscle", description=__doc__.split("\n")[0])
+    ap.add_argument("--batch_size", default=6, type=int)
+    ap.add_argument("--max_epoches", default=8, type=int)
+    ap.add_argument("--lr", default=1e-5, type=float)
+    ap.add_argument("--num_workers", default=8, type=int)
+    ap.add_argument("--wt_dec", default=1e-5, type=float)
+    ap.add_argument("--train_list", default="data/VOC2012/train_aug.txt", type=str)
+    ap.add_argument("--val_list", default="data/val.txt", type=str, help="images of the per-epoch validation")
+    ap.add_argument("--num_classes", default=21, type=int)
+    ap.add_argument("--session_name", default="runs/muscle", type=str)
+    ap.add_argument("--crop_size", default=448, type=int)
+    ap.add_argument("--weights", default=None, type=str)
+    ap.add_argument("--voc12_root", default="data/VOC2012", type=str)
+    ap.add_argument("--mask_root", required=True, type=str, help="directory of soft pseudo-labels <name>.npy, [H,W,21]")
+    ap.add_argument("--k", default=128, type=int)
+    ap.add_argument("--step", default=7, type=int)
+    ap.add_argument("--lamb", default=5e-2, type=float)
+    ap.add_argument("--tblog_dir", default="logs/tblog_muscle", type=str, help="created; nothing is written to it")
+    ap.add_argument("--cls_dir", default=None, type=str, help="per-image class scores <name>.npy for the validation")
+    ap.add_argument("--crf", default=0, type=int,
+                    help="1: dense CRF (t=1) in the validation, on the GPU with exact windowed kernels (not pydensecrf)")
+    ap.add_argument("--seed", default=221, type=int)
+    ap.add_argument("--pretrained", default="b7", type=str)
+    ap.add_argument("--bifpn", default=3, type=int)
+    return ap.parse_args(argv)
+
+
+def main(argv: Optional[List[str]] = None) -> int:
+    args = parse_args(argv)
+    import torch
+    import muscle_amd
+    from muscle_amd import edge
+    from muscle_amd.evaluation import validate_seg
+    from muscle_amd.infer_seg import read_names
+    from muscle_amd.segdata import SegLoader, VOC12SegDataset
+
+    print(vars(args))
+    if args.seed:                                                                           # train_muscle.py:103-106
+        random.seed(args.seed)
+        np.random.seed(args.seed)
+        torch.manual_seed(args.seed)
+    dev = torch.device("cuda:0")
+    model = muscle_amd.MuSCLe(num_classes=args.num_classes, pretrained="efficientnet-" + args.pretrained, layers=args.bifpn,
+                              MemoryEfficient=True, mode="dec", last_pooling=True)
+    os.makedirs(args.tblog_dir, exist_ok=True)
+    os.makedirs(args.session_name, exist_ok=True)
+    train_dataset = VOC12SegDataset(args.train_list, args.voc12_root, args.mask_root, min_scale=0.5, max_scale=1.75,
+                                    crop_size=args.crop_size, mask_type="soft")             # :119-125
+    if train_dataset.labels is None:
+        raise FileNotFoundError("data/cls_labels.npy (the image-level labels, src/data.py:53-56) not found")
+    loader = SegLoader(train_dataset, args.batch_size, dev, num_workers=args.num_workers, shuffle=True, drop_last=True,
+                       prefetch_factor=4)                                                   # :128-130
+    val_names = read_names(args.val_list)
+    max_step = len(train_dataset) // args.batch_size * args.max_epoches
+    if args.weights:
+        model.load_state_dict(torch.load(args.weights, map_location="cpu"), strict=False)   # :153-155
+    model = model.to(dev)
+    optimizer = muscle_amd.FusedAdam(model.parameters(), lr=args.lr, weight_decay=args.wt_dec)
+    scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(optimizer, "max", patience=0, cooldown=0, factor=0.5, min_lr=5e-6)
+    criterion2 = edge.FieldLoss(sobel_size=5, beta=1e2, k=args.k)
+    start = stage_start = time.time()
+    print("Session started: ", time.ctime(start))
+    for ep in range(args.max_epoches):
+        model.train()
+        print("lr: %.6f" % (optimizer.param_groups[0]["lr"]))
+        for it, (_names, batch) in enumerate(loader):
+            out = muscle_amd.muscle_step(model, optimizer, batch, lamb=args.lamb, step=args.step, k=args.k, criterion2=criterion2)
+            if it % 25 == 0:                                                                # :210-218
+                elapsed = time.time() - start
+                est_finish = int(start + elapsed / (it / max_step + 1))
+                print("Iter:%5d/%5d" % (it + max_step // args.max_epoches * ep, max_step),
+                      "loss_seg:%.4f" % (float(out["loss_seg"])),
+                      "loss_beacon:%.4f" % (float(out["loss_beacon"])),
+                      "imps:%.1f" % ((it + 1) * args.batch_size / (time.time() - stage_start)),
+                      "Fin:%s" % (time.ctime(est_finish)), flush=True)
+        torch.save(model.state_dict(), os.path.join(args.session_name, "_{}".format(str(ep)) + ".pth"))
+        stamp = time.time()                                                                 # :224-283
+        miou = validate_seg(model, val_names, args.voc12_root, dev, args.num_classes, cls_dir=args.cls_dir, crf=bool(args.crf))
+        print(f"\n Epoch:{ep} val miou:{miou}", f"Time elapse:{time.time() - stamp}s", flush=True)
+        scheduler.step(miou)
+        stage_start = time.time()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
