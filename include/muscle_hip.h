@@ -311,6 +311,17 @@ int mx_infer_accum(const float* src, float* acc, int h, int w, int lds, int K, i
  * v = (v - min - 1e-6) / (max - min + 1e-6) */
 int mx_infer_norm(float* acc, int channels, long HW, void* stream);
 
+/* ---- infer_mcl.py:107-148 for one image in ONE launch: every pass of the multi-scale / flip list, both maps, only the
+ * channels the script keeps (:172-174).  passes: device int64 [npass][8] {address of the pass's CAM [h,w,lds], address of
+ * its SGC [h,w,lds] (cam='cam_lr', one sample each), h, w, Hs, Ws, flip, 0} in the order of VOC12ClsDatasetMSF; trusted
+ * device data, h*w*lds < 2^31.  keep: device int32 [nkeep], foreground indices 0..K-2 ascending (model channel keep[j]+1).
+ * out_cam / out_sgc: fp32 [nkeep,H,W], fully written; either may be NULL (that map is neither read nor computed), both
+ * NULL is an error.  out[j,Y,X] = sum over passes in table order, from 0.f, of mx_infer_accum's per-pass value for channel
+ * keep[j]+1 (bit-equal to mx_infer_accum over the same passes into a zeroed accumulator).  No atomics.  The normalisation
+ * of infer_mcl.py:151-164 is mx_infer_norm(out, nkeep, H*W) on the compact buffer. */
+int mx_cam_infer(const long* passes, int npass, int lds, int K, int H, int W, const int* keep, int nkeep, float* out_cam,
+                 float* out_sgc, void* stream);
+
 /* ---- semantic-segmentation inference (infer_seg.py:101-133 without the dense CRF; src/evaluation.py:36-68) ------------
  * mx_seg_infer: one image, ALL passes of its multi-scale / flip list in one launch.  passes: device int64 [npass][8]
  * {address of the pass's NHWC logits [h,w,lds] (cam='seg_lr', one sample), h, w, Hs, Ws, flip, 0, 0}, in the order of
@@ -387,6 +398,15 @@ int mx_irn_finish(const float* rw, int C, int h, int w, int H, int W, float bg_t
  * counts[t][k][0..2] += (TP, P, T).  pred [K,H,W] fp32 (cam_maxnorm'ed), label [K], gt uint8 [H,W], counts int64 [nt][K][3]. */
 int mx_eval_confusion(const float* pred, const float* label, const unsigned char* gt, const float* thresholds, int nt, int K, int H,
                       int W, long long* counts, void* stream);
+
+/* ---- CAM quality evaluation (src/evaluation.py:25-50, input_type='npy'), one image, ALL thresholds of the curve (:126-133):
+ * predict(t) = argmax_k [t, tensor_1..tensor_{K-1}] with tensor_{keys[j]+1} = maps[j] and absent channels 0 (first maximum
+ * wins; no fp16 rounding, no label multiply); over pixels with gt < 255: counts[t][k][0..2] += (TP, P, T).
+ * maps fp32 [nkeep,H,W]; keys int32 [nkeep] ascending in 0..K-2; gt uint8 [H,W]; thresholds fp32 [nt] ascending and >= 0
+ * (so an absent channel never wins); counts int64 [nt][K][3], accumulated across calls with integer atomics (exact).
+ * nt <= 64, K <= 24.  Per pixel at most three LDS atomics whatever nt: the pixel is binned by #{t < its best value}. */
+int mx_camdict_confusion(const float* maps, const int* keys, int nkeep, const unsigned char* gt, const float* thresholds, int nt,
+                         int K, int H, int W, long long* counts, void* stream);
 
 /* adjoint of mx_upsample_to_nchw: gsrc (=|+=) W^T gdst */
 int mx_upsample_to_nchw_bwd(const float* gdst, float* gsrc, int N, int Hs, int Ws, int lds, int K, int Hd, int Wd,

@@ -435,7 +435,209 @@ __global__ __launch_bounds__(256) void eval_confusion_kernel(const float* pred, 
     if (lc[i]) atomicAdd((unsigned long long*)&counts[i], (unsigned long long)lc[i]);
 }
 
+// ---------------------------------------------------------------------------
+// infer_mcl.py:107-148 for one image in ONE launch: every pass of the multi-scale / flip list, both maps (raw CAM and
+// SGC), only the channels the script keeps (the image's labels, :172-174).  Per output pixel, pass and kept channel the
+// value is exactly infer_accum_kernel's: the hp_coord footprint of (Y, flip ? W-1-X : X), four bil_lr taps, the same
+// blend; summed over passes in table order from 0.f in a register.  The footprint, the 4 x 4 low-res offsets and the six
+// weights of a pass do not depend on the channel or the map: they are computed once per pixel and pass and shared by
+// the CH channels x NMAP maps of the thread (infer_accum_kernel recomputes them per channel and launch).  Channel chunks
+// of CH go to blockIdx.y.  No atomics, nothing is read back from out: the same bits every run.
+// tab: npass x 8 int64 {address of the pass's CAM [h,w,lds], address of its SGC [h,w,lds], h, w, Hs, Ws, flip, 0};
+// col0: table column of map 0 (0 = CAM first, 1 = SGC only).
+// ---------------------------------------------------------------------------
+// The bits must be infer_accum_kernel's, and hipcc contracts that kernel's a*b + c*d expressions into one rounded product
+// and one fma, choosing WHICH product is rounded per expression (and leaving the last blend as two products and an add),
+// as its --save-temps ISA shows.  A second kernel written with the same C expressions is contracted differently once the
+// coordinates are hoisted, so the arithmetic is spelt out here with contraction off and explicit fmas, operation for
+// operation as the old kernel executes it:
+//   bil_coord: w1 = fma(scale, d, -i0) (i0 from the rounded product scale*d);   hp_coord: s = fma(d + 0.5, in/out, -0.5)
+//   lerp_a(a, b, w) = fma(w, b, rn((1-w)*a)): every x-blend inside a tap, the y-blend of tap (y1,x0), the x-blend of row y0
+//   lerp_b(a, b, w) = fma(1-w, a, rn(w*b)):   the y-blend of the other three taps, the x-blend of row y1
+//   value = rn((1-wy)*R0) + rn(wy*R1)
+// tests/test_gpu_cam_infer.py asserts the equality bit for bit; if a compiler change moves infer_accum_kernel's
+// contraction, that test says so and this block is re-derived from the new ISA.
+__device__ __forceinline__ float lerp_a(float a, float b, float w) {
+#pragma clang fp contract(off)
+  float p = (1.f - w) * a;
+  return __builtin_fmaf(w, b, p);
+}
+__device__ __forceinline__ float lerp_b(float a, float b, float w) {
+#pragma clang fp contract(off)
+  float p = w * b;
+  return __builtin_fmaf(1.f - w, a, p);
+}
+__device__ __forceinline__ void bil_coord_x(int d, int in, int out, int& i0, int& i1, float& w1) {
+#pragma clang fp contract(off)
+  float scale = (out > 1) ? (float)(in - 1) / (float)(out - 1) : 0.f;
+  float s = scale * (float)d;
+  i0 = (int)s;
+  if (i0 > in - 1) i0 = in - 1;
+  i1 = i0 + ((i0 < in - 1) ? 1 : 0);
+  w1 = __builtin_fmaf(scale, (float)d, -(float)i0);
+}
+__device__ __forceinline__ void hp_coord_x(int d, int in, int out, int& i0, int& i1, float& w1) {
+#pragma clang fp contract(off)
+  float s = __builtin_fmaf((float)d + 0.5f, (float)in / (float)out, -0.5f);
+  if (s < 0.f) s = 0.f;
+  i0 = (int)s;
+  if (i0 > in - 1) i0 = in - 1;
+  i1 = i0 + ((i0 < in - 1) ? 1 : 0);
+  w1 = s - (float)i0;
+}
+// one align_corners tap of bil_lr from its four low-res corners; LERP_A: the y-blend of the tap at (y1, x0)
+template <bool LERP_A>
+__device__ __forceinline__ float bil_tap(const float* b, const int (&o)[4], float wy, float wx) {
+  float r0 = lerp_a(b[o[0]], b[o[1]], wx), r1 = lerp_a(b[o[2]], b[o[3]], wx);
+  return LERP_A ? lerp_a(r0, r1, wy) : lerp_b(r0, r1, wy);
+}
+__device__ __forceinline__ float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+__device__ __forceinline__ float blend_rows(float r0, float r1, float wy) {
+#pragma clang fp contract(off)
+  float p0 = (1.f - wy) * r0, p1 = wy * r1;
+  return p0 + p1;
+}
+
+template <int CH, int NMAP>
+__global__ __launch_bounds__(256) void cam_infer_kernel(const long* tab, int npass, int lds, int H, int W, const int* keep,
+                                                        int nkeep, int col0, float* out0, float* out1) {
+  const long HW = (long)H * W;
+  const int j0 = blockIdx.y * CH;
+  int kc[CH];
+#pragma unroll
+  for (int j = 0; j < CH; ++j) kc[j] = keep[min(j0 + j, nkeep - 1)] + 1;     // model channel (the index is clamped for the tail of the last chunk)
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < HW; i += (long)gridDim.x * 256) {
+    const int X = (int)(i % W), Y = (int)(i / W);
+    float acc[NMAP][CH];
+#pragma unroll
+    for (int m = 0; m < NMAP; ++m)
+#pragma unroll
+      for (int j = 0; j < CH; ++j) acc[m][j] = 0.f;
+    for (int n = 0; n < npass; ++n) {
+      const long* e = tab + n * 8;
+      const int h = (int)e[2], w = (int)e[3], Hs = (int)e[4], Ws = (int)e[5];
+      const int Xr = e[6] ? (W - 1 - X) : X;            // np.flip(axis=1) after the resize
+      int y0, y1, x0, x1;
+      float wy, wx;
+      hp_coord_x(Y, Hs, H, y0, y1, wy);
+      hp_coord_x(Xr, Ws, W, x0, x1, wx);
+      // bil_lr's coordinates of the footprint's two rows and two columns
+      int r0[2], r1[2], c0[2], c1[2];
+      float wr[2], wc[2];
+      bil_coord_x(y0, h, Hs, r0[0], r1[0], wr[0]);
+      bil_coord_x(y1, h, Hs, r0[1], r1[1], wr[1]);
+      bil_coord_x(x0, w, Ws, c0[0], c1[0], wc[0]);
+      bil_coord_x(x1, w, Ws, c0[1], c1[1], wc[1]);
+      int o[2][2][4];                                    // [row of the footprint][column][low-res corner]
+#pragma unroll
+      for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+          o[a][b][0] = (r0[a] * w + c0[b]) * lds; o[a][b][1] = (r0[a] * w + c1[b]) * lds;
+          o[a][b][2] = (r1[a] * w + c0[b]) * lds; o[a][b][3] = (r1[a] * w + c1[b]) * lds;
+        }
+#pragma unroll
+      for (int m = 0; m < NMAP; ++m) {
+        const float* src = reinterpret_cast<const float*>(e[col0 + m]);
+#pragma unroll
+        for (int j = 0; j < CH; ++j) {
+          if (j0 + j >= nkeep) continue;                 // uniform: the tail of the last chunk does no work
+          const float* b = src + kc[j];
+          float a00 = bil_tap<false>(b, o[0][0], wr[0], wc[0]), a01 = bil_tap<false>(b, o[0][1], wr[0], wc[1]);
+          float a10 = bil_tap<true>(b, o[1][0], wr[1], wc[0]), a11 = bil_tap<false>(b, o[1][1], wr[1], wc[1]);
+          acc[m][j] = add_rn(acc[m][j], blend_rows(lerp_a(a00, a01, wx), lerp_b(a10, a11, wx), wy));
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < CH; ++j)
+      if (j0 + j < nkeep) {
+        out0[(long)(j0 + j) * HW + i] = acc[0][j];
+        if (NMAP > 1) out1[(long)(j0 + j) * HW + i] = acc[NMAP - 1][j];
+      }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// src/evaluation.py:25-50 (input_type='npy') for one image and ALL thresholds of the curve at once.
+//   predict(t) = argmax_k [t, tensor_1 .. tensor_{K-1}]  (first maximum wins), tensor_{key+1} = the dict's float32 map,
+//   absent channels 0; over pixels with gt < 255: P[predict]++, T[gt]++, TP[gt] += (predict == gt).
+// For t >= 0 an absent channel never beats channel 0, so only the kept maps are compared: (best, bk) = their first
+// maximum, which does not depend on t; predict(t) = (t >= best) ? 0 : bk.  With ascending thresholds the pixel is
+// described by its bin b = #{t_i < best}: thresholds i < b see bk, thresholds i >= b see 0.  Per pixel at most three LDS
+// integer atomics, independent of nt:  hp[b][bk]++;  hq[b][g]++ if g == bk, hq[b][0]++ if g == 0 (a kept class is never 0,
+// so column 0 of hq is free for the "predict = 0 and gt = 0" side);  ht[g]++.  At the flush, per threshold i and class c:
+//   P[i][c>0] = sum_{b>i} hp[b][c]   P[i][0] = sum_{b<=i} sum_c hp[b][c]   TP[i][c>0] = sum_{b>i} hq[b][c]
+//   TP[i][0] = sum_{b<=i} hq[b][0]   T[i][c] = ht[c]
+// maps fp32 [nkeep,H,W]; keys int32 [nkeep] ascending in 0..K-2; thr fp32 [nt] ascending, >= 0; counts int64 [nt][K][3]
+// = (TP, P, T), accumulated with integer atomics: exact.
+// ---------------------------------------------------------------------------
+#define CDC_MAXT 64
+#define CDC_MAXK 24
+__global__ __launch_bounds__(256) void camdict_confusion_kernel(const float* maps, const int* keys, int nkeep,
+                                                                const unsigned char* gt, const float* thr, int nt, int K, long HW,
+                                                                long long* counts) {
+  __shared__ int hp[(CDC_MAXT + 1) * CDC_MAXK], hq[(CDC_MAXT + 1) * CDC_MAXK], ht[CDC_MAXK], hrow[CDC_MAXT + 1];
+  __shared__ float st[CDC_MAXT];
+  __shared__ int sk[CDC_MAXK];
+  for (int i = threadIdx.x; i < (nt + 1) * K; i += 256) { hp[i] = 0; hq[i] = 0; }
+  if (threadIdx.x < K) ht[threadIdx.x] = 0;
+  if (threadIdx.x < nt) st[threadIdx.x] = thr[threadIdx.x];
+  if (threadIdx.x < nkeep) sk[threadIdx.x] = keys[threadIdx.x] + 1;
+  __syncthreads();
+  for (long p = blockIdx.x * 256L + threadIdx.x; p < HW; p += (long)gridDim.x * 256) {
+    const int g = gt[p];
+    if (g >= 255) continue;
+    float best = maps[p];
+    int bk = sk[0];
+    for (int j = 1; j < nkeep; ++j) {
+      const float v = maps[(long)j * HW + p];
+      if (v > best) { best = v; bk = sk[j]; }    // strict: the first maximum wins, as np.argmax
+    }
+    int b = 0;
+    for (int t = 0; t < nt; ++t) b += (st[t] < best) ? 1 : 0;
+    if (bk < K) atomicAdd(&hp[b * K + bk], 1);
+    if (g < K) {
+      atomicAdd(&ht[g], 1);
+      if (g == bk || g == 0) atomicAdd(&hq[b * K + g], 1);
+    }
+  }
+  __syncthreads();
+  for (int b = threadIdx.x; b <= nt; b += 256) {           // pixels per bin, any winner
+    int s = 0;
+    for (int c = 1; c < K; ++c) s += hp[b * K + c];
+    hrow[b] = s;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < nt * K; i += 256) {
+    const int t = i / K, c = i % K;
+    int P = 0, TP = 0;
+    if (c == 0) {
+      for (int b = 0; b <= t; ++b) { P += hrow[b]; TP += hq[b * K]; }
+    } else {
+      for (int b = t + 1; b <= nt; ++b) { P += hp[b * K + c]; TP += hq[b * K + c]; }
+    }
+    unsigned long long* d = (unsigned long long*)&counts[(long)i * 3];
+    if (TP) atomicAdd(d + 0, (unsigned long long)TP);
+    if (P) atomicAdd(d + 1, (unsigned long long)P);
+    if (ht[c]) atomicAdd(d + 2, (unsigned long long)ht[c]);
+  }
+}
+
 static int gs(long n) { long b = (n + 255) / 256; return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b)); }
+
+// channels per thread of cam_infer_kernel: see the resource note in DESIGN.md (no scratch at 4 x 2 accumulators)
+#define CAM_CH 4
+template <int NMAP>
+static void cam_infer_launch(const long* passes, int npass, int lds, int H, int W, const int* keep, int nkeep, int col0,
+                             float* out0, float* out1, hipStream_t st) {
+  const int bx = gs((long)H * W);
+  hipLaunchKernelGGL((cam_infer_kernel<CAM_CH, NMAP>), dim3(bx, (nkeep + CAM_CH - 1) / CAM_CH), dim3(256), 0, st, passes, npass,
+                     lds, H, W, keep, nkeep, col0, out0, out1);
+}
 
 extern "C" {
 
@@ -562,6 +764,35 @@ int mx_seg_confusion(const unsigned char* pred, const unsigned char* gt, int K, 
   if (blocks > 1024) blocks = 1024;
   hipLaunchKernelGGL(seg_confusion_kernel, dim3(blocks), dim3(256), sizeof(int) * K * 3, (hipStream_t)stream, pred, gt, K, HW,
                      counts);
+  MX_LAUNCH_CHECK();
+  return MX_OK;
+}
+
+int mx_cam_infer(const long* passes, int npass, int lds, int K, int H, int W, const int* keep, int nkeep, float* out_cam,
+                 float* out_sgc, void* stream) {
+  MX_CHECK_ARG(passes && keep && (out_cam || out_sgc), "cam_infer: NULL table, keep list or both outputs NULL");
+  MX_CHECK_ARG(npass > 0 && K > 1 && K <= lds && lds % 4 == 0 && H > 0 && W > 0 && nkeep > 0 && nkeep <= K - 1,
+               "cam_infer: bad args npass=%d K=%d lds=%d H=%d W=%d nkeep=%d", npass, K, lds, H, W, nkeep);
+  if (out_cam && out_sgc)
+    cam_infer_launch<2>(passes, npass, lds, H, W, keep, nkeep, 0, out_cam, out_sgc, (hipStream_t)stream);
+  else
+    cam_infer_launch<1>(passes, npass, lds, H, W, keep, nkeep, out_cam ? 0 : 1, out_cam ? out_cam : out_sgc, nullptr,
+                        (hipStream_t)stream);
+  MX_LAUNCH_CHECK();
+  return MX_OK;
+}
+
+int mx_camdict_confusion(const float* maps, const int* keys, int nkeep, const unsigned char* gt, const float* thresholds, int nt,
+                         int K, int H, int W, long long* counts, void* stream) {
+  MX_CHECK_ARG(maps && keys && gt && thresholds && counts, "camdict_confusion: NULL argument");
+  MX_CHECK_ARG(nt > 0 && nt <= CDC_MAXT && K >= 2 && K <= CDC_MAXK && nkeep > 0 && nkeep <= K - 1 && H > 0 && W > 0,
+               "camdict_confusion: bad args nt=%d K=%d nkeep=%d H=%d W=%d", nt, K, nkeep, H, W);
+  const long HW = (long)H * W;
+  int blocks = (int)((HW + 256 * 8 - 1) / (256 * 8));
+  if (blocks < 1) blocks = 1;
+  if (blocks > 1024) blocks = 1024;
+  hipLaunchKernelGGL(camdict_confusion_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, maps, keys, nkeep, gt, thresholds,
+                     nt, K, HW, counts);
   MX_LAUNCH_CHECK();
   return MX_OK;
 }

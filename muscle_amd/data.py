@@ -453,7 +453,9 @@ class StagedLoader:
     in its worker processes (decode, flip, views, PIL resize, jitter, crop: ~10 ms of one core per image, so 245 img/s per
     GPU want ~3 cores per GPU) with the SAME per-worker seeding of torch / random as in the reference (base_seed + worker
     id), and each batch of plans goes through the `InputStager` in the training process: one pinned copy + three launches.
-    Iterating yields `(names, batch)`, `batch` being the dict `mcl_step` takes."""
+    Iterating yields `(names, batch)`, `batch` being the dict `mcl_step` takes.  `host_labels` / `host_label_sum` hold the
+    label array [n,20] of the batch just yielded and its sum as the host has them anyway (None without labels):
+    `mcl_step(..., valid_channel=int(loader.host_label_sum))` is train_mcl.py:178 without its device->host read."""
 
     def __init__(self, dataset: VOC12ClsPix, batch_size: int, device, num_workers: int = 0, shuffle: bool = True,
                  drop_last: bool = True, generator=None):
@@ -462,6 +464,8 @@ class StagedLoader:
         self.loader = DataLoader(dataset, batch_size=batch_size, shuffle=shuffle, num_workers=num_workers, drop_last=drop_last,
                                  collate_fn=_keep, worker_init_fn=_reference_worker_init if num_workers else None,
                                  generator=generator, persistent_workers=bool(num_workers))
+        self.host_labels: Optional[np.ndarray] = None
+        self.host_label_sum: Optional[float] = None
 
     def __len__(self):
         return len(self.loader)
@@ -470,8 +474,11 @@ class StagedLoader:
         for items in self.loader:
             names = [it[0] for it in items]
             labels = None
+            self.host_labels = self.host_label_sum = None
             if items[0][2] is not None:
-                labels = torch.from_numpy(np.stack([it[2] for it in items]))
+                self.host_labels = np.stack([it[2] for it in items])
+                self.host_label_sum = float(self.host_labels.sum(dtype=np.float64))
+                labels = torch.from_numpy(self.host_labels)
             yield names, self.stager([it[1] for it in items], labels=labels)
 
 

@@ -10,10 +10,21 @@ accumulates an int64 [thresholds, 21, 3] table on the device; the table is read 
 PNGs): one integer confusion kernel per image over the uint8 prediction and ground truth.
 
 `SegValidation` / `validate_seg` are the per-epoch validation of train_muscle.py:224-283 on top of `infer.infer_seg` and `SegEval`.
+
+`CamDictEval` is do_python_eval(input_type='npy') over the `{class: float32[H,W]}` dicts that infer_mcl writes, for a whole
+list of thresholds at once (one mx_camdict_confusion launch per image); `python -m muscle_amd.evaluation` is the
+reference's src/evaluation.py command line (:105-133) on top of it and of `SegEval`.
+
+Differences of the command line a caller can see:
+  * --curve takes a value as in the README (`--curve True`): True / true / 1 switch the threshold curve on and, unlike the
+    reference's `type=bool` (any non-empty string is True), False / false / 0 switch it off;
+  * --type npy needs --t or --curve (the reference would compare against `None`); a negative threshold is refused;
+  * the curve reads every file once for all 60 thresholds (the reference: 60 sweeps of 8 processes each);
+  * the list is read as src/data.py:load_img_name_list does (`infer_seg.read_names`), not with pandas.
 """
 from __future__ import annotations
 
-from typing import Dict, List, Sequence
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -155,3 +166,156 @@ def validate_seg(model, names: Sequence[str], voc12_root: str, device, num_cls: 
         gt = np.array(PIL.Image.open(os.path.join(voc12_root, 'SegmentationClass', name + '.png')))
         val.add(model, img, gt, name)
     return val.miou()
+
+
+class CamDictEval:
+    """do_python_eval(input_type='npy') (src/evaluation.py:25-68) for every threshold of `thresholds` at once: accumulates the
+    int64 (TP, P, T) table [len(thresholds), num_cls, 3] on the device, one mx_camdict_confusion launch per image."""
+
+    def __init__(self, device, thresholds: Sequence[float], num_cls: int = 21):
+        self.thresholds = tuple(float(t) for t in thresholds)
+        if not self.thresholds or len(self.thresholds) > 64:
+            raise ValueError(f"CamDictEval takes 1..64 thresholds (got {len(self.thresholds)})")
+        if any(t < 0 for t in self.thresholds):
+            raise ValueError("CamDictEval: a negative threshold would let the zero of an absent channel win; not supported")
+        if any(b < a for a, b in zip(self.thresholds, self.thresholds[1:])):
+            raise ValueError("CamDictEval: thresholds must be ascending")
+        if not 2 <= num_cls <= 24:
+            raise ValueError(f"CamDictEval: num_cls {num_cls} outside 2..24")
+        self.num_cls = num_cls
+        self.dev = torch.device(device)
+        self.thr = torch.tensor(self.thresholds, dtype=torch.float32, device=device)
+        self.counts = torch.zeros(len(self.thresholds), num_cls, 3, dtype=torch.int64, device=device)
+
+    def add(self, pred_dict: Dict[int, np.ndarray], gt) -> None:
+        """pred_dict: {class key 0..num_cls-2: [H,W] map of any float dtype} (stored as float32, as `tensor[key+1] = ...` of
+        :29-31 does); gt: uint8 [H,W] SegmentationClass map (255 = ignore), numpy or tensor."""
+        if not self.counts.is_cuda:
+            raise MuscleHipError("CamDictEval.add runs on the HIP kernels only: create it with a ROCm device")
+        keys = sorted(int(k) for k in pred_dict.keys())
+        if not keys:
+            raise ValueError("CamDictEval.add: empty dict (src/evaluation.py:28 needs one map for the image size)")
+        if keys[0] < 0 or keys[-1] > self.num_cls - 2 or len(set(keys)) != len(keys):
+            raise ValueError(f"CamDictEval.add: class keys {keys} outside 0..{self.num_cls - 2}")
+        maps = np.stack([np.asarray(pred_dict[k]) for k in keys]).astype(np.float32, copy=False)
+        if maps.ndim != 3:
+            raise ValueError(f"CamDictEval.add: maps must be [H,W] (got {maps.shape[1:]})")
+        _, H, W = maps.shape
+        g = gt if torch.is_tensor(gt) else torch.from_numpy(np.ascontiguousarray(gt))
+        if g.dtype != torch.uint8 or tuple(g.shape) != (H, W):
+            raise ValueError(f"gt must be uint8 [{H},{W}] (got {g.dtype} {tuple(g.shape)})")
+        m = torch.from_numpy(np.ascontiguousarray(maps)).to(self.dev)
+        kk = torch.tensor(keys, dtype=torch.int32).to(self.dev)
+        call("mx_camdict_confusion", ptr(m), ptr(kk), len(keys), ptr(g.to(self.dev).contiguous()), ptr(self.thr),
+             len(self.thresholds), self.num_cls, H, W, ptr(self.counts), stream())
+
+    def loglist(self, ti: int) -> Dict[str, float]:
+        """do_python_eval's return value for threshold index ti (src/evaluation.py:56-75)."""
+        return miou_loglist(self.counts[ti].cpu().numpy())
+
+    def mious(self) -> List[float]:
+        """loglist(ti)['mIoU'] for every threshold, from one read of the table."""
+        c = self.counts.cpu().numpy()
+        return [miou_loglist(c[ti])['mIoU'] for ti in range(len(self.thresholds))]
+
+
+# ---- python -m muscle_amd.evaluation: src/evaluation.py:72-133 --------------------------------------------------------------
+def print_loglist(loglist: Dict[str, float], num_cls: int = 21) -> None:
+    """do_python_eval(printlog=True), src/evaluation.py:76-83."""
+    for i in range(num_cls):
+        nm = categories[i] if i < len(categories) else str(i)
+        if i % 2 != 1:
+            print('%11s:%7.3f%%' % (nm, loglist[nm]), end='\t')
+        else:
+            print('%11s:%7.3f%%' % (nm, loglist[nm]))
+    print('\n======================================================')
+    print('%11s:%7.3f%%' % ('mIoU', loglist['mIoU']))
+
+
+def writedict(file, dictionary) -> None:
+    """src/evaluation.py:86-92."""
+    s = ''
+    for key in dictionary.keys():
+        s += '%s:%s  ' % (key, dictionary[key])
+    file.write(s + '\n')
+
+
+def writelog(filepath: str, metric, comment: str) -> None:
+    """src/evaluation.py:94-102: appends the time stamp, the comment, the metric dict and a rule."""
+    import time
+    with open(filepath, 'a') as logfile:
+        logfile.write(time.strftime("%Y-%m-%d %H:%M:%S", time.localtime()))
+        logfile.write('\t%s\n' % comment)
+        writedict(logfile, metric)
+        logfile.write('=====================================\n')
+
+
+def _flag(v: str) -> bool:
+    if v in ("True", "true", "1"):
+        return True
+    if v in ("False", "false", "0"):
+        return False
+    import argparse
+    raise argparse.ArgumentTypeError(f"--curve takes True/true/1 or False/false/0 (got {v!r})")
+
+
+def parse_args(argv: Optional[List[str]] = None):
+    import argparse
+    ap = argparse.ArgumentParser(prog="python -m muscle_amd.evaluation",
+                                 description="The reference's src/evaluation.py (IoU table of CAM dicts or segmentation PNGs) on the HIP path.")
+    ap.add_argument("--list", default="data/train.txt", type=str)
+    ap.add_argument("--predict_dir", default="out_sgc", type=str)
+    ap.add_argument("--gt_dir", default="data/VOC2012/SegmentationClass", type=str)
+    ap.add_argument("--logfile", default="./evallog.txt", type=str)
+    ap.add_argument("--comment", required=True, type=str)
+    ap.add_argument("--type", default="npy", choices=["npy", "png"], type=str)
+    ap.add_argument("--t", default=None, type=float, help="background threshold of --type npy (>= 0)")
+    ap.add_argument("--curve", default=False, type=_flag,
+                    help="True/true/1: mIoU at the 60 thresholds 0.00..0.59 from one pass over the files; False/false/0: off "
+                         "(the reference's type=bool reads any non-empty string as True)")
+    args = ap.parse_args(argv)
+    if args.curve and args.type != "npy":
+        ap.error("--curve sweeps the background threshold of --type npy")
+    if args.type == "npy" and not args.curve and args.t is None:
+        ap.error("--type npy needs a background threshold: --t T, or --curve True for the 60-threshold sweep")
+    if args.type == "npy" and not args.curve and args.t < 0:
+        ap.error("--t must be >= 0")
+    return args
+
+
+def main(argv: Optional[List[str]] = None) -> int:
+    args = parse_args(argv)
+    import os
+    import PIL.Image
+    from .infer_seg import read_names
+    dev = torch.device("cuda:0")
+    names = read_names(args.list)
+    gt_of = lambda n: np.array(PIL.Image.open(os.path.join(args.gt_dir, n + ".png")))  # noqa: E731
+    if args.type == "png":
+        ev = SegEval(dev, 21)
+        for n in names:
+            pred = np.array(PIL.Image.open(os.path.join(args.predict_dir, n + ".png")))
+            ev.add(torch.from_numpy(pred).to(dev), torch.from_numpy(gt_of(n)).to(dev))
+        loglist = ev.loglist()
+        print_loglist(loglist)
+        writelog(args.logfile, loglist, args.comment)
+        return 0
+    thresholds = [i / 100.0 for i in range(60)] if args.curve else [args.t]
+    cev = CamDictEval(dev, thresholds, 21)
+    for n in names:
+        cev.add(np.load(os.path.join(args.predict_dir, n + ".npy"), allow_pickle=True).item(), gt_of(n))
+    if not args.curve:
+        loglist = cev.loglist(0)
+        print_loglist(loglist)
+        writelog(args.logfile, loglist, args.comment)
+        return 0
+    l = cev.mious()
+    for i, t in enumerate(thresholds):
+        print('%d/60 background score: %.3f\tmIoU: %.3f%%' % (i, t, l[i]))
+    writelog(args.logfile, {'mIoU': l}, args.comment)
+    return 0
+
+
+if __name__ == "__main__":
+    import sys
+    sys.exit(main())

@@ -83,6 +83,62 @@ def infer_cam(model, img_list: List[torch.Tensor], label: torch.Tensor, H: int, 
     return cam_dict, sgc_dict, score
 
 
+def infer_cam_fused(model, img_list: List[torch.Tensor], label: torch.Tensor, H: int, W: int, want_cam: bool = True,
+                    want_sgc: bool = True) -> Tuple[Dict[int, np.ndarray], Dict[int, np.ndarray], torch.Tensor]:
+    """`infer_cam` with the post-processing in one launch: the same batch-2 forwards of a scale and its flip, then ONE
+    mx_cam_infer over all passes, both maps and only the channels of the image's labels (the sum and the min-max are per
+    channel, so the other 17-19 of 20 never need to exist), one mx_infer_norm per requested map on the compact
+    [nkeep,H,W] buffer and one device->host copy of it.  Same bits as `infer_cam`.  want_cam / want_sgc = False: that map
+    is neither read nor computed and its dict is empty.  An image without labels: empty dicts, nothing launched after the
+    forwards."""
+    if label.dim() != 2 or label.shape[0] != 1:
+        raise ValueError("infer_cam_fused handles one image per call (infer_mcl.py's DataLoader has batch_size 1)")
+    if not img_list:
+        raise ValueError("infer_cam_fused needs at least one pass")
+    model.eval()
+    if getattr(model.backbone, "_eval_fold", None) is None and hasattr(model, "fold_eval_bn"):
+        model.fold_eval_bn()              # eval BatchNorm folded into the 1x1 weights once, not per pass (train() drops it)
+    dev = img_list[0].device
+    K = model.classes
+    keep = [i for i in range(K - 1) if float(label[0, i]) > 1e-5]
+    maps, rows, scores = [], [], []       # the low-res maps stay referenced until the one launch below is enqueued
+    lds = _CPAD
+    with torch.no_grad():
+        i = 0
+        while i < len(img_list):
+            img = img_list[i]
+            if img.dim() != 4 or img.shape[0] != 1:
+                raise ValueError("each entry of img_list is one image [1,3,Hs,Ws]")
+            pair = i % 2 == 0 and i + 1 < len(img_list) and img_list[i + 1].shape == img.shape
+            x = torch.cat([img, img_list[i + 1]], dim=0).float() if pair else img.float()
+            cam_lr, sgc_lr, _emb, score = model(x, cam="cam_lr")                 # NHWC [b,h,w,24]
+            _, h, w, lds = cam_lr.shape
+            for b in range(x.shape[0]):
+                rows.append([cam_lr[b].data_ptr(), sgc_lr[b].data_ptr(), h, w, img.shape[2], img.shape[3], (i + b) % 2, 0])
+                scores.append(score[b:b + 1, 1:])
+            maps.append((cam_lr, sgc_lr))
+            i += x.shape[0]
+        score = torch.sigmoid(torch.mean(torch.cat(scores, dim=0), dim=0))
+        cam_dict: Dict[int, np.ndarray] = {}
+        sgc_dict: Dict[int, np.ndarray] = {}
+        if not keep or not (want_cam or want_sgc):
+            return cam_dict, sgc_dict, score
+        tab = torch.tensor(rows, dtype=torch.int64).to(dev)
+        idx = torch.tensor(keep, dtype=torch.int32).to(dev)
+        nk = len(keep)
+        out_cam = torch.empty(nk, H, W, dtype=torch.float32, device=dev) if want_cam else None
+        out_sgc = torch.empty(nk, H, W, dtype=torch.float32, device=dev) if want_sgc else None
+        call("mx_cam_infer", ptr(tab), len(rows), lds, K, H, W, ptr(idx), nk, ptr(out_cam), ptr(out_sgc), stream())
+        for out, d in ((out_cam, cam_dict), (out_sgc, sgc_dict)):
+            if out is None:
+                continue
+            call("mx_infer_norm", ptr(out), nk, H * W, stream())
+            host = out.cpu().numpy()
+            for j, k in enumerate(keep):
+                d[k] = host[j]
+    return cam_dict, sgc_dict, score
+
+
 def save_cam_dict(path: str, d: Dict[int, np.ndarray]) -> None:
     """infer_mcl.py:177-178: np.save of the {class: map} dict (an object array holding the dict)."""
     np.save(path, d)
