@@ -22,7 +22,6 @@ With save=False (no backward will follow) every tensor only backward would read 
 """
 from __future__ import annotations
 
-import functools
 import os
 
 from dataclasses import dataclass, field
@@ -222,29 +221,23 @@ def _prepare_weights(backbone, cfg: NetCfg, tape: Tape, dev, backward: bool):
         for (w, _), im in zip(ws, plan.run_forward()):
             if im is not None:
                 tape.wp[id(w)] = im
-    if not (backward and ops.DGRAD_AS_FORWARD):
+    if not backward:
         return
     side = _WgradLane(dev).s
-    if side is None:
+    if side is not None:
+        side.wait_stream(torch.cuda.current_stream())        # the optimizer step that produced these weights
+    with torch.cuda.stream(side):                            # (no side stream: in line)
         if plan is not None:
             wts, ims = plan.run_backward()
             for (w, _), wt, im in zip(ws, wts, ims):
                 tape.wt[id(w)] = wt
                 if im is not None and ops.get_gemm_mode() != 0:
                     tape.wtp[id(w)] = im
-        return
-    side.wait_stream(torch.cuda.current_stream())            # the optimizer step that produced these weights
-    with torch.cuda.stream(side):
-        if plan is not None:
-            wts, ims = plan.run_backward()
-            for (w, _), wt, im in zip(ws, wts, ims):
-                tape.wt[id(w)] = wt
-                if im is not None and ops.get_gemm_mode() != 0:
-                    tape.wtp[id(w)] = im
-        else:
+        elif side is not None:
             for w, v in ws:
                 tape.wt[id(w)] = ops.transpose(v)
-        tape.wt_event = side.record_event()
+        if side is not None:
+            tape.wt_event = side.record_event()
 
 
 def backbone_forward(backbone, cfg: NetCfg, img: torch.Tensor, training: bool,
@@ -383,30 +376,11 @@ class GradSink:
         return g
 
 
-FUSED_DW_BACKWARD = True
-# BN0 backward apply inside the expand data-gradient GEMM's operand load (the GEMM also writes dz for the weight gradient):
-# one pass over the Cexp-wide tensors less on paper, measured on MI355X (B7/448/bs32, A/B/A/B on one box) 130.2 / 130.5 ms
-# per step without against 133.0 / 133.2 with it - the second operand stream and the dz stores of the N-tile-0 workgroups
-# cost the MFMA-bound GEMMs more than the 8.5 ms pass gives back a third of.  Off; kept as an option.
-FOLD_BN0_APPLY = os.environ.get("MUSCLE_FOLD_BN0", "0") == "1"
-# Round 4: dZ = c1*G + c2*X + c3 formed in the operand loads of BOTH consumers (the second-generation split data gradient, whose
-# activations go straight to registers, and the split weight gradient's loader threads), dZ never written: the 2R + 1W pass over
-# the Cexp-wide tensors of the 28 x 28 stages disappears (-2.3 ms of bn_bwd_apply per step, -13 GB of traffic).  Measured
-# A/B/A/B on one box (profiles/r04_fold_bn0_both_ab.txt): 107.4 / 107.7 ms per step without, 109.9 / 110.0 with - the folded GEMMs
-# lose more (+5.3 ms: 192 registers take the data gradient from 3 to 2 workgroups per CU, 222 the weight gradient from 3 to 2 waves
-# per SIMD) than the pass costs.  Off; MUSCLE_FOLD_BN0_BOTH=1 turns it on (kernels and tests stay: tests/test_gpu_split.py).
-FOLD_BN0_BOTH = os.environ.get("MUSCLE_FOLD_BN0_BOTH", "0") == "1"
-# ... but in stages 1-2 (expand convs 32 -> 192, 48 -> 288 at 0.4-1.6 M rows) both consumers are HBM-bound, and there the same fold
-# (data gradient through the planes kernel, weight gradient through wgrad_small_kernel<..., GBN>) trades a 3-pass kernel for one
-# more operand stream in two kernels that wait on memory anyway.  MUSCLE_FOLD_BN0_EARLY=0 restores the pass.
+# BatchNorm-0 backward apply folded into both consumers of dZ = c1*G + c2*X + c3 in stages 1-2 (expand convs 32 -> 192, 48 -> 288 at
+# 0.4-1.6 M rows): there the data gradient (planes kernel) and the weight gradient (wgrad_small_kernel<..., GBN>) are HBM-bound, and
+# forming dZ in their operand loads trades a 3-pass kernel for one more operand stream in two kernels that wait on memory anyway.
+# MUSCLE_FOLD_BN0_EARLY=0 restores the pass.  (The folds that were measured and lost are in DESIGN.md; their kernels are lab code.)
 FOLD_BN0_EARLY = os.environ.get("MUSCLE_FOLD_BN0_EARLY", "1") == "1"
-# Round 5: the fold on the weight-gradient side only.  The expand convolution's weight gradient runs FIRST, on the main stream; the
-# loader waves of wgrad_split_ws_kernel<true> form dZ and store it, the data gradient reads the stored dZ as before: bn_bwd_apply is gone
-# for the split-arithmetic layers (stages 4-7), neither GEMM's matrix waves carry a second operand.  Measured (profiles/r05_knob_ab.txt):
-# bn_bwd_apply 7.00 -> 2.94 ms per step, but the 42 folded weight gradients 6.6 -> 10.4 ms (their two G loader waves carry twice the
-# requests, the stores and the FMAs; the kernel is sensitive to its L2 traffic, which grows 1.75x) - step 96.50 -> 96.16 ms A/B/A/B on one box, 96.77 -> 97.09 on another.
-# Too little for a second dZ buffer per block: off by default (MUSCLE_FOLD_BN0_WGRAD=1); kernel and test stay.
-FOLD_BN0_WGRAD = os.environ.get("MUSCLE_FOLD_BN0_WGRAD", "0") == "1"
 # Weight-gradient GEMMs on a second HIP stream (MUSCLE_WGRAD_STREAM=0 turns it off; `engine.WGRAD_SIDE_STREAM` can be
 # flipped at run time).  Nothing in the backward chain consumes them (only the optimizer and the gradient exchange do),
 # they are MFMA-bound, and the chain between two of them (BN backward, SE, depthwise) is HBM-bound.  Measured on
@@ -414,118 +388,50 @@ FOLD_BN0_WGRAD = os.environ.get("MUSCLE_FOLD_BN0_WGRAD", "0") == "1"
 # data-gradient twin - both kernels fill every CU's wave slots, so the second one only trickles in.  Under overlap the
 # duration of a single launch says nothing about the kernel: bench.py takes its per-launch HIP events with this off.
 WGRAD_SIDE_STREAM = os.environ.get("MUSCLE_WGRAD_STREAM", "1") == "1"
-_side_streams: Dict[tuple, "torch.cuda.Stream"] = {}
-
-
-def _masked_stream(device, n_cus: int):
-    """A HIP stream confined to `n_cus` of the chip's compute units (hipExtStreamCreateWithCUMask), wrapped for torch.
-    Stream creation is plumbing, so it goes straight to the HIP runtime torch has already loaded."""
-    import ctypes
-    hip = ctypes.CDLL("libamdhip64.so")
-    total = torch.cuda.get_device_properties(device).multi_processor_count
-    n_cus = max(1, min(int(n_cus), total))
-    words = (total + 31) // 32
-    # every (256 // n)-th CU rather than the first n: the mask's bit order walks the XCDs / shader engines round-robin on
-    # some runtimes and CU-major on others; an evenly spaced pattern takes the same share of every XCD under both
-    mask = (ctypes.c_uint32 * words)()
-    for i in range(n_cus):
-        cu = (i * total) // n_cus
-        mask[cu // 32] |= 1 << (cu % 32)
-    handle = ctypes.c_void_p()
-    with torch.cuda.device(device):
-        rc = hip.hipExtStreamCreateWithCUMask(ctypes.byref(handle), ctypes.c_uint32(words), mask)
-    if rc != 0 or not handle.value:
-        raise RuntimeError(f"hipExtStreamCreateWithCUMask failed (hipError {rc})")
-    return torch.cuda.ExternalStream(handle.value, device=device)
-
-
-# Weight-gradient side stream confined to this many CUs (0 = the whole chip).  The side stream's 180 us GEMM workgroups
-# otherwise take wave slots on every CU and the small latency-bound kernels of the main chain queue behind them
-# (profiles/r02_b_timeline.txt: se_bwd_b 134.9 us instead of 25.7 under overlap).
-WGRAD_CUS = int(os.environ.get("MUSCLE_WGRAD_CUS", "0"))
-# MUSCLE_FUSED_BN0_FINALIZE=1: the fused depthwise backward finishes the BatchNorm-0 backward statistics itself (its last workgroup per
-# channel chunk; mx_dwconv_bwd_fused_bn0, same bits) instead of a bn_reduce_finalize launch between it and the BN0 apply / the folded
-# GEMMs: 51 launches fewer per step and no time gained (alternating on one box 96.15 / 96.21, 96.74 / 96.60, 96.47 / 96.17 ms) - the
-# backward is bound by the sum of its kernels' work, not by the chain's launches.  Off; built and tested (tests/test_gpu_dwfused.py).
-FUSED_BN0_FINALIZE = os.environ.get("MUSCLE_FUSED_BN0_FINALIZE", "0") != "0"
-# SE excitation parameter gradients (se_bwd_b) on the side stream instead of the data-gradient chain
-SE_PARAMS_ASIDE = os.environ.get("MUSCLE_SE_PARAMS_ASIDE", "0") != "0"     # measured 0.6 ms per step SLOWER (profiles/r04_knob_sweep.txt)
-# Priority of the weight-gradient side stream: 0 = as the main stream, -1 = higher, 1 = LOWER (a raw HIP stream: torch only offers -1 / 0)
-WGRAD_PRIO = int(os.environ.get("MUSCLE_WGRAD_PRIO", "0"))
-
-
-def _low_priority_stream(device, prio: int):
-    """A HIP stream of priority `prio` > 0 (LOWER than the default streams; torch.cuda.Stream clamps to [-1, 0]), wrapped for torch.
-    hipDeviceGetStreamPriorityRange on MI355X: least = 1, greatest = -1."""
-    import ctypes
-    hip = ctypes.CDLL("libamdhip64.so")
-    handle = ctypes.c_void_p()
-    with torch.cuda.device(device):
-        rc = hip.hipStreamCreateWithPriority(ctypes.byref(handle), ctypes.c_uint(1), ctypes.c_int(int(prio)))      # hipStreamNonBlocking
-    if rc != 0 or not handle.value:
-        raise RuntimeError(f"hipStreamCreateWithPriority failed (hipError {rc})")
-    return torch.cuda.ExternalStream(handle.value, device=device)
+_side_streams: Dict[int, "torch.cuda.Stream"] = {}           # device index -> its side stream
 
 
 class _WgradLane:
     def __init__(self, device):
         self.s = None
-        self.pending = []
+        self.pending = []        # (launch, the tensors it reads), in issue order
         self.keep = []
         if WGRAD_SIDE_STREAM:
-            key = (device.index if device.index is not None else torch.cuda.current_device(), WGRAD_CUS)
+            key = device.index if device.index is not None else torch.cuda.current_device()
             if key not in _side_streams:
-                if WGRAD_CUS > 0:
-                    _side_streams[key] = _masked_stream(device, WGRAD_CUS)
-                elif WGRAD_PRIO > 0:
-                    _side_streams[key] = _low_priority_stream(device, WGRAD_PRIO)
-                else:
-                    _side_streams[key] = torch.cuda.Stream(device=device, priority=WGRAD_PRIO)
+                _side_streams[key] = torch.cuda.Stream(device=device)
             self.s = _side_streams[key]
 
-    def wgrad_bnbwd(self, G, G2, coef, X, dW):
-        """Queue dW += (c1*G + c2*G2 + c3)^T X (ops.pw_wgrad_bnbwd)."""
+    def _queue(self, launch, *reads):
+        """Run `launch` now (no side stream) or in the next flush(); `reads` then stay referenced until join()."""
         if self.s is None:
-            return ops.pw_wgrad_bnbwd(G, G2, coef, X, dW)
-        self.pending.append((G, X, dW, {"_bnbwd": (G2, coef)}))
-
-    def dw_reduce(self, scratch, dW):
-        """Queue the addition of a depthwise weight gradient's partial rows (ops.dw_parts_reduce): no consumer before Adam."""
-        if self.s is None:
-            return ops.dw_parts_reduce(scratch, dW)
-        self.pending.append((scratch, None, dW, {"_dwreduce": True}))
-
-    def defer(self, fn, *tensors):
-        """Queue any launch whose results nothing reads before the optimizer (`tensors` = its operands, kept alive until join())."""
-        if self.s is None:
-            return fn()
-        self.pending.append((tensors, None, None, {"_fn": fn}))
+            return launch()
+        self.pending.append((launch, reads))
 
     def wgrad(self, G, X, dW, **kw):
         """Queue dW += G^T X'.  It is launched by the next flush(), i.e. right after the data-gradient GEMM of the same
         conv has been enqueued on the main stream: two MFMA-bound GEMMs side by side gain nothing, a weight-gradient GEMM
         next to the HBM-bound kernels that follow the data gradient does."""
-        if self.s is None:
-            return ops.pw_wgrad(G, X, dW, **kw)
-        self.pending.append((G, X, dW, kw))
+        return self._queue(lambda: ops.pw_wgrad(G, X, dW, **kw), G, X)
+
+    def wgrad_bnbwd(self, G, G2, coef, X, dW):
+        """Queue dW += (c1*G + c2*G2 + c3)^T X (ops.pw_wgrad_bnbwd)."""
+        return self._queue(lambda: ops.pw_wgrad_bnbwd(G, G2, coef, X, dW), G, X, G2, coef)
+
+    def dw_reduce(self, scratch, dW):
+        """Queue the addition of a depthwise weight gradient's partial rows (ops.dw_parts_reduce): no consumer before Adam."""
+        return self._queue(lambda: ops.dw_parts_reduce(scratch, dW), scratch)
 
     def flush(self):
         if self.s is None or not self.pending:
             return
         self.s.wait_stream(torch.cuda.current_stream())     # operands ready, the data-gradient GEMM done
         with torch.cuda.stream(self.s):
-            for G, X, dW, kw in self.pending:
-                if "_fn" in kw:
-                    kw["_fn"]()
-                elif "_dwreduce" in kw:
-                    ops.dw_parts_reduce(G, dW)
-                elif "_bnbwd" in kw:
-                    ops.pw_wgrad_bnbwd(G, kw["_bnbwd"][0], kw["_bnbwd"][1], X, dW)
-                else:
-                    ops.pw_wgrad(G, X, dW, **kw)
+            for launch, _ in self.pending:
+                launch()
         # the caller drops G and X before the side stream has read them: they stay referenced until join() (one dz per
         # block, ~10 GB for B7/448/bs32 of 288; no record_stream, so the same code can be captured into a hipGraph)
-        self.keep.extend((G, X, kw.get("_bnbwd")) for G, X, _, kw in self.pending)
+        self.keep.extend(reads for _, reads in self.pending)
         self.pending = []
 
     def progress(self, done, module):
@@ -546,132 +452,123 @@ class _WgradLane:
         self.keep = []
 
 
+def _dw_input(t: BlockTape):
+    """What the depthwise conv read: (raw tensor, the BatchNorm + SiLU applied to it on load, or None for a materialised input)."""
+    return (t.e_raw, t.bn0) if t.cfg.expand else (t.x, t.x_st)
+
+
+def _project_backward(lane, tape: Tape, t: BlockTape, m, g_out, sink: GradSink):
+    """g_out --BN2 bwd--> dp --pw_wgrad / pw_dgrad--> dA = dL/d(act*gate) [Mo, Cexp]."""
+    b, hw = t.cfg, t.Ho * t.Wo
+    Mo = tape.N * hw
+    # BN2 backward (upstream gradient carries the drop_connect scale of the sample)
+    dp = ops.bn_backward(g_out.reshape(Mo, b.cout), t.p_raw, m._bn2, t.bn2, sink.of(m._bn2.weight), sink.of(m._bn2.bias), tape.training,
+                         row_scale=t.row_scale, rows_per_sample=hw)
+    # project conv: weight gradient against the recomputed activated+gated input, then data gradient
+    if t.a is not None:
+        lane.wgrad(dp, t.a, sink.of(m._project_conv.weight).view(b.cout, b.cexp))
+        t.a = None
+    else:
+        lane.wgrad(dp, t.d_raw.view(Mo, b.cexp), sink.of(m._project_conv.weight).view(b.cout, b.cexp), x_mode=ops.BNACT,
+                   x_scale=t.bn1.scale, x_shift=t.bn1.shift, x_gate=t.gate, rows_per_sample=hw)
+    ga = ops.pw_dgrad(dp, m._project_conv.weight.view(b.cout, b.cexp), b.cexp, wt=tape.wt.get(id(m._project_conv.weight)),
+                      planes=tape.wtp.get(id(m._project_conv.weight)))
+    lane.flush()
+    return ga
+
+
+def _se_bn1_coeffs(tape: Tape, t: BlockTape, m, ga, sink: GradSink):
+    """(dA, d_raw) --se_bn1_pool--> se_bwd --> gh --bn1_coeffs--> (c1..c3 of the BN1 data gradient, pooled-path gradient `add`).
+    One pass over (ga, d_raw) yields the SE gate gradient sum_hw ga*act AND the per-sample pieces of the BN1 backward sums; the
+    excitation backward then gives `add`, and the BN1 sums follow without touching the big tensors again."""
+    b, hw = t.cfg, t.Ho * t.Wo
+    Mo = tape.N * hw
+    pooled5 = ops.se_bn1_pool(ga, t.d_raw.view(Mo, b.cexp), t.bn1, hw)
+    gh = ops.se_bwd(pooled5[0], t.gate, t.s, t.h, m._se_expand.weight.view(b.cexp, b.se),
+                    sink.of(m._se_reduce.weight).view(b.se, b.cexp), sink.of(m._se_reduce.bias),
+                    sink.of(m._se_expand.weight).view(b.cexp, b.se), sink.of(m._se_expand.bias))
+    # pooled-path gradient `add`, the BN1 backward sums and their finalisation: one launch, no second pass over the tensors
+    return ops.bn1_coeffs(pooled5, t.gate, gh, m._se_reduce.weight.view(b.se, b.cexp), 1.0 / hw, Mo, m._bn1, t.bn1,
+                          sink.of(m._bn1.weight), sink.of(m._bn1.bias), tape.training)
+
+
+def _depthwise_backward(lane, tape: Tape, t: BlockTape, m, ga, c1, add, skip_res, sink: GradSink):
+    """BN1 data gradient + depthwise conv backward.  Returns (gx = gradient at the depthwise input's activation, the BatchNorm
+    backward sums of that input where the fused kernel has formed them, else None).  skip_res (the identity branch's gradient)
+    is added here only where the depthwise input is the block input itself."""
+    b, N = t.cfg, tape.N
+    dw_in, dw_st = _dw_input(t)
+    res = None if dw_st is not None else skip_res
+    if b.stride == 1 and b.pad_lo == (b.kernel - 1) // 2:
+        # stride 1: BN1 data gradient, depthwise weight + data gradients and the BN0 backward sums in one kernel
+        return ops.dwconv_bwd_fused(ga.view(N, t.Ho, t.Wo, b.cexp), t.d_raw, t.gate, add, t.bn1, c1, dw_in, dw_st,
+                                    m._depthwise_conv.weight, sink.of(m._depthwise_conv.weight), b.kernel, b.pad_lo,
+                                    residual=res, defer=lane.dw_reduce)
+    # BN1 backward with g = (ga*gate + add) * swish'(bn1(d_raw)), in place over ga
+    dd = ops.bn_backward_from_coeffs(ga, t.d_raw.view(N * t.Ho * t.Wo, b.cexp), t.bn1, c1, gate=t.gate, gate_add=add,
+                                     rows_per_sample=t.Ho * t.Wo, out=ga).view(N, t.Ho, t.Wo, b.cexp)
+    ops.dwconv_bwd_weight(dw_in, dd, sink.of(m._depthwise_conv.weight), b.kernel, b.stride, b.pad_lo, st=dw_st)
+    return ops.dwconv_bwd_data(dd, m._depthwise_conv.weight, b.kernel, b.stride, b.pad_lo, t.H, t.W, residual=res), None
+
+
+def _bn0_expand_backward(lane, backbone, cfg: NetCfg, tape: Tape, t: BlockTape, m, gx, part0, skip_res, sink: GradSink):
+    """The depthwise input sits behind a BatchNorm + SiLU (BN0 of an expand block, or the stem's BN for block 0):
+    gx --BN0 bwd--> dz --pw_wgrad / pw_dgrad (+skip gradient)--> g_in [N,H,W,Cin]; block 0 ends in the stem's weight gradient (None)."""
+    b, N, training = t.cfg, tape.N, tape.training
+    dw_in, dw_st = _dw_input(t)
+    bn_mod = m._bn0 if b.expand else backbone._bn0
+    M = N * t.H * t.W
+    raw2, gx2 = dw_in.view(M, dw_in.shape[3]), gx.view(M, dw_in.shape[3])
+    res = skip_res.reshape(M, b.cin) if skip_res is not None else None
+    if part0 is not None:
+        c0 = ops.bn_bwd_coeffs(part0, M, bn_mod, dw_st, sink.of(bn_mod.weight), sink.of(bn_mod.bias), training)
+        wtp = tape.wtp.get(id(m._expand_conv.weight)) if b.expand else None
+        if FOLD_BN0_EARLY and wtp is not None and ops.bnbwd_fold_takes(M, b.cexp, b.cin) == "small":
+            # the early fold: both GEMMs form dz in their operand loads, it is never written
+            lane.wgrad_bnbwd(gx2, raw2, c0, t.x.view(M, b.cin), sink.of(m._expand_conv.weight).view(b.cexp, b.cin))
+            g_in = ops.pw_dgrad_bnbwd_planes(gx2, raw2, c0, wtp, b.cin, residual=res)
+            lane.flush()
+            return g_in.view(N, t.H, t.W, b.cin)
+        dz = ops.bn_bwd_apply_plain(gx2, raw2, c0, gx2)
+    else:
+        dz = ops.bn_backward(gx2, raw2, bn_mod, dw_st, sink.of(bn_mod.weight), sink.of(bn_mod.bias), training, act=dw_st, out=gx2)
+    if not b.expand:
+        # block 0: the input is the stem's raw output -> stem weight gradient
+        dw28 = torch.zeros(cfg.stem_out, 28, dtype=torch.float32, device=dz.device)
+        ops.pw_wgrad(dz, tape.cols, dw28)
+        sink.of(backbone._conv_stem.weight).view(cfg.stem_out, 27).add_(dw28[:, :27])
+        return None
+    lane.wgrad(dz, t.x.view(M, b.cin), sink.of(m._expand_conv.weight).view(b.cexp, b.cin))
+    g_in = ops.pw_dgrad(dz, m._expand_conv.weight.view(b.cexp, b.cin), b.cin, wt=tape.wt.get(id(m._expand_conv.weight)),
+                        planes=tape.wtp.get(id(m._expand_conv.weight)), residual=res)
+    lane.flush()
+    return g_in.view(N, t.H, t.W, b.cin)
+
+
 def backbone_backward(backbone, cfg: NetCfg, tape: Tape, tap_grads: Dict[int, torch.Tensor], sink: GradSink):
     """tap_grads: {block index: dL/d out [N,Ho,Wo,Cout]} for the tapped features.  Parameter gradients are
     accumulated into `sink`.  The image gets no gradient (the reference never asks for one)."""
-    N, training = tape.N, tape.training
     g_out: Optional[torch.Tensor] = None
     lane = _WgradLane(tape.blocks[0].out.device)
     if tape.wt_event is not None:
         torch.cuda.current_stream().wait_event(tape.wt_event)
+    done = getattr(sink, "block_done", None) if getattr(sink, "on_ready", None) is not None else None
     for t in reversed(tape.blocks):
-        b, m = t.cfg, _blk(backbone, t.cfg.index)
-        tg = tap_grads.get(b.index)
+        m = _blk(backbone, t.cfg.index)
+        tg = tap_grads.get(t.cfg.index)
         if tg is not None:
             g_out = tg if g_out is None else g_out + tg
         if g_out is None:
             continue                                   # blocks after the last tap get no gradient
-        M, Mo = N * t.H * t.W, N * t.Ho * t.Wo
-        hw = t.Ho * t.Wo
-        g2 = g_out.reshape(Mo, b.cout)
-        # BN2 backward (upstream gradient carries the drop_connect scale of the sample)
-        dp = ops.bn_backward(g2, t.p_raw, m._bn2, t.bn2, sink.of(m._bn2.weight), sink.of(m._bn2.bias), training,
-                             row_scale=t.row_scale, rows_per_sample=hw)
-        # project conv: weight gradient against the recomputed activated+gated input, then data gradient
-        d2 = t.d_raw.view(Mo, b.cexp)
-        if t.a is not None:
-            lane.wgrad(dp, t.a, sink.of(m._project_conv.weight).view(b.cout, b.cexp))
-            t.a = None
-        else:
-            lane.wgrad(dp, d2, sink.of(m._project_conv.weight).view(b.cout, b.cexp), x_mode=ops.BNACT, x_scale=t.bn1.scale,
-                       x_shift=t.bn1.shift, x_gate=t.gate, rows_per_sample=hw)
-        ga = ops.pw_dgrad(dp, m._project_conv.weight.view(b.cout, b.cexp), b.cexp, wt=tape.wt.get(id(m._project_conv.weight)),
-                          planes=tape.wtp.get(id(m._project_conv.weight)))                    # dL/d(act*gate) [Mo,Cexp]
-        lane.flush()
-        del dp
-        # One pass over (ga, d_raw) yields the SE gate gradient sum_hw ga*act AND the per-sample pieces of the BN1 backward
-        # sums; the excitation backward then gives the pooled-path term `add`, and the BN1 sums follow without
-        # touching the big tensors again.
-        pooled5 = ops.se_bn1_pool(ga, d2, t.bn1, hw)
-        W2 = m._se_expand.weight.view(b.cexp, b.se)
-        if SE_PARAMS_ASIDE:
-            # the excitation's parameter gradients have no consumer on this chain: beside the weight-gradient GEMMs
-            gh = ops.se_bwd_gh(pooled5[0], t.gate, t.h, W2)
-            lane.defer(functools.partial(ops.se_bwd_params, pooled5[0], t.gate, t.s, t.h, gh,
-                                         sink.of(m._se_reduce.weight).view(b.se, b.cexp), sink.of(m._se_reduce.bias),
-                                         sink.of(m._se_expand.weight).view(b.cexp, b.se), sink.of(m._se_expand.bias)),
-                       pooled5, t.gate, t.s, t.h, gh)
-        else:
-            gh = ops.se_bwd(pooled5[0], t.gate, t.s, t.h, W2,
-                            sink.of(m._se_reduce.weight).view(b.se, b.cexp), sink.of(m._se_reduce.bias),
-                            sink.of(m._se_expand.weight).view(b.cexp, b.se), sink.of(m._se_expand.bias))
-        # pooled-path gradient `add`, the BN1 backward sums and their finalisation: one launch, no second pass over the tensors
-        c1, add = ops.bn1_coeffs(pooled5, t.gate, gh, m._se_reduce.weight.view(b.se, b.cexp), 1.0 / hw, Mo, m._bn1, t.bn1,
-                                 sink.of(m._bn1.weight), sink.of(m._bn1.bias), training)
-        dw_in, dw_st = (t.e_raw, t.bn0) if b.expand else (t.x, t.x_st)
-        skip_res = g_out if b.skip else None            # d out / d x through the identity branch
-        fused = FUSED_DW_BACKWARD and b.stride == 1 and b.pad_lo == (b.kernel - 1) // 2
-        if fused:
-            # stride 1: BN1 data gradient, depthwise weight + data gradients and the BN0 backward sums in one kernel
-            bn_mod0 = m._bn0 if b.expand else backbone._bn0
-            fin0 = (bn_mod0, sink.of(bn_mod0.weight), sink.of(bn_mod0.bias), training) if (FUSED_BN0_FINALIZE and dw_st is not None) else None
-            res = ops.dwconv_bwd_fused(ga.view(N, t.Ho, t.Wo, b.cexp), t.d_raw, t.gate, add, t.bn1, c1, dw_in, dw_st,
-                                       m._depthwise_conv.weight, sink.of(m._depthwise_conv.weight), b.kernel, b.pad_lo,
-                                       residual=None if dw_st is not None else skip_res, defer=lane.dw_reduce, bn0=fin0)
-            gx, part0, c0_fin = res if fin0 is not None else (res[0], res[1], None)
-            del ga
-        else:
-            # BN1 backward with g = (ga*gate + add) * swish'(bn1(d_raw)), in place over ga
-            dd = ops.bn_backward_from_coeffs(ga, d2, t.bn1, c1, gate=t.gate, gate_add=add, rows_per_sample=hw,
-                                             out=ga).view(N, t.Ho, t.Wo, b.cexp)
-            ops.dwconv_bwd_weight(dw_in, dd, sink.of(m._depthwise_conv.weight), b.kernel, b.stride, b.pad_lo, st=dw_st)
-            gx = ops.dwconv_bwd_data(dd, m._depthwise_conv.weight, b.kernel, b.stride, b.pad_lo, t.H, t.W,
-                                     residual=None if dw_st is not None else skip_res)
-            del dd, ga
-        if dw_st is not None:
-            # the depthwise input sits behind a BatchNorm + SiLU (BN0 of an expand block, or the stem's BN for block 0)
-            bn_mod = m._bn0 if b.expand else backbone._bn0
-            raw2 = dw_in.view(M, dw_in.shape[3])
-            gx2 = gx.view(M, dw_in.shape[3])
-            fold = fused and b.expand and FOLD_BN0_APPLY and ops.DGRAD_AS_FORWARD and b.cexp % 4 == 0
-            # round 4: the apply folded into BOTH consumers (dZ never written) where both run in split arithmetic
-            wtp = tape.wtp.get(id(m._expand_conv.weight)) if b.expand else None
-            kind = ops.bnbwd_fold_takes(M, b.cexp, b.cin) if (fused and b.expand and not fold and wtp is not None and ops.DGRAD_AS_FORWARD) else None
-            fold2 = (kind == "tile" and FOLD_BN0_BOTH) or (kind == "small" and FOLD_BN0_EARLY)
-            fold3 = (fused and b.expand and not fold and not fold2 and FOLD_BN0_WGRAD and gx2.is_contiguous() and raw2.is_contiguous()
-                     and ops.wgrad_bnbwd_dz_takes(M, b.cexp, b.cin))
-            if fused:
-                c0 = c0_fin if c0_fin is not None else ops.bn_bwd_coeffs(part0, M, bn_mod, dw_st, sink.of(bn_mod.weight), sink.of(bn_mod.bias), training)
-                if fold3:
-                    dz = ops.pw_wgrad_bnbwd_dz(gx2, raw2, c0, t.x.view(M, b.cin), sink.of(m._expand_conv.weight).view(b.cexp, b.cin))
-                elif not fold and not fold2:
-                    dz = ops.bn_bwd_apply_plain(gx2, raw2, c0, gx2)
-            else:
-                dz = ops.bn_backward(gx2, raw2, bn_mod, dw_st, sink.of(bn_mod.weight), sink.of(bn_mod.bias), training,
-                                     act=dw_st, out=gx2)
-            if fold2:
-                lane.wgrad_bnbwd(gx2, raw2, c0, t.x.view(M, b.cin), sink.of(m._expand_conv.weight).view(b.cexp, b.cin))
-                g_in = ops.pw_dgrad_bnbwd_planes(gx2, raw2, c0, wtp, b.cin,
-                                                 residual=skip_res.reshape(M, b.cin) if skip_res is not None else None)
-                lane.flush()
-                g_out = g_in.view(N, t.H, t.W, b.cin)
-            elif fold:
-                # the BN0 backward apply rides in the data-gradient GEMM's operand load (which also writes dz for the weight
-                # gradient): one pass over the Cexp-wide tensors less than bn_bwd_apply + GEMM
-                g_in, dz = ops.pw_dgrad_bnbwd(gx2, raw2, c0, m._expand_conv.weight.view(b.cexp, b.cin), b.cin,
-                                              residual=skip_res.reshape(M, b.cin) if skip_res is not None else None,
-                                              wt=tape.wt.get(id(m._expand_conv.weight)))
-                lane.wgrad(dz, t.x.view(M, b.cin), sink.of(m._expand_conv.weight).view(b.cexp, b.cin))
-                lane.flush()
-                g_out = g_in.view(N, t.H, t.W, b.cin)
-            elif b.expand:
-                if not fold3:
-                    lane.wgrad(dz, t.x.view(M, b.cin), sink.of(m._expand_conv.weight).view(b.cexp, b.cin))
-                g_in = ops.pw_dgrad(dz, m._expand_conv.weight.view(b.cexp, b.cin), b.cin, wt=tape.wt.get(id(m._expand_conv.weight)),
-                                    planes=tape.wtp.get(id(m._expand_conv.weight)),
-                                    residual=skip_res.reshape(M, b.cin) if skip_res is not None else None)
-                lane.flush()
-                g_out = g_in.view(N, t.H, t.W, b.cin)
-            else:
-                # block 0: the input is the stem's raw output -> stem weight gradient
-                dw28 = torch.zeros(cfg.stem_out, 28, dtype=torch.float32, device=dz.device)
-                ops.pw_wgrad(dz, tape.cols, dw28)
-                sink.of(backbone._conv_stem.weight).view(cfg.stem_out, 27).add_(dw28[:, :27])
-                g_out = None
+        ga = _project_backward(lane, tape, t, m, g_out, sink)
+        c1, add = _se_bn1_coeffs(tape, t, m, ga, sink)
+        skip_res = g_out if t.cfg.skip else None        # d out / d x through the identity branch
+        gx, part0 = _depthwise_backward(lane, tape, t, m, ga, c1, add, skip_res, sink)
+        del ga
+        if _dw_input(t)[1] is not None:
+            g_out = _bn0_expand_backward(lane, backbone, cfg, tape, t, m, gx, part0, skip_res, sink)
         else:
             g_out = gx
-        done = getattr(sink, "block_done", None)
-        if done is not None and getattr(sink, "on_ready", None) is not None:
+        if done is not None:
             lane.progress(done, m)   # this block's (and every later block's) parameter gradients are enqueued
     lane.join()
-    return

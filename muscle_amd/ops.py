@@ -27,25 +27,40 @@ def _f32(*shape, device):
     return torch.empty(shape, dtype=torch.float32, device=device)
 
 
-# Scratch for the entry points that take `ws` (include/muscle_hip.h): one persistent, zero-initialised buffer per
-# (device, stream) - the arrival counters in its first 64 KB are left zero by every launch, so it can be handed to one call
-# after the other.  A buffer that has to grow is REPLACED but never freed: a captured hipGraph has the old pointer baked in.
-_scratch_bufs: dict = {}
+# Persistent scratch: one buffer per (device, stream) and purpose.  A buffer that has to grow is REPLACED but never freed: a
+# captured hipGraph has the old pointer baked in.
+_scratch_bufs: dict = {}     # for the entry points that take `ws` (include/muscle_hip.h): zero-initialised - the arrival counters in
+#                              its first 64 KB are left zero by every launch, so it can be handed to one call after the other
+_wgrad_ws: dict = {}         # partial sums of the weight-gradient GEMMs
+_acc_bufs: dict = {}         # fp64 acc[64][2C] of the two-level BatchNorm statistics reduction (layers with > 1024 partial rows)
 _scratch_retired: list = []
 
 
-def _scratch(device, nbytes):
-    """(pointer, size) of this stream's scratch, at least nbytes large; (None, 0) when nbytes == 0."""
-    if nbytes <= 0:
-        return None, 0
+def _stream_buffer(bufs, device, n, dtype, floor, zero=False):
+    """This stream's buffer in `bufs`, at least n elements of dtype (`floor` when first made, so that it rarely has to grow)."""
     key = (device.index if device.index is not None else torch.cuda.current_device(), stream())
-    buf = _scratch_bufs.get(key)
-    if buf is None or buf.numel() < nbytes:
+    buf = bufs.get(key)
+    if buf is None or buf.numel() < n:
         if buf is not None:
             _scratch_retired.append(buf)
-        buf = torch.zeros(max(int(nbytes), 64 << 20), dtype=torch.uint8, device=device)
-        _scratch_bufs[key] = buf
+        buf = bufs[key] = (torch.zeros if zero else torch.empty)(max(int(n), floor), dtype=dtype, device=device)
+    return buf
+
+
+def _scratch(device, nbytes):
+    """(pointer, size) of this stream's counter scratch, at least nbytes large; (None, 0) when nbytes == 0."""
+    if nbytes <= 0:
+        return None, 0
+    buf = _stream_buffer(_scratch_bufs, device, nbytes, torch.uint8, 64 << 20, zero=True)
     return buf.data_ptr(), buf.numel()
+
+
+def _wgrad_workspace(device, nbytes):
+    return _stream_buffer(_wgrad_ws, device, nbytes, torch.uint8, 64 << 20)
+
+
+def _acc_scratch(dev, n):
+    return _stream_buffer(_acc_bufs, dev, n, torch.float64, 128 * 4096).data_ptr()
 
 
 def _call_ws(name, *args):
@@ -63,25 +78,28 @@ def _call_ws(name, *args):
 
 
 # ---- GEMMs ------------------------------------------------------------------------------------
-_uses_planes: dict = {}
+def _per_mode(ask):
+    """Remember the library's answer to `ask(M, K, N)`: it depends on the shape and the current GEMM arithmetic only."""
+    memo: dict = {}
+
+    def cached(*shape):
+        key = (get_gemm_mode(), *shape)
+        if key not in memo:
+            memo[key] = ask(*shape)
+        return memo[key]
+    return cached
 
 
+@_per_mode
 def _planes_take(M, K, N_out):
-    """Does a plain-A GEMM of this shape go to the second-generation split kernel in the current arithmetic?  (cached per mode)"""
-    key = (get_gemm_mode(), M, K, N_out)
-    r = _uses_planes.get(key)
-    if r is None:
-        r = _uses_planes[key] = bool(lib().mx_pw_fwd_uses_planes(M, K, N_out))
-    return r
+    """Does a plain-A GEMM of this shape go to the second-generation split kernel in the current arithmetic?"""
+    return bool(lib().mx_pw_fwd_uses_planes(M, K, N_out))
 
 
+@_per_mode
 def _planes_act_take(M, K, N_out):
     """The same question for the project convolution's activated-input form (mx_pw_fwd_planes_act)."""
-    key = ("act", get_gemm_mode(), M, K, N_out)
-    r = _uses_planes.get(key)
-    if r is None:
-        r = _uses_planes[key] = bool(lib().mx_pw_fwd_act_uses_planes(M, K, N_out))
-    return r
+    return bool(lib().mx_pw_fwd_act_uses_planes(M, K, N_out))
 
 
 def pw_fwd(A, W, N_out, *, a_mode=PLAIN, a_scale=None, a_shift=None, a_gate=None, rows_per_sample=1,
@@ -223,15 +241,13 @@ def transpose(W):
     return out
 
 
-DGRAD_AS_FORWARD = True      # dX = G W as a forward GEMM against W^T (row-major LDS images, 16-column tiles); False: NN kernel
-
-
 def pw_dgrad(G, W, N_in, *, residual=None, out=None, wt=None, planes=None):
-    """G: [M, K=Cout]; W: [Cout, Cin] -> dX [M, Cin].  wt: W^T [Cin, Cout] if the caller already has it, planes: its pre-split image."""
+    """G: [M, K=Cout]; W: [Cout, Cin] -> dX [M, Cin], as a forward GEMM against W^T (row-major LDS images, 16-column tiles; the NN
+    kernel where K % 4 != 0).  wt: W^T [Cin, Cout] if the caller already has it, planes: its pre-split image."""
     M, K = G.shape
     if out is None:
         out = _f32(M, N_in, device=G.device)
-    if DGRAD_AS_FORWARD and K % 4 == 0:
+    if K % 4 == 0:
         if planes is not None and _planes_take(M, K, N_in):
             call("mx_pw_fwd_planes", ptr(G), planes, ptr(out), M, K, N_in, G.stride(0), N_in, None, ptr(residual), 0, None, stream())
             return out
@@ -244,7 +260,8 @@ def pw_dgrad(G, W, N_in, *, residual=None, out=None, wt=None, planes=None):
 
 def pw_dgrad_bnbwd(G, X, coef, W, N_in, *, residual=None, wt=None):
     """The BatchNorm backward apply dZ = c1*G + c2*X + c3 (coef [3, K], as bn_bwd_coeffs returns it) folded into the data
-    gradient dX = dZ W: returns (dX [M, N_in], dZ [M, K]) - dZ is materialised by the GEMM for the weight gradient."""
+    gradient dX = dZ W: returns (dX [M, N_in], dZ [M, K]) - dZ is materialised by the GEMM for the weight gradient.
+    Lab kernel: not on the engine's path."""
     M, K = G.shape
     out = _f32(M, N_in, device=G.device)
     dz = torch.empty_like(G)
@@ -262,21 +279,18 @@ def pw_dgrad_bnbwd_planes(G, X, coef, planes, N_in, *, residual=None):
     return out
 
 
+@_per_mode
 def bnbwd_fold_takes(M, K, N):
     """Which weight-gradient kernel can fold the BatchNorm backward apply for dZ [M, K] (data gradient against W^T [N, K], weight
     gradient dW [K, N]) in the current arithmetic, given that the data gradient takes the planes kernel: "small" (the HBM-bound
     small-output kernel of stages 1-2), "tile" (the split-arithmetic tiled kernel) or None."""
-    key = ("fold", get_gemm_mode(), M, K, N)
-    r = _uses_planes.get(key, 0)
-    if r == 0:
-        r = None
-        if _planes_take(M, K, N):
-            if lib().mx_pw_wgrad_small_bnbwd_ok(M, K, N):
-                r = "small"
-            elif lib().mx_pw_wgrad_small_ws(M, K, N, PLAIN) <= 0 and lib().mx_pw_wgrad_tile_bnbwd_ok(M, K, N):
-                r = "tile"
-        _uses_planes[key] = r
-    return r
+    if not _planes_take(M, K, N):
+        return None
+    if lib().mx_pw_wgrad_small_bnbwd_ok(M, K, N):
+        return "small"
+    if lib().mx_pw_wgrad_small_ws(M, K, N, PLAIN) <= 0 and lib().mx_pw_wgrad_tile_bnbwd_ok(M, K, N):
+        return "tile"
+    return None
 
 
 def pw_wgrad_bnbwd(G, G2, coef, X, dW):
@@ -294,17 +308,14 @@ def pw_wgrad_bnbwd(G, G2, coef, X, dW):
 
 
 def wgrad_bnbwd_dz_takes(R, Co, Ci) -> bool:
-    """True where `pw_wgrad_bnbwd_dz` exists: the wave-specialised split weight-gradient kernel takes dW [Co, Ci] over R rows."""
-    key = ("dzfold", get_gemm_mode(), get_wgrad_kernel(), R, Co, Ci)
-    r = _uses_planes.get(key)
-    if r is None:
-        r = _uses_planes[key] = bool(lib().mx_pw_wgrad_tile_bnbwd_dz_ok(R, Co, Ci, Co, Ci))
-    return r
+    """True where `pw_wgrad_bnbwd_dz` exists: the wave-specialised split weight-gradient kernel takes dW [Co, Ci] over R rows.
+    Lab kernel: not on the engine's path."""
+    return bool(lib().mx_pw_wgrad_tile_bnbwd_dz_ok(R, Co, Ci, Co, Ci))
 
 
 def pw_wgrad_bnbwd_dz(G, G2, coef, X, dW, dz=None):
     """dW[Co, Ci] += dZ^T X with dZ = c1*G + c2*G2 + c3 formed AND stored by the weight-gradient kernel's loader waves (round 5):
-    returns dZ [R, Co] for the data gradient that follows; mx_bn_bwd_apply is not launched."""
+    returns dZ [R, Co] for the data gradient that follows; mx_bn_bwd_apply is not launched.  Lab kernel: not on the engine's path."""
     R, Co = G.shape
     Ci = X.shape[1]
     if dz is None:
@@ -316,21 +327,8 @@ def pw_wgrad_bnbwd_dz(G, G2, coef, X, dW, dz=None):
     return dz
 
 
-_wgrad_ws: dict = {}
-_wgrad_ws_retired: list = []      # outgrown workspaces stay alive: captured graphs keep writing to them
 WGRAD_TILE = os.environ.get("MUSCLE_WGRAD_TILE", "1") == "1"   # large outputs: tiled deterministic kernel (wgrad.hip) instead of the atomic TN GEMM
 WGRAD_SMALL = True       # small outputs / long reductions: one workgroup owns the whole output, deterministic partial sums
-
-
-def _wgrad_workspace(device, nbytes):
-    key = (device.index if device.index is not None else torch.cuda.current_device(), stream())
-    ws = _wgrad_ws.get(key)
-    if ws is None or ws.numel() < nbytes:
-        if ws is not None:
-            _wgrad_ws_retired.append(ws)
-        ws = torch.empty(max(nbytes, 64 << 20), dtype=torch.uint8, device=device)
-        _wgrad_ws[key] = ws
-    return ws
 
 
 def pw_wgrad(G, X, dW, *, x_mode=PLAIN, x_scale=None, x_shift=None, x_gate=None, rows_per_sample=1):
@@ -413,21 +411,6 @@ def fold_block(We, bn0, bn1, Wp, bn2, out=None):
          ptr(Wp.detach()), *four(bn2), cin, cexp, cout, ptr(f.get("We")), ptr(f.get("be")), ptr(vec[1]), ptr(vec[2]),
          ptr(f["Wp"]), ptr(f["bp"]), stream())
     return f
-
-
-_acc_bufs: dict = {}
-
-
-def _acc_scratch(dev, n):
-    """fp64 scratch acc[64][2C] of the two-level statistics reduction (only touched when a layer has more than 1024 partial
-    rows): one persistent buffer per (device, stream) instead of an allocation per BatchNorm; outgrown ones are kept."""
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), stream())
-    t = _acc_bufs.get(key)
-    if t is None or t.numel() < n:
-        if t is not None:
-            _scratch_retired.append(t)
-        t = _acc_bufs[key] = torch.empty(max(n, 128 * 4096), dtype=torch.float64, device=dev)
-    return t.data_ptr()
 
 
 _nbt_pending: list = []
@@ -513,7 +496,8 @@ def dwconv_bwd_fused(dA, D, gate, add, st1: BNState, c1, X, st0: Optional[BNStat
     defer: a callable taking (scratch, dW) - the addition of the weight gradient's partial rows is handed to it (e.g. queued for
     the side stream) instead of being launched behind the kernel.
     bn0 = (bn module, dgamma, dbeta, training): the kernel finishes the BatchNorm-0 backward statistics itself (its last workgroup per
-    channel chunk; mx_dwconv_bwd_fused_bn0) and a third value is returned: the [3, C] coefficients bn_bwd_coeffs would have made."""
+    channel chunk; mx_dwconv_bwd_fused_bn0) and a third value is returned: the [3, C] coefficients bn_bwd_coeffs would have made.
+    Lab kernel: the engine never passes bn0."""
     N, H, Wd, C = X.shape
     gX = _f32(N, H, Wd, C, device=X.device)
     P = lib().mx_dwconv_bwd_fused_parts(N, H, Wd, C, K)
@@ -625,7 +609,8 @@ def se_bwd(ggate, gate, s, h, W2, dW1, db1, dW2, db2):
 
 
 def se_bwd_gh(ggate, gate, h, W2):
-    """First half of se_bwd: gh alone (the data-gradient chain needs nothing else of the excitation backward)."""
+    """First half of se_bwd: gh alone (the data-gradient chain needs nothing else of the excitation backward).
+    Lab kernel: not on the engine's path."""
     N, C = ggate.shape
     gh = torch.empty_like(h)
     call("mx_se_bwd_gh", ptr(ggate), ptr(gate), ptr(h), ptr(W2), ptr(gh), N, C, W2.shape[1], stream())
@@ -633,7 +618,8 @@ def se_bwd_gh(ggate, gate, h, W2):
 
 
 def se_bwd_params(ggate, gate, s, h, gh, dW1, db1, dW2, db2):
-    """Second half of se_bwd: the parameter gradients (+=), which nothing reads before the optimizer."""
+    """Second half of se_bwd: the parameter gradients (+=), which nothing reads before the optimizer.
+    Lab kernel: not on the engine's path."""
     N, C = ggate.shape
     call("mx_se_bwd_params", ptr(ggate), ptr(gate), ptr(s), ptr(h), ptr(gh), ptr(dW1), ptr(db1), ptr(dW2), ptr(db2), N, C,
          h.shape[1], stream())

@@ -265,8 +265,7 @@ def test_grad_averager_behind_the_side_stream_issues_every_chunk_once(monkeypatc
     monkeypatch.setattr(torch.cuda, "stream", lambda s: _Ctx(s))
     monkeypatch.setattr(torch.cuda, "current_device", lambda: 0)
     monkeypatch.setattr(engine, "WGRAD_SIDE_STREAM", True)
-    monkeypatch.setattr(engine, "WGRAD_CUS", 0)
-    monkeypatch.setitem(engine._side_streams, (0, 0), side)
+    monkeypatch.setitem(engine._side_streams, 0, side)
     monkeypatch.setattr(ops, "pw_wgrad", lambda G, X, dW, **kw: log.append(("wgrad", active[-1].name, dW)))
 
     n, chunk = 1000, 64

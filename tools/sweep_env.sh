@@ -1,7 +1,6 @@
 run() { env "$@" python bench.py --no-cpu-baseline --no-other-arith --no-configs --steps 10 --warmup 3 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.readline()); print('$*', round(d['ms_per_step'],2))"; }
 run A=1
-run MUSCLE_FOLD_BN0=1
 run MUSCLE_MATERIALISE_ABOVE=64
 run MUSCLE_MATERIALISE_ABOVE=224
 run MUSCLE_MATERIALISE_ABOVE=384

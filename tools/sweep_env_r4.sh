@@ -11,5 +11,4 @@ run MX_WGRAD_TILE_PERSIST=1
 run MX_WGRAD_TILE_PERSIST=2
 run MX_WGRAD_SMALL_RMIN=16384
 run MX_WGRAD_SMALL_RMIN=262144
-run MUSCLE_WGRAD_PRIO=-1
 run A=3

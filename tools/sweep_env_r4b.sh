@@ -11,5 +11,4 @@ run A=2
 run MX_DW_GROUPS=2048
 run MX_COLREDUCE_BLOCKS=2048
 run MX_STREAM_BLOCKS=8192
-run MUSCLE_FOLD_BN0_BOTH=1
 run A=3
