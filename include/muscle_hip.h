@@ -338,6 +338,16 @@ int mx_seg_infer(const long* passes, int npass, int lds, int K, int H, int W, co
                  float* prob, void* stream);
 int mx_seg_confusion(const unsigned char* pred, const unsigned char* gt, int K, int H, int W, long long* counts, void* stream);
 
+/* mx_seg_infer_batch: mx_seg_infer for B images of one output size (H, W) in one launch (the per-epoch validation of
+ * train_muscle.py:224-283, one pass per image).  rows: device int64 [nrow][8] {address of the row's NHWC logits [h,w,lds],
+ * h, w, Hs, Ws, flip, image 0..B-1, 0}; every row belongs to one image and every image has at least one row.  Per image the
+ * rows are summed in table order and divided by the image's row count: pred uint8 [B,H,W] and prob fp32 [B,K,H,W] (NULL =
+ * not written) hold, per image, the bits mx_seg_infer produces over that image's rows; cls_scale fp32 [B,K] or NULL.
+ * gt uint8 [B,H,W] with counts int64 [K][3] (both or neither): mx_seg_confusion's (TP, P, T) of src/evaluation.py:36-50
+ * over all B images, accumulated across calls with integer atomics (exact). */
+int mx_seg_infer_batch(const long* rows, int nrow, int B, int lds, int K, int H, int W, const float* cls_scale, unsigned char* pred,
+                       float* prob, const unsigned char* gt, long long* counts, void* stream);
+
 /* ---- input stage (src/data.py:215-332, src/imutils.py:143-181,376-388) ------------------------------
  * dst[n,3,Hd,Wd] (fp32, fully written) = RandomCrop container of color_norm(uint8 HWC crop n) at (top,left), CHW, zeros
  * elsewhere; src = packed crops, jobs = n x 8 int32 {src_off, sh, sw, top, left, ey | ex<<16, eh | ew<<16, source row
@@ -398,6 +408,18 @@ int mx_irn_finish(const float* rw, int C, int h, int w, int H, int W, float bg_t
  * counts[t][k][0..2] += (TP, P, T).  pred [K,H,W] fp32 (cam_maxnorm'ed), label [K], gt uint8 [H,W], counts int64 [nt][K][3]. */
 int mx_eval_confusion(const float* pred, const float* label, const unsigned char* gt, const float* thresholds, int nt, int K, int H,
                       int W, long long* counts, void* stream);
+
+/* ---- the same evaluation for B images of one size from the model's LOW-RESOLUTION SGC maps (train_mcl.py:297-303 +
+ * src/evaluation.py:19-52): sgc NHWC [B,h,w,lds] (cam='cam_lr'), label_with_bg [B,K] (entry 0 unused), gt uint8 [B,H,W],
+ * thresholds [nt], counts int64 [nt][K][3] accumulated across calls.  Per image and channel the kernel takes the extremes of
+ * relu(mx_upsample_to_nchw's value) over the H x W grid, then per pixel recomputes that value, applies cam_maxnorm
+ * (train_mcl.py:21-28, mx_maxnorm's expression) and counts as mx_eval_confusion does: the table is the one the chain
+ * mx_upsample_to_nchw -> mx_maxnorm -> mx_eval_confusion gives per image, integer for integer, and no [K,H,W] tensor is
+ * read or written.  K <= min(lds, 24), lds a multiple of 4, nt <= 64.  ws: mx_rapid_eval_lr_ws(B, K) bytes of scratch (the
+ * [B][K][2] extremes; zeroed by the call). */
+long mx_rapid_eval_lr_ws(int B, int K);
+int mx_rapid_eval_lr(const float* sgc, const float* label_with_bg, const unsigned char* gt, const float* thresholds, int nt, int B,
+                     int h, int w, int lds, int K, int H, int W, long long* counts, void* ws, long ws_bytes, void* stream);
 
 /* ---- CAM quality evaluation (src/evaluation.py:25-50, input_type='npy'), one image, ALL thresholds of the curve (:126-133):
  * predict(t) = argmax_k [t, tensor_1..tensor_{K-1}] with tensor_{keys[j]+1} = maps[j] and absent channels 0 (first maximum

@@ -188,6 +188,53 @@ __device__ __forceinline__ void bn_bwd_reduce_finalize_32(const float* part, int
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 
+// ---------------------------------------------------------------------------
+// Arithmetic that more than one kernel must reproduce bit for bit.  hipcc contracts a*b + c*d per expression and per kernel, so a
+// second kernel written with the same C expression can round differently; here every operation is spelt out with contraction off.
+//   lerp_a(a, b, w) = fma(w, b, rn((1-w)*a))      lerp_b(a, b, w) = fma(1-w, a, rn(w*b))      blend_rows = rn((1-wy)*r0) + rn(wy*r1)
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ float lerp_a(float a, float b, float w) {
+#pragma clang fp contract(off)
+  float p = (1.f - w) * a;
+  return __builtin_fmaf(w, b, p);
+}
+__device__ __forceinline__ float lerp_b(float a, float b, float w) {
+#pragma clang fp contract(off)
+  float p = w * b;
+  return __builtin_fmaf(1.f - w, a, p);
+}
+__device__ __forceinline__ float blend_rows(float r0, float r1, float wy) {
+#pragma clang fp contract(off)
+  float p0 = (1.f - wy) * r0, p1 = wy * r1;
+  return p0 + p1;
+}
+// mx_upsample_to_nchw (MuSCLe.py:256-257), operation for operation as upsample_to_nchw_kernel has always executed it: the
+// align_corners coordinate from the ROUNDED product scale*d (w1 = rn(scale*d) - i0, no fma), then
+//   value = rn((1-wy) * lerp_a(a00, a01, wx)) + rn(wy * lerp_b(a10, a11, wx))
+// Shared by that kernel and by the kernels that recompute its pixels instead of reading them (mx_rapid_eval_lr).
+__device__ __forceinline__ void bil_coord_rn(int d, int in, int out, int& i0, int& i1, float& w1) {
+#pragma clang fp contract(off)
+  float scale = (out > 1) ? (float)(in - 1) / (float)(out - 1) : 0.f;
+  float s = scale * (float)d;
+  i0 = (int)s;
+  if (i0 > in - 1) i0 = in - 1;
+  i1 = i0 + ((i0 < in - 1) ? 1 : 0);
+  w1 = s - (float)i0;
+}
+__device__ __forceinline__ float upsample_ac_value(float a00, float a01, float a10, float a11, float wy, float wx) {
+  return blend_rows(lerp_a(a00, a01, wx), lerp_b(a10, a11, wx), wy);
+}
+// cam_maxnorm (train_mcl.py:21-28) of one value from its channel's extremes mn / mx of relu(x), as mx_maxnorm evaluates it:
+//   y = relu((relu(x) - mn - 1e-6) * (1 / (mx - mn + 1e-6)))
+__device__ __forceinline__ float maxnorm_inv(float mn, float mx) {
+#pragma clang fp contract(off)
+  return 1.f / (mx - mn + 1e-6f);
+}
+__device__ __forceinline__ float maxnorm_apply(float x, float mn, float inv) {
+#pragma clang fp contract(off)
+  return fmaxf((fmaxf(x, 0.f) - mn - 1e-6f) * inv, 0.f);
+}
+
 // Operand prologue descriptor used by the GEMM and elementwise kernels.
 // A "matrix" is [rows, cols] row-major fp32 with cols == channels (NHWC activations).
 //   mode 0 PLAIN : v = p[r,c]

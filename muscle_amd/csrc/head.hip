@@ -57,12 +57,12 @@ __global__ __launch_bounds__(256) void upsample_to_nchw_kernel(const float* src,
     int k = (int)(q % K), n = (int)(q / K);
     int y0, y1, x0, x1;
     float wy, wx;
-    bil_coord(y, Hs, Hd, y0, y1, wy);
-    bil_coord(x, Ws, Wd, x0, x1, wx);
+    bil_coord_rn(y, Hs, Hd, y0, y1, wy);
+    bil_coord_rn(x, Ws, Wd, x0, x1, wx);
     const float* b = src + (long)n * Hs * Ws * lds + k;
     float a00 = b[((long)y0 * Ws + x0) * lds], a01 = b[((long)y0 * Ws + x1) * lds];
     float a10 = b[((long)y1 * Ws + x0) * lds], a11 = b[((long)y1 * Ws + x1) * lds];
-    dst[i] = (1.f - wy) * ((1.f - wx) * a00 + wx * a01) + wy * ((1.f - wx) * a10 + wx * a11);
+    dst[i] = upsample_ac_value(a00, a01, a10, a11, wy, wx);   // common.h: the bits this kernel has always produced
   }
 }
 
@@ -309,9 +309,28 @@ __device__ __forceinline__ void seg_softmax_at(const float* src, int h, int w, i
 }
 
 // tab: npass x 8 int64 {address of the pass's [h,w,lds] logits, h, w, Hs, Ws, flip, 0, 0}
+// BATCH (mx_seg_infer_batch): blockIdx.y is the image; column 6 of the table is the row's image, rows of other images are
+// skipped, so an image's passes are summed in table order exactly as the single-image launch sums them; the mean divides by
+// the image's own row count; cls / pred / prob are per image; with gt the (TP, P, T) counts of seg_confusion_kernel are
+// taken here, per workgroup in LDS with one flush of integer atomics.
+template <bool BATCH>
 __global__ __launch_bounds__(256) void seg_infer_kernel(const long* tab, int npass, int lds, int K, int H, int W,
-                                                        const float* cls, unsigned char* pred, float* prob) {
+                                                        const float* cls, unsigned char* pred, float* prob,
+                                                        const unsigned char* gt, long long* counts) {
   const long HW = (long)H * W;
+  __shared__ int sc[BATCH ? SEG_MAXK * 3 : 1];
+  const int img = BATCH ? blockIdx.y : 0;
+  int mine = npass;
+  if (BATCH) {
+    cls = cls ? cls + (long)img * K : nullptr;
+    pred += img * HW;
+    prob = prob ? prob + (long)img * K * HW : nullptr;
+    gt = gt ? gt + img * HW : nullptr;
+    mine = 0;
+    for (int n = 0; n < npass; ++n) mine += (tab[n * 8 + 6] == img) ? 1 : 0;
+    for (int i = threadIdx.x; i < K * 3; i += 256) sc[i] = 0;
+    __syncthreads();
+  }
   for (long i = blockIdx.x * 256L + threadIdx.x; i < HW; i += (long)gridDim.x * 256) {
     const int X = (int)(i % W), Y = (int)(i / W);
     float acc[SEG_MAXK];
@@ -319,6 +338,7 @@ __global__ __launch_bounds__(256) void seg_infer_kernel(const long* tab, int npa
     for (int k = 0; k < SEG_MAXK; ++k) acc[k] = 0.f;
     for (int n = 0; n < npass; ++n) {
       const long* e = tab + n * 8;
+      if (BATCH && e[6] != img) continue;
       const float* src = reinterpret_cast<const float*>(e[0]);
       const int h = (int)e[1], w = (int)e[2], Hs = (int)e[3], Ws = (int)e[4];
       const int Xr = e[5] ? (W - 1 - X) : X;          // np.flip(axis=1) after the resize
@@ -335,7 +355,7 @@ __global__ __launch_bounds__(256) void seg_infer_kernel(const long* tab, int npa
         for (int k = 0; k < SEG_MAXK; ++k) acc[k] += f * p[k];
       }
     }
-    const float fn = (float)npass;
+    const float fn = (float)mine;
     float best = 0.f;
     int bk = 0;
 #pragma unroll
@@ -348,6 +368,21 @@ __global__ __launch_bounds__(256) void seg_infer_kernel(const long* tab, int npa
       }
     }
     pred[i] = (unsigned char)bk;
+    if (BATCH && gt) {
+      const int g = gt[i];
+      if (g < 255) {
+        atomicAdd(&sc[bk * 3 + 1], 1);
+        if (g < K) {
+          atomicAdd(&sc[g * 3 + 2], 1);
+          if (bk == g) atomicAdd(&sc[g * 3 + 0], 1);
+        }
+      }
+    }
+  }
+  if (BATCH && gt) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < K * 3; i += 256)
+      if (sc[i]) atomicAdd((unsigned long long*)&counts[i], (unsigned long long)sc[i]);
   }
 }
 
@@ -436,6 +471,144 @@ __global__ __launch_bounds__(256) void eval_confusion_kernel(const float* pred, 
 }
 
 // ---------------------------------------------------------------------------
+// mx_rapid_eval_lr: the rapid evaluation of B images of one size straight from the model's low-resolution SGC maps
+// (cam='cam_lr', NHWC [B,h,w,lds]): train_mcl.py:297-303 + src/evaluation.py:19-52 without any [K,H,W] tensor.  Every
+// full-resolution value is recomputed from its <= 4 low-res neighbours with upsample_ac_value (common.h: the bits of
+// mx_upsample_to_nchw), normalised with maxnorm_apply (the bits of mx_maxnorm) and counted as eval_confusion_kernel counts.
+// Grid: (row bands, images); a workgroup owns `rows` consecutive rows of one image, one thread one pixel at a time with the
+// pixel's coordinates and weights computed once and the channels read 16 bytes at a time.
+// Phase (a), rapid_extremes_kernel: ext[b][k] = {~bits(min), bits(max)} of relu(upsample) over the H x W grid.  The values
+//   are non-negative floats, whose bit patterns order as the floats do, and min / max do not depend on order: wave reduce,
+//   LDS integer atomicMax, one global integer atomicMax per workgroup and entry (the min is kept as the complement, so both
+//   are maxima over a zero-filled scratch).  Exact, the same bits every run.
+// Phase (b), rapid_count_kernel: per pixel with gt < 255 the first maximum over k = 1..K-1 of half(maxnorm * label_k), then
+//   per threshold P[pr]++ and TP[g] += (pr == g) in LDS; T[g] does not depend on the threshold: one LDS counter per class,
+//   added to every threshold's column at the flush.
+// ---------------------------------------------------------------------------
+#define REV_MAXK 24
+#define REV_MAXT 64
+
+struct RevPixel { int o00, o01, o10, o11; float wy, wx; };
+
+__device__ __forceinline__ RevPixel rev_pixel(int y, int x, int h, int w, int lds, int H, int W) {
+  int y0, y1, x0, x1;
+  RevPixel p;
+  bil_coord_rn(y, h, H, y0, y1, p.wy);
+  bil_coord_rn(x, w, W, x0, x1, p.wx);
+  p.o00 = (y0 * w + x0) * lds; p.o01 = (y0 * w + x1) * lds;
+  p.o10 = (y1 * w + x0) * lds; p.o11 = (y1 * w + x1) * lds;
+  return p;
+}
+// channels 4q .. 4q+3 of the upsampled map at the pixel
+__device__ __forceinline__ float4 rev_quad(const float* src, const RevPixel& p, int q) {
+  const float4 a00 = ld4(src + p.o00 + q * 4), a01 = ld4(src + p.o01 + q * 4);
+  const float4 a10 = ld4(src + p.o10 + q * 4), a11 = ld4(src + p.o11 + q * 4);
+  return make_float4(upsample_ac_value(a00.x, a01.x, a10.x, a11.x, p.wy, p.wx), upsample_ac_value(a00.y, a01.y, a10.y, a11.y, p.wy, p.wx),
+                     upsample_ac_value(a00.z, a01.z, a10.z, a11.z, p.wy, p.wx), upsample_ac_value(a00.w, a01.w, a10.w, a11.w, p.wy, p.wx));
+}
+// bit pattern of relu(v) with the sign of a zero dropped (fmaxf(-0, 0) may be either zero; mx_maxnorm's result does not
+// depend on which: the extremes only enter x - mn - 1e-6 and mx - mn + 1e-6)
+__device__ __forceinline__ unsigned rev_bits(float v) { return __float_as_uint(fmaxf(v, 0.f)) & 0x7fffffffu; }
+
+__global__ __launch_bounds__(256) void rapid_extremes_kernel(const float* sgc, int h, int w, int lds, int K, int H, int W, int rows,
+                                                             unsigned* ext) {
+  __shared__ unsigned se[REV_MAXK * 2];
+  const int b = blockIdx.y, yb = blockIdx.x * rows;
+  const int npix = min(rows, H - yb) * W;
+  const float* src = sgc + (long)b * h * w * lds;
+  if (threadIdx.x < REV_MAXK * 2) se[threadIdx.x] = 0u;
+  __syncthreads();
+  unsigned lo[REV_MAXK], hi[REV_MAXK];                 // lo = ~bits of the running minimum: both are running maxima
+#pragma unroll
+  for (int k = 0; k < REV_MAXK; ++k) { lo[k] = 0u; hi[k] = 0u; }
+  for (int p = threadIdx.x; p < npix; p += 256) {
+    const RevPixel px = rev_pixel(yb + p / W, p % W, h, w, lds, H, W);
+#pragma unroll
+    for (int q = 0; q < REV_MAXK / 4; ++q) {
+      if (q * 4 < K) {                                 // quad q lies inside the row: K <= lds and lds % 4 == 0
+        const float4 v = rev_quad(src, px, q);
+        const unsigned u[4] = {rev_bits(v.x), rev_bits(v.y), rev_bits(v.z), rev_bits(v.w)};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { lo[q * 4 + j] = max(lo[q * 4 + j], ~u[j]); hi[q * 4 + j] = max(hi[q * 4 + j], u[j]); }
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < REV_MAXK; ++k) {                 // (a thread without a pixel still holds 0, the identity of both maxima)
+    if (k < K) {
+      unsigned a = lo[k], c = hi[k];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) { a = max(a, (unsigned)__shfl_xor((int)a, o, 64)); c = max(c, (unsigned)__shfl_xor((int)c, o, 64)); }
+      if ((threadIdx.x & 63) == 0) { atomicMax(&se[k * 2], a); atomicMax(&se[k * 2 + 1], c); }
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < K * 2) atomicMax(&ext[(long)b * K * 2 + threadIdx.x], se[threadIdx.x]);
+}
+
+__global__ __launch_bounds__(256) void rapid_count_kernel(const float* sgc, const float* label, const unsigned char* gt, const float* thr,
+                                                          int nt, int h, int w, int lds, int K, int H, int W, int rows,
+                                                          const unsigned* ext, long long* counts) {
+  __shared__ int lc[REV_MAXT * REV_MAXK * 2];          // [nt][K][2] = (TP, P)
+  __shared__ int ht[REV_MAXK];                         // T per class
+  __shared__ float smn[REV_MAXK], sinv[REV_MAXK], slab[REV_MAXK], sth[REV_MAXT];
+  const int b = blockIdx.y, yb = blockIdx.x * rows;
+  const int npix = min(rows, H - yb) * W;
+  const float* src = sgc + (long)b * h * w * lds;
+  const unsigned char* g8 = gt + ((long)b * H + yb) * W;
+  for (int i = threadIdx.x; i < nt * K * 2; i += 256) lc[i] = 0;
+  if (threadIdx.x < REV_MAXK) {
+    const int k = threadIdx.x;
+    ht[k] = 0;
+    float mn = 0.f, mx = 0.f, lb = 0.f;
+    if (k < K) {
+      mn = __uint_as_float(~ext[((long)b * K + k) * 2]);
+      mx = __uint_as_float(ext[((long)b * K + k) * 2 + 1]);
+      lb = label[(long)b * K + k];
+    }
+    smn[k] = mn; sinv[k] = maxnorm_inv(mn, mx); slab[k] = lb;
+  }
+  if (threadIdx.x < nt) sth[threadIdx.x] = thr[threadIdx.x];
+  __syncthreads();
+  for (int p = threadIdx.x; p < npix; p += 256) {
+    const int g = g8[p];
+    if (g >= 255) continue;
+    const RevPixel px = rev_pixel(yb + p / W, p % W, h, w, lds, H, W);
+    float best = -1.f;                                 // values are >= 0; strict > keeps the first maximum
+    int bk = 0;
+#pragma unroll
+    for (int q = 0; q < REV_MAXK / 4; ++q) {
+      if (q * 4 < K) {
+        const float4 u = rev_quad(src, px, q);
+        const float v[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int k = q * 4 + j;
+          if (k >= 1 && k < K) {
+            const float m = maxnorm_apply(v[j], smn[k], sinv[k]);
+            const float hv = __half2float(__float2half_rn(m * slab[k]));
+            if (hv > best) { best = hv; bk = k; }
+          }
+        }
+      }
+    }
+    if (g < K) atomicAdd(&ht[g], 1);
+    for (int t = 0; t < nt; ++t) {
+      const int pr = (sth[t] >= best) ? 0 : bk;        // channel 0 holds the threshold and precedes every other channel
+      atomicAdd(&lc[(t * K + pr) * 2 + 1], 1);
+      if (pr == g) atomicAdd(&lc[(t * K + g) * 2], 1);
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < nt * K; i += 256) {
+    unsigned long long* d = (unsigned long long*)&counts[(long)i * 3];
+    if (lc[i * 2]) atomicAdd(d + 0, (unsigned long long)lc[i * 2]);
+    if (lc[i * 2 + 1]) atomicAdd(d + 1, (unsigned long long)lc[i * 2 + 1]);
+    if (ht[i % K]) atomicAdd(d + 2, (unsigned long long)ht[i % K]);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // infer_mcl.py:107-148 for one image in ONE launch: every pass of the multi-scale / flip list, both maps (raw CAM and
 // SGC), only the channels the script keeps (the image's labels, :172-174).  Per output pixel, pass and kept channel the
 // value is exactly infer_accum_kernel's: the hp_coord footprint of (Y, flip ? W-1-X : X), four bil_lr taps, the same
@@ -457,16 +630,7 @@ __global__ __launch_bounds__(256) void eval_confusion_kernel(const float* pred, 
 //   value = rn((1-wy)*R0) + rn(wy*R1)
 // tests/test_gpu_cam_infer.py asserts the equality bit for bit; if a compiler change moves infer_accum_kernel's
 // contraction, that test says so and this block is re-derived from the new ISA.
-__device__ __forceinline__ float lerp_a(float a, float b, float w) {
-#pragma clang fp contract(off)
-  float p = (1.f - w) * a;
-  return __builtin_fmaf(w, b, p);
-}
-__device__ __forceinline__ float lerp_b(float a, float b, float w) {
-#pragma clang fp contract(off)
-  float p = w * b;
-  return __builtin_fmaf(1.f - w, a, p);
-}
+// lerp_a, lerp_b and blend_rows are in common.h (mx_upsample_to_nchw's value is built from the same three).
 __device__ __forceinline__ void bil_coord_x(int d, int in, int out, int& i0, int& i1, float& w1) {
 #pragma clang fp contract(off)
   float scale = (out > 1) ? (float)(in - 1) / (float)(out - 1) : 0.f;
@@ -494,11 +658,6 @@ __device__ __forceinline__ float bil_tap(const float* b, const int (&o)[4], floa
 __device__ __forceinline__ float add_rn(float a, float b) {
 #pragma clang fp contract(off)
   return a + b;
-}
-__device__ __forceinline__ float blend_rows(float r0, float r1, float wy) {
-#pragma clang fp contract(off)
-  float p0 = (1.f - wy) * r0, p1 = wy * r1;
-  return p0 + p1;
 }
 
 template <int CH, int NMAP>
@@ -750,8 +909,50 @@ int mx_seg_infer(const long* passes, int npass, int lds, int K, int H, int W, co
                  float* prob, void* stream) {
   MX_CHECK_ARG(passes && pred && npass > 0 && K >= 1 && K <= SEG_MAXK && K <= lds && lds % 4 == 0 && H > 0 && W > 0,
                "seg_infer: bad args npass=%d K=%d lds=%d H=%d W=%d", npass, K, lds, H, W);
-  hipLaunchKernelGGL(seg_infer_kernel, dim3(gs((long)H * W)), dim3(256), 0, (hipStream_t)stream, passes, npass, lds, K, H, W,
-                     cls_scale, pred, prob);
+  hipLaunchKernelGGL(seg_infer_kernel<false>, dim3(gs((long)H * W)), dim3(256), 0, (hipStream_t)stream, passes, npass, lds, K, H,
+                     W, cls_scale, pred, prob, (const unsigned char*)nullptr, (long long*)nullptr);
+  MX_LAUNCH_CHECK();
+  return MX_OK;
+}
+
+int mx_seg_infer_batch(const long* rows, int nrow, int B, int lds, int K, int H, int W, const float* cls_scale, unsigned char* pred,
+                       float* prob, const unsigned char* gt, long long* counts, void* stream) {
+  MX_CHECK_ARG(rows && pred, "seg_infer_batch: NULL table or pred");
+  MX_CHECK_ARG((gt == nullptr) == (counts == nullptr), "seg_infer_batch: gt and counts go together");
+  MX_CHECK_ARG(B > 0 && B <= 65535 && nrow >= B && nrow <= 4096 && K >= 1 && K <= SEG_MAXK && K <= lds && lds % 4 == 0 && H > 0 &&
+                   W > 0 && (long)B * K * H * W < (1L << 40),
+               "seg_infer_batch: bad args nrow=%d B=%d K=%d lds=%d H=%d W=%d", nrow, B, K, lds, H, W);
+  hipLaunchKernelGGL(seg_infer_kernel<true>, dim3(gs((long)H * W), B), dim3(256), 0, (hipStream_t)stream, rows, nrow, lds, K, H, W,
+                     cls_scale, pred, prob, gt, counts);
+  MX_LAUNCH_CHECK();
+  return MX_OK;
+}
+
+// rows of one image per workgroup of the rapid-evaluation kernels: about 512 workgroups (two per CU) for the batch
+static int rev_rows(int B, int H) {
+  int r = (int)(((long)B * H + 511) / 512);
+  return r < 1 ? 1 : r;
+}
+
+long mx_rapid_eval_lr_ws(int B, int K) { return (B > 0 && K > 0) ? (long)B * K * 2 * (long)sizeof(unsigned) : 0; }
+
+int mx_rapid_eval_lr(const float* sgc, const float* label_with_bg, const unsigned char* gt, const float* thresholds, int nt, int B,
+                     int h, int w, int lds, int K, int H, int W, long long* counts, void* ws, long ws_bytes, void* stream) {
+  MX_CHECK_ARG(sgc && label_with_bg && gt && thresholds && counts && ws, "rapid_eval_lr: NULL argument");
+  MX_CHECK_ARG(nt > 0 && nt <= REV_MAXT && K >= 2 && K <= REV_MAXK && K <= lds && lds % 4 == 0 && B > 0 && B <= 65535 && h > 0 &&
+                   w > 0 && H > 0 && W > 0 && (long)h * w * lds < 0x7fffffffL && (long)H * W < 0x7fffffffL,
+               "rapid_eval_lr: bad args nt=%d B=%d h=%d w=%d lds=%d K=%d H=%d W=%d", nt, B, h, w, lds, K, H, W);
+  MX_CHECK_ARG(ws_bytes >= mx_rapid_eval_lr_ws(B, K), "rapid_eval_lr: ws has %ld bytes, needs %ld", ws_bytes,
+               mx_rapid_eval_lr_ws(B, K));
+  hipStream_t st = (hipStream_t)stream;
+  const int rows = rev_rows(B, H);
+  const dim3 grid((H + rows - 1) / rows, B);
+  hipError_t e = hipMemsetAsync(ws, 0, (size_t)mx_rapid_eval_lr_ws(B, K), st);
+  if (e != hipSuccess) { mx_set_error("rapid_eval_lr: memset failed: %s", hipGetErrorString(e)); return (int)e; }
+  hipLaunchKernelGGL(rapid_extremes_kernel, grid, dim3(256), 0, st, sgc, h, w, lds, K, H, W, rows, (unsigned*)ws);
+  MX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(rapid_count_kernel, grid, dim3(256), 0, st, sgc, label_with_bg, gt, thresholds, nt, h, w, lds, K, H, W, rows,
+                     (const unsigned*)ws, counts);
   MX_LAUNCH_CHECK();
   return MX_OK;
 }

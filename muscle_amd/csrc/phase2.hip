@@ -42,8 +42,8 @@ __global__ __launch_bounds__(256) void maxnorm_fwd_kernel(const float* x, float*
     if (smn[w] < mn || (smn[w] == mn && simn[w] < imn)) { mn = smn[w]; imn = simn[w]; }
     if (smx[w] > mx || (smx[w] == mx && simx[w] < imx)) { mx = smx[w]; imx = simx[w]; }
   }
-  const float inv = 1.f / (mx - mn + 1e-6f);
-  for (long i = threadIdx.x; i < HW; i += 256) y[nk * HW + i] = fmaxf((fmaxf(xp[i], 0.f) - mn - 1e-6f) * inv, 0.f);
+  const float inv = maxnorm_inv(mn, mx);                       // common.h: shared with mx_rapid_eval_lr
+  for (long i = threadIdx.x; i < HW; i += 256) y[nk * HW + i] = maxnorm_apply(xp[i], mn, inv);
   if (threadIdx.x == 0) {
     stats[nk * 4 + 0] = mn; stats[nk * 4 + 1] = mx;
     stats[nk * 4 + 2] = __int_as_float(imn); stats[nk * 4 + 3] = __int_as_float(imx);

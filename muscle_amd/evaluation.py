@@ -11,6 +11,10 @@ PNGs): one integer confusion kernel per image over the uint8 prediction and grou
 
 `SegValidation` / `validate_seg` are the per-epoch validation of train_muscle.py:224-283 on top of `infer.infer_seg` and `SegEval`.
 
+Batched sweeps (`size_buckets`, `RapidEval.add_batch`, `SegValidation.add_batch`, `rapid_eval_sweep`, `validate_seg(batch=)`):
+the eval-mode forward is per-sample, so images of one size share a forward and one post-processing launch
+(mx_rapid_eval_lr / mx_seg_infer_batch); the tables are integer for integer the per-image ones.  batch=1 is the per-image path.
+
 `CamDictEval` is do_python_eval(input_type='npy') over the `{class: float32[H,W]}` dicts that infer_mcl writes, for a whole
 list of thresholds at once (one mx_camdict_confusion launch per image); `python -m muscle_amd.evaluation` is the
 reference's src/evaluation.py command line (:105-133) on top of it and of `SegEval`.
@@ -29,13 +33,72 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from ._lib import MuscleHipError, call, ptr, stream
+from ._lib import MuscleHipError, call, lib, ptr, stream
 from .phase2 import cam_maxnorm
 
 categories = ['background', 'aeroplane', 'bicycle', 'bird', 'boat', 'bottle', 'bus', 'car', 'cat', 'chair', 'cow',
               'diningtable', 'dog', 'horse', 'motorbike', 'person', 'pottedplant', 'sheep', 'sofa', 'train', 'tvmonitor']
 
 RAPID_THRESHOLDS = tuple(t / 100.0 for t in range(20, 52, 2))          # train_mcl.py:308-309
+
+# the largest batch of the batched sweeps: sample b of an eval-mode batch-B forward equals the batch-1 forward of that sample
+# bit for bit, which tests/test_gpu_eval_batch.py pins for B up to this value; nothing larger is accepted
+MAX_EVAL_BATCH = 8
+_DECODE_THREADS = 4        # host threads that decode the next batch's files; fixed, never sized by the machine
+
+
+def _check_batch(batch: int) -> int:
+    if not 1 <= int(batch) <= MAX_EVAL_BATCH:
+        raise ValueError(f"batch must be 1..{MAX_EVAL_BATCH} (the per-sample equality of the eval forward is pinned up to "
+                         f"{MAX_EVAL_BATCH}); got {batch}")
+    return int(batch)
+
+
+def size_buckets(names_and_sizes, batch: int) -> List[List[str]]:
+    """names_and_sizes: (name, (W, H)) pairs, the size as `PIL.Image.open(path).size` gives it.  Groups the names by size and
+    cuts every group into batches of at most `batch`; within a group the list order is kept, the groups come in the order
+    of their first image.  batch=1 is the list itself, one name per batch."""
+    if int(batch) < 1:
+        raise ValueError(f"batch must be >= 1 (got {batch})")
+    pairs = [(n, tuple(sz)) for n, sz in names_and_sizes]
+    if int(batch) == 1:
+        return [[n] for n, _ in pairs]
+    groups: Dict[tuple, List[str]] = {}
+    for n, sz in pairs:
+        groups.setdefault(sz, []).append(n)
+    return [g[i:i + batch] for g in groups.values() for i in range(0, len(g), batch)]
+
+
+def _image_sizes(names: Sequence[str], voc12_root: str):
+    """(name, (W, H)) from the JPEG headers (PIL.Image.open decodes nothing)."""
+    import os
+    import PIL.Image
+    out = []
+    for n in names:
+        with PIL.Image.open(os.path.join(voc12_root, 'JPEGImages', n + '.jpg')) as im:
+            out.append((n, im.size))
+    return out
+
+
+def _decode(voc12_root: str, name: str):
+    """Host only: the RGB image and the SegmentationClass map of one name."""
+    import os
+    import PIL.Image
+    img = PIL.Image.open(os.path.join(voc12_root, 'JPEGImages', name + '.jpg')).convert('RGB')
+    gt = np.ascontiguousarray(np.array(PIL.Image.open(os.path.join(voc12_root, 'SegmentationClass', name + '.png'))), dtype=np.uint8)
+    return img, gt
+
+
+def _prefetched(buckets: List[List[str]], voc12_root: str):
+    """Yields (names, [(img, gt), ...]) per bucket; the NEXT bucket's files are decoded on a small thread pool while the
+    caller works on the current one.  The pool only reads and decodes files."""
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max_workers=_DECODE_THREADS) as pool:
+        submit = lambda b: [pool.submit(_decode, voc12_root, n) for n in b]  # noqa: E731
+        nxt = submit(buckets[0]) if buckets else None
+        for i, b in enumerate(buckets):
+            cur, nxt = nxt, (submit(buckets[i + 1]) if i + 1 < len(buckets) else None)
+            yield b, [f.result() for f in cur]
 
 
 def miou_loglist(counts) -> Dict[str, float]:
@@ -82,6 +145,33 @@ class RapidEval:
         lwb = torch.cat([torch.ones(1, device=pred.device), label.view(-1).to(pred.device).float()])
         self.add_prediction(pred[0], lwb, gt)
 
+    def add_batch(self, model, imgs: torch.Tensor, labels: torch.Tensor, gts: torch.Tensor) -> None:
+        """B images of one size in one forward: imgs [B,3,H,W], labels [B,20], gts uint8 [B,H,W].  The forward is asked for
+        its low-resolution maps (cam='cam_lr') and mx_rapid_eval_lr does the upsample, cam_maxnorm, label multiply, fp16
+        rounding, argmax and counting of `add` without a full-resolution tensor: the same integers as B calls of `add`."""
+        if not imgs.is_cuda:
+            raise MuscleHipError("RapidEval runs on the HIP kernels only")
+        if imgs.dim() != 4:
+            raise ValueError(f"imgs must be [B,3,H,W] (got {tuple(imgs.shape)})")
+        B, _, H, W = imgs.shape
+        _check_batch(B)
+        K, nt = self.num_cls, len(self.thresholds)
+        if tuple(gts.shape) != (B, H, W) or gts.dtype != torch.uint8:
+            raise ValueError(f"gts must be uint8 [{B},{H},{W}] (got {gts.dtype} {tuple(gts.shape)})")
+        if tuple(labels.shape) != (B, K - 1):
+            raise ValueError(f"labels must be [{B},{K - 1}] (got {tuple(labels.shape)})")
+        if not model.training and getattr(model.backbone, "_eval_fold", None) is None and hasattr(model, "fold_eval_bn"):
+            model.fold_eval_bn()
+        dev = imgs.device
+        with torch.no_grad():
+            _, sgc_lr, _, _ = model(imgs.float(), cam="cam_lr")                 # NHWC [B,h,w,24]
+        _, h, w, lds = sgc_lr.shape
+        lwb = torch.cat([torch.ones(B, 1, device=dev), labels.to(dev).float()], dim=1).contiguous()
+        nbytes = int(lib().mx_rapid_eval_lr_ws(B, K))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        call("mx_rapid_eval_lr", ptr(sgc_lr.contiguous()), ptr(lwb), ptr(gts.to(dev).contiguous()), ptr(self.thr), nt, B, h, w, lds,
+             K, H, W, ptr(self.counts), ptr(ws), nbytes, stream())
+
     def loglist(self, ti: int) -> Dict[str, float]:
         """do_python_eval's return value for threshold index ti (src/evaluation.py:56-68)."""
         return miou_loglist(self.counts[ti].cpu().numpy())
@@ -91,6 +181,28 @@ class RapidEval:
         mious: List[float] = [self.loglist(i)['mIoU'] for i in range(len(self.thresholds))]
         max_miou = max(mious)
         return max_miou, self.thresholds[mious.index(max_miou)], mious
+
+
+def rapid_eval_sweep(model, names: Sequence[str], voc12_root: str, labels, device, batch: int = 1, num_cls: int = 21) -> RapidEval:
+    """train_mcl.py:286-306 over the images `names` of a VOC tree; labels: {name: [20]}.  Returns the filled RapidEval
+    (`.best()` is :308-312); leaves the model in eval mode.  batch=1: one image per forward (`RapidEval.add`), in list order.
+    batch>1: images of one size share a forward (`size_buckets`, `RapidEval.add_batch`) and the next batch's files are
+    decoded on host threads meanwhile; the table is the same, integer for integer."""
+    from .data import MSFStager
+    batch = _check_batch(batch)
+    model.eval()
+    ev, stager = RapidEval(device, num_cls=num_cls), MSFStager(device)
+    lab = lambda n: torch.from_numpy(np.asarray(labels[n], dtype=np.float32)).view(1, -1)  # noqa: E731
+    if batch == 1:
+        for name in names:
+            img, gt = _decode(voc12_root, name)
+            ev.add(model, stager(img, (1,))[0], lab(name), torch.from_numpy(gt).to(device))
+        return ev
+    for bnames, items in _prefetched(size_buckets(_image_sizes(names, voc12_root), batch), voc12_root):
+        imgs = torch.cat([stager(img, (1,))[0] for img, _ in items], dim=0)
+        gts = torch.from_numpy(np.stack([gt for _, gt in items])).to(device)
+        ev.add_batch(model, imgs, torch.cat([lab(n) for n in bnames], dim=0), gts)
+    return ev
 
 
 class SegEval:
@@ -150,21 +262,51 @@ class SegValidation:
         self.table.add(pred, torch.from_numpy(np.ascontiguousarray(gt, dtype=np.uint8)).to(self.dev))
         return pred
 
+    def add_batch(self, model, pil_imgs, gts, names=None) -> torch.Tensor:
+        """`add` for B images of one size in one forward and one mx_seg_infer_batch launch, which also counts (without the
+        CRF; with it mx_crf_inference and the counting run per image, as in `add`).  pil_imgs: B RGB images; gts: B uint8
+        [H,W] maps; names: the B names, needed with cls_dir.  Returns the uint8 predictions [B,H,W] on the device."""
+        import os
+        from .infer import infer_seg_batch
+        B = _check_batch(len(pil_imgs))
+        g = np.stack([np.ascontiguousarray(np.asarray(x), dtype=np.uint8) for x in gts])
+        if g.ndim != 3 or g.shape[0] != B:
+            raise ValueError(f"gts must be {B} maps of one size [H,W] (got {g.shape})")
+        _, H, W = g.shape
+        cls = None
+        if self.cls_dir:
+            cls = np.stack([np.asarray(np.load(os.path.join(self.cls_dir, n + '.npy'), allow_pickle=True).squeeze(),
+                                       dtype=np.float32).reshape(-1) for n in names])
+        crf_imgs = [np.asarray(im, dtype=np.uint8) for im in pil_imgs] if self.crf else None
+        imgs = torch.cat([self.stager(im, (1,))[0] for im in pil_imgs], dim=0)
+        gd = torch.from_numpy(g).to(self.dev)
+        pred, _ = infer_seg_batch(model, imgs, H, W, cls_labels=cls, crf_imgs=crf_imgs, crf_t=1, crf_trunc=self.crf_trunc,
+                                  gts=None if self.crf else gd, counts=None if self.crf else self.table.counts)
+        if self.crf:
+            for b in range(B):
+                self.table.add(pred[b], gd[b])
+        return pred
+
     def miou(self) -> float:
         return float(miou_loglist(self.table.counts.cpu().numpy())['mIoU']) / 100.0
 
 
-def validate_seg(model, names: Sequence[str], voc12_root: str, device, num_cls: int = 21, cls_dir=None, crf: bool = False) -> float:
+def validate_seg(model, names: Sequence[str], voc12_root: str, device, num_cls: int = 21, cls_dir=None, crf: bool = False,
+                 batch: int = 1) -> float:
     """train_muscle.py:224-283 over the images `names` of a VOC tree; leaves the model in eval mode (as the script does
-    until the next epoch's model.train())."""
-    import os
-    import PIL.Image
+    until the next epoch's model.train()).  batch=1: one image per forward (`SegValidation.add`), in list order.  batch>1:
+    images of one size share a forward (`size_buckets`, `SegValidation.add_batch`) and the next batch's files are decoded on
+    host threads meanwhile; the same table."""
+    batch = _check_batch(batch)
     model.eval()
     val = SegValidation(device, num_cls, cls_dir=cls_dir, crf=crf)
-    for name in names:
-        img = PIL.Image.open(os.path.join(voc12_root, 'JPEGImages', name + '.jpg')).convert('RGB')
-        gt = np.array(PIL.Image.open(os.path.join(voc12_root, 'SegmentationClass', name + '.png')))
-        val.add(model, img, gt, name)
+    if batch == 1:
+        for name in names:
+            img, gt = _decode(voc12_root, name)
+            val.add(model, img, gt, name)
+        return val.miou()
+    for bnames, items in _prefetched(size_buckets(_image_sizes(names, voc12_root), batch), voc12_root):
+        val.add_batch(model, [img for img, _ in items], [gt for _, gt in items], bnames)
     return val.miou()
 
 

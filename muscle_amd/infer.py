@@ -197,6 +197,56 @@ def infer_seg(model, img_list: List[torch.Tensor], H: int, W: int, cls_label=Non
     return pred, prob
 
 
+def infer_seg_batch(model, imgs: torch.Tensor, H: int, W: int, cls_labels=None, crf_imgs=None, return_prob: bool = False,
+                    crf_t: int = 4, crf_trunc: float = 4.0, gts: Optional[torch.Tensor] = None,
+                    counts: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """`infer_seg` with a single pass per image (the `img_list[:1]` of the per-epoch validation) for B images of one input
+    size and one output size: imgs [B,3,Hs,Ws] on the device; one cam='seg_lr' forward and one mx_seg_infer_batch launch.
+    cls_labels: optional [B,K] class scores; crf_imgs: optional B uint8 [H,W,3] images, the dense CRF then runs per image
+    (mx_crf_inference looped over the batch).  gts uint8 [B,H,W] with counts int64 [K,3] (both or neither, not with the
+    CRF): the (TP, P, T) table of `SegEval.add` is accumulated by the same launch.  Returns (pred uint8 [B,H,W], the fp32
+    map [B,K,H,W] if return_prob else None); per image the bits of `infer_seg(model, [imgs[b:b+1]], H, W, ...)`."""
+    if imgs.dim() != 4 or imgs.shape[0] < 1:
+        raise ValueError(f"imgs must be [B,3,Hs,Ws] (got {tuple(imgs.shape)})")
+    if (gts is None) != (counts is None):
+        raise ValueError("gts and counts go together")
+    if crf_imgs is not None and gts is not None:
+        raise ValueError("with the CRF the prediction changes after the launch: count with SegEval.add per image")
+    B, _, Hs, Ws = imgs.shape
+    if crf_imgs is not None and len(crf_imgs) != B:
+        raise ValueError(f"crf_imgs has {len(crf_imgs)} images, the batch {B}")
+    model.eval()
+    if getattr(model.backbone, "_eval_fold", None) is None and hasattr(model, "fold_eval_bn"):
+        model.fold_eval_bn()
+    dev = imgs.device
+    K = model.classes
+    with torch.no_grad():
+        seg_lr = model(imgs.float(), cam="seg_lr")                                   # NHWC [B,h,w,24]
+        _, h, w, lds = seg_lr.shape
+        tab = torch.tensor([[seg_lr[b].data_ptr(), h, w, Hs, Ws, 0, b, 0] for b in range(B)], dtype=torch.int64).to(dev)
+        cls = None
+        if cls_labels is not None:
+            cls = torch.as_tensor(np.asarray(cls_labels, dtype=np.float32).reshape(B, -1)).to(dev).contiguous()
+            if cls.shape[1] != K:
+                raise ValueError(f"cls_labels has {cls.shape[1]} entries per image, the model {K} classes")
+        if gts is not None and (gts.dtype != torch.uint8 or tuple(gts.shape) != (B, H, W) or tuple(counts.shape) != (K, 3)
+                                or counts.dtype != torch.int64):
+            raise ValueError(f"gts must be uint8 [{B},{H},{W}] and counts int64 [{K},3]")
+        pred = torch.empty(B, H, W, dtype=torch.uint8, device=dev)
+        prob = torch.empty(B, K, H, W, dtype=torch.float32, device=dev) if return_prob or crf_imgs is not None else None
+        call("mx_seg_infer_batch", ptr(tab), B, B, lds, K, H, W, ptr(cls), ptr(pred), ptr(prob),
+             ptr(gts.contiguous()) if gts is not None else None, ptr(counts), stream())
+        if crf_imgs is not None:
+            from .crf import crf_run
+            qs = []
+            for b in range(B):
+                q, pb = crf_run(crf_imgs[b], prob[b], crf_t, 1.5, K, 0.5, crf_trunc, want_q=return_prob, want_pred=True)
+                pred[b].copy_(pb)
+                qs.append(q)
+            prob = torch.stack(qs) if return_prob else None
+    return pred, prob
+
+
 def save_seg_png(path: str, pred) -> None:
     """infer_seg.py:129-131: the class-index map as an 8-bit single-channel PNG, the file src/evaluation.py:24-25 reads
     back with np.array(Image.open(path))."""

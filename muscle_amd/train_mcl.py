@@ -11,6 +11,7 @@ Differences a caller can see:
     `--weights <session>/_7.pth --start_epoch 8` enters the PixPro / EMD epoch gates where it left off.  The reference
     saves no optimiser state: the learning rate and Adam's moments start afresh;
   * the rapid evaluation counts on the device (`RapidEval`): no training_eval/*.npy files are written;
+  * --eval_batch N (new, default 1): images of one size share a forward of the rapid evaluation; the same table;
   * --tblog_dir is created and otherwise unused: the JET overlays of :256-277 are not built (no tensorboardX, no cv2).
 """
 from __future__ import annotations
@@ -46,26 +47,21 @@ def parse_args(argv: Optional[List[str]] = None):
                     help="first epoch of range(start_epoch, max_epoches): continue a run from --weights <session>/_<N-1>.pth "
                          "--start_epoch N with the epoch gates (IMC 4, PixPro 8, EMD 12) where it left off; no optimiser "
                          "state is saved, so the learning rate and Adam's moments restart")
+    ap.add_argument("--eval_batch", default=1, type=int,
+                    help="images per forward of the rapid evaluation (1..8): 1 = one image per forward; above 1 images of one "
+                         "size share a forward and the files of the next batch are decoded on host threads.  Same table")
     args = ap.parse_args(argv)
+    if not 1 <= args.eval_batch <= 8:
+        ap.error(f"--eval_batch {args.eval_batch} outside 1..8")
     if not 0 <= args.start_epoch <= args.max_epoches:
         ap.error(f"--start_epoch {args.start_epoch} outside 0..--max_epoches {args.max_epoches}")
     return args
 
 
-def rapid_eval(model, names, labels, voc12_root: str, dev, num_cls: int = 21):
+def rapid_eval(model, names, labels, voc12_root: str, dev, num_cls: int = 21, batch: int = 1):
     """train_mcl.py:286-315 over the images `names`: (max_miou, max_t).  Leaves the model in eval mode."""
-    import PIL.Image
-    import torch
-    from muscle_amd.data import MSFStager
-    from muscle_amd.evaluation import RapidEval
-    model.eval()
-    ev, stager = RapidEval(dev, num_cls=num_cls), MSFStager(dev)
-    for name in names:
-        img = PIL.Image.open(os.path.join(voc12_root, "JPEGImages", name + ".jpg")).convert("RGB")
-        gt = np.array(PIL.Image.open(os.path.join(voc12_root, "SegmentationClass", name + ".png")))
-        label = torch.from_numpy(np.asarray(labels[name], dtype=np.float32)).view(1, -1)
-        ev.add(model, stager(img, (1,))[0], label, torch.from_numpy(np.ascontiguousarray(gt, dtype=np.uint8)).to(dev))
-    max_miou, max_t, _ = ev.best()
+    from muscle_amd.evaluation import rapid_eval_sweep
+    max_miou, max_t, _ = rapid_eval_sweep(model, names, voc12_root, labels, dev, batch=batch, num_cls=num_cls).best()
     return max_miou, max_t
 
 
@@ -121,7 +117,8 @@ def main(argv: Optional[List[str]] = None) -> int:
             print("")
         torch.save(model.state_dict(), os.path.join(args.session_name, "_{}".format(str(ep)) + ".pth"))   # :283
         stamp = time.time()                                                                 # :286-318
-        max_miou, max_t = rapid_eval(model, eval_names, train_dataset.labels, args.voc12_root, dev, args.num_classes)
+        max_miou, max_t = rapid_eval(model, eval_names, train_dataset.labels, args.voc12_root, dev, args.num_classes,
+                                     batch=args.eval_batch)
         print(f"\n Epoch:{ep} max miou:{max_miou} max t:{max_t}", f"Time elapse:{time.time() - stamp}s", flush=True)
         scheduler.step(max_miou)
         stage_start = time.time()

@@ -7,6 +7,7 @@ Differences a caller can see:
   * --val_list (new, default data/val.txt: the list the reference hard-codes) names the images of the per-epoch validation;
   * --crf 1 runs the dense CRF of the validation on the GPU with t=1 (the exact windowed CRF of muscle_amd/crf.py, not
     pydensecrf's lattice filter);
+  * --val_batch N (new, default 1): images of one size share a forward of the validation; the same table;
   * --tblog_dir is created and otherwise unused (the reference opens a tensorboardX writer and never writes to it).
 """
 from __future__ import annotations
@@ -46,7 +47,13 @@ def parse_args(argv: Optional[List[str]] = None):
     ap.add_argument("--seed", default=221, type=int)
     ap.add_argument("--pretrained", default="b7", type=str)
     ap.add_argument("--bifpn", default=3, type=int)
-    return ap.parse_args(argv)
+    ap.add_argument("--val_batch", default=1, type=int,
+                    help="images per forward of the validation (1..8): 1 = one image per forward; above 1 images of one size "
+                         "share a forward and the files of the next batch are decoded on host threads.  Same table")
+    args = ap.parse_args(argv)
+    if not 1 <= args.val_batch <= 8:
+        ap.error(f"--val_batch {args.val_batch} outside 1..8")
+    return args
 
 
 def main(argv: Optional[List[str]] = None) -> int:
@@ -99,7 +106,8 @@ def main(argv: Optional[List[str]] = None) -> int:
                       "Fin:%s" % (time.ctime(est_finish)), flush=True)
         torch.save(model.state_dict(), os.path.join(args.session_name, "_{}".format(str(ep)) + ".pth"))
         stamp = time.time()                                                                 # :224-283
-        miou = validate_seg(model, val_names, args.voc12_root, dev, args.num_classes, cls_dir=args.cls_dir, crf=bool(args.crf))
+        miou = validate_seg(model, val_names, args.voc12_root, dev, args.num_classes, cls_dir=args.cls_dir, crf=bool(args.crf),
+                            batch=args.val_batch)
         print(f"\n Epoch:{ep} val miou:{miou}", f"Time elapse:{time.time() - stamp}s", flush=True)
         scheduler.step(miou)
         stage_start = time.time()
