@@ -59,10 +59,12 @@ int mx_pw_fwd(const float* A, int a_mode, const float* a_scale, const float* a_s
 int mx_set_gemm_mode(int mode);
 int mx_get_gemm_mode(void);
 /* Which kernel takes the split-arithmetic weight gradients with plain operands (backward of model.py:77,86), and an optional fixed
- * number of row groups for them (process-wide; for tests and measurement).  kernel: 0 = wgrad_split_kernel (rounds 3-4), 1 = the
- * single-stream pipelined kernel, 2 = (default; initial value from MX_WGRAD_PIPE) the wave-specialised persistent kernel of round 5,
- * -1 = leave as is.  groups: > 0 fixes the row groups of every such launch (same groups => the three kernels give the same bits:
- * same tiles, same MFMA order per group, same fixed-order sum of the groups), 0 = back to the planner's choice, -1 = leave as is. */
+ * number of row groups for them (process-wide; for tests and measurement).  kernel: 0 = wgrad_split_kernel (rounds 3-4), 2 = (default)
+ * the wave-specialised persistent kernel of round 5, -1 = leave as is; 1 (the single-stream pipelined kernel, removed) and every
+ * other value are MX_EARG and change nothing.  groups: > 0 fixes the row groups of every such launch, 0 = back to the planner's
+ * choice, -1 = leave as is.  Same groups of at most 1568 rows each => the two kernels give the same bits: same tiles, same MFMA order
+ * per group, same fixed-order sum of the groups.  (A longer group is one accumulation chain in kernel 0, while kernel 2 flushes its
+ * accumulators every 1568 rows: the sums then differ in the last bits.) */
 int mx_set_wgrad_kernel(int kernel, int groups);
 int mx_get_wgrad_kernel(void);
 /* 1 if, in the current mode, this GEMM runs in split arithmetic on the bf16 pipe (kind 0: mx_pw_fwd / data gradient
@@ -147,7 +149,7 @@ int mx_pw_wgrad_small(const float* G, const float* X, int x_mode, const float* x
 
 /* The same weight gradient for LARGE outputs (Co*Ci >= 16384): dW cut into 128/64-wide tiles, the rows into groups, partial
  * tiles per group added in a fixed order - deterministic, no atomics; workgroup ids are XCD-aware so that a row slab crosses
- * the fabric once.  mx_pw_wgrad_tile_ws: bytes of scratch needed, 0 = shape not taken.
+ * the fabric once.  mx_pw_wgrad_tile_ws: bytes of scratch needed for contiguous operands (ldg = Co, ldx = Ci), 0 = shape not taken.
  * Kernels behind it (same results contract, chosen per shape and arithmetic): split arithmetic, plain operands - one persistent
  * workgroup per CU of 4 MFMA waves + 4 loader waves (wgrad_split_ws_kernel; mx_set_wgrad_kernel selects the earlier forms);
  * exact-fp32 arithmetic (mx_set_gemm_mode(0)), plain operands, 128 x 128 tiles - the same workgroup with loader waves that only move

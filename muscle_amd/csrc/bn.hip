@@ -44,11 +44,11 @@ static ColGeom col_geom(long rows, int C, int rps, long rows_limit /*rows that o
   }
   g.rpp = 256 / g.tcols;
   int colchunks = cdiv(g.c4, g.tcols);
-  // workgroups per reduction launch (tuning override MX_COLREDUCE_BLOCKS), swept twice on one box, ms per step:
+  // workgroups per reduction launch, swept twice on one box, ms per step:
   // 256: 153.3  512: 150.1/150.5  1024: 147.7/147.9  2048: 149.4/150.0  4096: 150.3/151.7
-  static const long block_target = getenv("MX_COLREDUCE_BLOCKS") ? atol(getenv("MX_COLREDUCE_BLOCKS")) : 1024;
+  constexpr long block_target = 1024;
   // (the five-plane SE / BN1 pass carries 10 loads per row and thread and a five-fold final sum: half as many workgroups suit it
-  //  better - tools/microbench.py pool, MX_COLREDUCE_BLOCKS 1024 / 512 / 256)
+  //  better - tools/microbench.py pool at 1024 / 512 / 256)
   long target_blocks = (planes == 5 ? block_target / 2 : block_target) / ((long)colchunks * groups);
   if (target_blocks < 1) target_blocks = 1;
   long rpb = (rows_limit + target_blocks - 1) / target_blocks;
@@ -486,7 +486,7 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const double* acc,
 // Up to FUSED_FINALIZE_MAX_ROWS partial rows: reduction and finalisation in ONE launch (one workgroup = 32 channels x 8 row
 // lanes walks all rows).  The memset + reduce + finalise triple costs three ~5 us launches per BatchNorm per direction:
 // 324 BatchNorm finalisations per B7 step.
-static const int FUSED_FINALIZE_MAX_ROWS = getenv("MX_BN_FUSED_ROWS") ? atoi(getenv("MX_BN_FUSED_ROWS")) : 1024;
+constexpr int FUSED_FINALIZE_MAX_ROWS = 1024;
 template <bool BWD>
 __global__ __launch_bounds__(256) void bn_reduce_finalize_kernel(const float* part, int P, int C, BnFwdFin f, BnBwdFin b) {
   __shared__ double sh[2][8][32];
@@ -635,9 +635,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(GEff e, const float* 
 }
 
 static int grid_for(long total4) {
-  // grid cap of the grid-stride streaming kernels (tuning override MX_STREAM_BLOCKS); swept 2048 / 4096 / 8192 twice:
+  // grid cap of the grid-stride streaming kernels; swept 2048 / 4096 / 8192 twice:
   // 148.6, 149.4 / 147.9, 148.1 / 148.9, 149.4 ms per step
-  static const long cap = getenv("MX_STREAM_BLOCKS") ? atol(getenv("MX_STREAM_BLOCKS")) : 4096;
+  constexpr long cap = 4096;
   long b = (total4 + 255) / 256;
   return (int)(b < cap ? (b < 1 ? 1 : b) : cap);
 }

@@ -2,6 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <mutex>
+#include <set>
+#include <utility>
 
 #define MX_OK 0
 #define MX_EARG (-1)
@@ -25,6 +28,26 @@ void mx_set_error(const char* fmt, ...);
       return (int)e__;                                        \
     }                                                         \
   } while (0)
+
+// Opt a kernel into `bytes` of dynamic LDS (beyond the 64 KB every kernel may ask for).  The attribute belongs to the (function, device)
+// pair, so it is set once per pair; a failure is the entry point's error return (MX_OK otherwise).
+inline int mx_dyn_lds_optin(const void* kernel, int bytes) {
+  static std::mutex mu;
+  static std::set<std::pair<const void*, int>> done;
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e == hipSuccess) {
+    std::lock_guard<std::mutex> lock(mu);
+    if (done.count({kernel, dev})) return MX_OK;
+    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess) {
+      done.insert({kernel, dev});
+      return MX_OK;
+    }
+  }
+  mx_set_error("dynamic LDS opt-in (%d bytes) failed: %s", bytes, hipGetErrorString(e));
+  return (int)e;
+}
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 

@@ -865,11 +865,10 @@ static void launch_dw_parts_reduce(const float* part, int P, int n, float* dW, h
   hipLaunchKernelGGL(dw_parts_reduce_kernel, dim3(cdiv(n, 16)), dim3(256), 0, st, part, P, n, dW);
 }
 
-// tile shape of the fused backward: 1 = 14 x 28 (PX 7), 0 = 8 x 16 (PX 8), 3 = 8 x 28 (3x3 only), 2 = 7 x 28 (a knob: MX_DW_FUSED_TILE=2).  The large tile wherever it covers the image with
-// fewer staged elements per valid output (its halo factor is lower, its quantisation coarser); MX_DW_FUSED_TILE forces one.
+// tile shape of the fused backward: 1 = 14 x 28 (PX 7), 0 = 8 x 16 (PX 8), 3 = 8 x 28 (3x3 only).  The large tile wherever it covers the image with
+// fewer staged elements per valid output (its halo factor is lower, its quantisation coarser).  (7 x 28 tiles were measured and dropped:
+// profiles/r04_knob_sweep.txt.)
 static int dw_fused_shape(int H, int Wd, int K) {
-  static const int forced = getenv("MX_DW_FUSED_TILE") ? atoi(getenv("MX_DW_FUSED_TILE")) : -1;
-  if (forced == 0 || forced == 1 || forced == 2 || (forced == 3 && K == 3)) return forced;
   // measured on MI355X (tools/microbench.py dwfused, profiles/r03_dwfused_tiles.txt): 5x5 gains 13-19 % on every B7 layer
   // (2.3-2.6 -> 2.8-2.9 TB/s); 3x3, which ran 3 workgroups per CU on the small tile, loses 9-15 % at 112 / 224 pixels and is
   // level at 28: the large tile is taken for 5x5 only
@@ -882,31 +881,25 @@ static int dw_fused_shape(int H, int Wd, int K) {
   return large < 0.9 * small ? 1 : 0;
 }
 
-// groups = partial rows written; gpp > 0: XCD-aware launch (a plane = one sample x one channel chunk is cut into gpp groups that do
-// not straddle samples, all on one XCD); gpp = 0: plain 2-D grid, a group is tpb consecutive tiles of the (sample, tile) sequence
-static void dw_fused_geom(int N, int H, int Wd, int C, int K, int* tiles_x, int* tiles_y, int* tpb, int* groups, int* gpp) {
+// groups = partial rows written: a plain 2-D grid, a group is tpb consecutive tiles of the (sample, tile) sequence.  (XCD-aware ids for
+// this grid were built on PMC evidence of 1.4-1.6x fabric-side over-read and measured neutral, profiles/r03_dw_xcd.txt: the Infinity
+// Cache serves the halo.  The host never sets DwFusedArgs::xcd / gpp.)
+static void dw_fused_geom(int N, int H, int Wd, int C, int K, int* tiles_x, int* tiles_y, int* tpb, int* groups) {
   const int shape = dw_fused_shape(H, Wd, K);
-  *tiles_x = cdiv(Wd, shape ? 28 : 16); *tiles_y = cdiv(H, shape == 2 ? 7 : shape == 3 ? 8 : shape ? 14 : 8);
+  *tiles_x = cdiv(Wd, shape ? 28 : 16); *tiles_y = cdiv(H, shape == 3 ? 8 : shape ? 14 : 8);
   const int ntile = (*tiles_x) * (*tiles_y);
   long ntiles = (long)N * ntile;
   int chunks = cdiv(C, CB);
-  // workgroups per launch ~ this target (tuning override MX_DW_GROUPS).  The 5x5 kernel (2 workgroups per CU, heavy
+  // workgroups per launch ~ this target.  The 5x5 kernel (2 workgroups per CU, heavy
   // per-workgroup prologue / partial-row epilogue) wants few long-lived workgroups: 11.0 -> 9.8 ms per step at 1024
   // instead of 4096; the 3x3 kernel (3 per CU) wants the opposite: 6.8 ms at 4096, 8.0 ms at 1024.
-  static const long override_target = getenv("MX_DW_GROUPS") ? atol(getenv("MX_DW_GROUPS")) : 0;
   // (round 4, rewritten kernel: the 14 x 28 / 5x5 form is level or 2-5 % faster at 512 - one workgroup per slot of its 2 per CU)
-  const long group_target = override_target > 0 ? override_target : (shape == 3 ? 4096 : shape == 2 ? 768 : shape ? 512 : K == 5 ? 1024 : 4096);
+  const long group_target = shape == 3 ? 4096 : shape ? 512 : K == 5 ? 1024 : 4096;
   long g = group_target / chunks;
   if (g < 1) g = 1;
   if (g > ntiles) g = ntiles;
   *tpb = (int)((ntiles + g - 1) / g);
   *groups = cdiv(ntiles, *tpb);
-  *gpp = 0;
-  static const int xcd_on = getenv("MX_DW_XCD") ? atoi(getenv("MX_DW_XCD")) : 0;      // XCD-aware ids: built on PMC evidence of 1.4-1.6x fabric-side over-read, measured neutral (profiles/r03_dw_xcd.txt): the Infinity Cache serves the halo
-  if (xcd_on && *tpb < ntile && (long)chunks * N >= 64) {
-    *gpp = cdiv(ntile, *tpb);
-    *groups = N * (*gpp);
-  }
 }
 
 // ---------------------------------------------------------------------------
@@ -940,20 +933,17 @@ static int dw_check(const DwArgs& a, int K, int S, const char* who) {
 
 extern "C" {
 
-// tile groups of the forward: ~MX_DWF_GROUPS workgroups per launch (default 4096), each walking tpb consecutive tiles
-// 1: the stride-1 forward takes its 8 x 28 tiles (images a multiple of 28 pixels wide: 224 / 112 / 56 / 28 of B7 at 448; MX_DWF_WIDE=0: never)
-static int dw_fwd_wide(int Wo, int S) {
-  static const int on = getenv("MX_DWF_WIDE") ? atoi(getenv("MX_DWF_WIDE")) : 1;
-  return (on && S == 1 && Wo % 28 == 0) ? 1 : 0;
-}
+// 1: the stride-1 forward takes its 8 x 28 tiles (images a multiple of 28 pixels wide: 224 / 112 / 56 / 28 of B7 at 448)
+static int dw_fwd_wide(int Wo, int S) { return (S == 1 && Wo % 28 == 0) ? 1 : 0; }
+
 
 static void dw_fwd_geom(int N, int Ho, int Wo, int C, int S, bool pooled, int* tiles_x, int* tiles_y, int* tpb, int* groups, int* gpp) {
   *tiles_x = cdiv(Wo, dw_fwd_wide(Wo, S) ? 28 : S == 1 ? 16 : 8); *tiles_y = cdiv(Ho, 8);
   const int ntile = (*tiles_x) * (*tiles_y);
   const long ntiles = (long)N * ntile;
   const int chunks = cdiv(C, CB);
-  static const long target = getenv("MX_DWF_GROUPS") ? atol(getenv("MX_DWF_GROUPS")) : 4096;
-  long g = target / chunks;
+  constexpr long TARGET = 4096;                            // tile groups of the forward: ~4096 workgroups per launch, each walking tpb consecutive tiles
+  long g = TARGET / chunks;
   if (g < 1) g = 1;
   if (g > ntiles) g = ntiles;
   if (pooled) {
@@ -1073,8 +1063,8 @@ int mx_dwconv_bwd_weight(const float* X, const float* scale, const float* shift,
 // number of partial rows mx_dwconv_bwd_fused writes (BN0 sums [rows][2][C] and dW scratch [rows][C*K*K])
 int mx_dwconv_bwd_fused_parts(int N, int H, int Wd, int C, int K) {
   if (N <= 0 || H <= 0 || Wd <= 0 || C <= 0 || (K != 3 && K != 5)) return MX_EARG;
-  int tx, ty, tpb, groups, gpp;
-  dw_fused_geom(N, H, Wd, C, K, &tx, &ty, &tpb, &groups, &gpp);
+  int tx, ty, tpb, groups;
+  dw_fused_geom(N, H, Wd, C, K, &tx, &ty, &tpb, &groups);
   return groups;
 }
 
@@ -1126,26 +1116,14 @@ static int dw_bwd_fused_impl(const float* dA, const float* D, const float* gate,
   a.x = X; a.a0 = a0; a.b0 = b0; a.w = W; a.res = residual; a.gx = gX; a.dwpart = dw_scratch; a.part = a0 ? part : nullptr;
   a.N = N; a.H = H; a.W = Wd; a.C = C; a.pad = pad_lo;
   int groups;
-  dw_fused_geom(N, H, Wd, C, K, &a.tiles_x, &a.tiles_y, &a.tiles_per_block, &groups, &a.gpp);
+  dw_fused_geom(N, H, Wd, C, K, &a.tiles_x, &a.tiles_y, &a.tiles_per_block, &groups);
   dim3 grid(groups, cdiv(C, CB), 1);
   a.chunks = grid.y;
-  if (a.gpp > 0) {
-    a.xcd = 1;
-    grid = dim3((unsigned)(cdiv((long)a.chunks * N, 8) * 8 * a.gpp), 1, 1);
-  }
-  if (fin_counters) {
-    MX_CHECK_ARG(!a.xcd, "dwconv_bwd_fused_bn0: not with the XCD-grouped grid (MX_DW_XCD)");
-    a.fin_counters = fin_counters; a.fin = *fin;
-  }
+  if (fin_counters) { a.fin_counters = fin_counters; a.fin = *fin; }
   const int shape = dw_fused_shape(H, Wd, K);
   if (shape == 3) {
     hipLaunchKernelGGL((dw_bwd_fused_kernel<3, 8, 28, 7>), grid, dim3(256), 0, (hipStream_t)stream, a);
-  } else if (shape == 2) {
-    if (K == 3) hipLaunchKernelGGL((dw_bwd_fused_kernel<3, 7, 28, 7>), grid, dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((dw_bwd_fused_kernel<5, 7, 28, 7>), grid, dim3(256), 0, (hipStream_t)stream, a);
-  } else if (shape) {
-    static bool big_lds = false;                         // 14 x 28 tiles: 72 KB (5x5) / 60 KB (3x3) of static LDS
-    (void)big_lds;
+  } else if (shape) {                                    // 14 x 28 tiles: 72 KB (5x5) / 60 KB (3x3) of static LDS
     if (K == 3) hipLaunchKernelGGL((dw_bwd_fused_kernel<3, 14, 28, 7>), grid, dim3(256), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL((dw_bwd_fused_kernel<5, 14, 28, 7>), grid, dim3(256), 0, (hipStream_t)stream, a);
   } else {

@@ -308,31 +308,26 @@ template <int LAYOUT, int WM, int WN, int TM, int TN, int BK = 16>
 static void launch(const GemmArgs& g, int batch_or_splits, hipStream_t st) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   const int mt = cdiv(g.M, BM), nt = cdiv(g.N, BN);
-  static const int xcd_mode = getenv("MX_GEMM_XCD") ? atoi(getenv("MX_GEMM_XCD")) : 1;
-  // experiment knob: unused dynamic LDS for the weight-gradient kernels, which caps their workgroups per CU and so leaves
-  // wave slots to the HBM-bound kernels of the main stream while they run on the side stream
-  static const int tn_pad = getenv("MX_WGRAD_LDS_PAD") ? atoi(getenv("MX_WGRAD_LDS_PAD")) : 0;
-  const int dyn = LAYOUT == L_TN ? tn_pad : 0;
-  if (LAYOUT != L_TN && xcd_mode && nt >= 2 && nt <= 16 && mt >= 64) {     // 17..32 N tiles measured: 1-5 % slower
+  if (LAYOUT != L_TN && nt >= 2 && nt <= 16 && mt >= 64) {     // XCD-aware ids; 17..32 N tiles measured: 1-5 % slower
     GemmArgs a = g;
     a.xcd_nt = nt; a.mt = mt;
     dim3 grid(8 * cdiv(mt, 8) * nt, 1, batch_or_splits);
-    hipLaunchKernelGGL((gemm_kernel<LAYOUT, WM, WN, TM, TN, BK>), grid, dim3(256), dyn, st, a);
+    hipLaunchKernelGGL((gemm_kernel<LAYOUT, WM, WN, TM, TN, BK>), grid, dim3(256), 0, st, a);
     return;
   }
   // weight gradient: measured win only for the stage-2 layers (401 408 rows, 2-6 output tiles: 277 -> 236, 331 -> 255 us);
   // 5-13 % slower on the 25 088-row layers and 3 % slower at 1.6 M rows, where it stays off
-  if (LAYOUT == L_TN && xcd_mode && batch_or_splits >= 8 && mt * nt >= 2 && mt * nt <= 8 && g.K >= 200000 && g.K < 1000000) {
+  if (LAYOUT == L_TN && batch_or_splits >= 8 && mt * nt >= 2 && mt * nt <= 8 && g.K >= 200000 && g.K < 1000000) {
     GemmArgs a = g;
     a.xcd_nt = nt; a.mt = mt; a.zt = batch_or_splits;
     dim3 grid(8 * cdiv(batch_or_splits, 8) * mt * nt, 1, 1);
-    hipLaunchKernelGGL((gemm_kernel<LAYOUT, WM, WN, TM, TN, BK>), grid, dim3(256), dyn, st, a);
+    hipLaunchKernelGGL((gemm_kernel<LAYOUT, WM, WN, TM, TN, BK>), grid, dim3(256), 0, st, a);
     return;
   }
   GemmArgs a = g;
   a.xcd_nt = 0; a.mt = mt; a.zt = batch_or_splits;
   dim3 grid(mt, nt, batch_or_splits);
-  hipLaunchKernelGGL((gemm_kernel<LAYOUT, WM, WN, TM, TN, BK>), grid, dim3(256), dyn, st, a);
+  hipLaunchKernelGGL((gemm_kernel<LAYOUT, WM, WN, TM, TN, BK>), grid, dim3(256), 0, st, a);
 }
 
 // Tile configurations (block tile BM x BN; 4 waves).  EfficientNet's channel counts (48, 80, 160, 224, 288, 480,
@@ -1222,8 +1217,9 @@ static void launch_nt_split_t(const GemmArgs& g, int batch, hipStream_t st) {
 }
 
 // 128 x 128 unless the narrower tile pads fewer columns or balances the 768 resident workgroups (3 per CU) better
+static int g_split_nj = getenv("MX_GEMM_SPLIT_NJ") ? atoi(getenv("MX_GEMM_SPLIT_NJ")) : 0;     // tile override of both split generations (tools/gemm_nj.py, gemm_lab): 1 force 128 x 64, 2 force 128 x 128, 3: 64 / 128 only, >= 16: that width (second generation)
 static void launch_nt_split(const GemmArgs& g, int batch, hipStream_t st) {
-  static const int forced = getenv("MX_GEMM_SPLIT_NJ") ? atoi(getenv("MX_GEMM_SPLIT_NJ")) : 0;
+  const int forced = g_split_nj;
   auto score = [&](int bn, double eff) {
     const long nt = cdiv(g.N, bn), tiles = (long)cdiv(g.M, 128) * nt * batch;
     const double pad = (double)g.N / (double)(nt * bn);
@@ -1236,14 +1232,13 @@ static void launch_nt_split(const GemmArgs& g, int batch, hipStream_t st) {
   // filled last round is cheaper than a full one because its workgroups share their CU with fewer neighbours - and the
   // 64-wide tile does 0.87 of the 128-wide tile's work per unit time.  (K = 3840 -> N = 640 took 876 us with the 64-wide tile
   // the first rule picked and 788 us with the 128-wide one.)
-  static const int fitted = getenv("MX_GEMM_SPLIT_FITTED") ? atoi(getenv("MX_GEMM_SPLIT_FITTED")) : 1;   // 0: first rule only (A/B)
   auto cost = [&](int bn, double eff) {
     const double rounds = (double)cdiv(g.M, 128) * cdiv(g.N, bn) * batch / 768.0;
     const double full = (double)(long)rounds, tail = rounds - full;
     return (full + (tail > 0 ? (tail + 0.12 < 1.0 ? tail + 0.12 : 1.0) : 0.0)) * bn / eff;
   };
   const bool narrow = forced ? forced == 1
-                    : (g.K >= 1024 && fitted) ? cost(64, 0.87) < cost(128, 1.0)
+                    : g.K >= 1024 ? cost(64, 0.87) < cost(128, 1.0)
                                   : score(64, 0.92) > score(128, 1.0) + 1e-9;
   if (forced == 4) launch_nt_split_t<4>(g, batch, st);
   else if (narrow) launch_nt_split_t<1>(g, batch, st);
@@ -1251,7 +1246,7 @@ static void launch_nt_split(const GemmArgs& g, int batch, hipStream_t st) {
 }
 
 // ---- second-generation split kernel: pre-split weight planes (mx_pw_planes_batch) -----------------------------------
-static int g_split3_xcd_chunk = getenv("MX_SPLIT3_XCD_CHUNK") ? atoi(getenv("MX_SPLIT3_XCD_CHUNK")) : 6;   // N tiles per XCD-local chunk when there are more than 16
+static int g_split3_xcd_chunk = 6;     // N tiles per XCD-local chunk when there are more than 16 (lab hook: tools/hip/gemm_lab.hip chunk)
 template <int TN>
 static void launch_nt_split3_t(const GemmArgs& g, int batch, hipStream_t st) {
   constexpr int BN = 16 * TN;
@@ -1279,7 +1274,6 @@ static void launch_nt_split3_t(const GemmArgs& g, int batch, hipStream_t st) {
 // per CU always takes the 64-wide tile (M = 6272: 2304 -> 384 108 -> 91 us, M = 12544: 1152 -> 192 61 -> 51).  The odd widths are
 // only taken where they divide N (N = 160 = 2 x 80, 224 = 2 x 112, 960 = 10 x 96, 2304 = 24 x 96): no padded columns at all
 // (960 -> 160: 69 us at 64 columns, 55 at 80; 1344 -> 224: 99 at 128, 91 at 112; 480 -> 80 at 100 352 rows: 73 -> 54).
-static int g_split_nj = getenv("MX_GEMM_SPLIT_NJ") ? atoi(getenv("MX_GEMM_SPLIT_NJ")) : 0;     // 1: force 128 x 64, 2: force 128 x 128, 3: 64 / 128 only
 static void launch_nt_split3(const GemmArgs& g, int batch, hipStream_t st) {
   auto cost = [&](int bn, double eff) {
     const double per_cu = (double)cdiv(g.M, 128) * cdiv(g.N, bn) * batch / 256.0;
@@ -1338,10 +1332,6 @@ static void launch_nt(const GemmArgs& g, int batch, hipStream_t st) {
 // Choice among the NT tiles: fewest padded columns first (16-column granularity), then the widest tile whose grid still
 // gives every CU at least ~2 workgroups.
 static int pick_nt_cfg(int M, int N) {
-  if (const char* e = getenv("MX_GEMM_NT_CFG")) {
-    int forced = atoi(e);
-    if (forced >= 0 && forced < kNumNtCfgs) return forced;
-  }
   int best = 0;
   double best_score = -1.0;
   for (int c = 0; c < kNumNtCfgs; ++c) {
@@ -1389,10 +1379,9 @@ static int check_operand(const MxOperand& o, const char* nm) {
 static int tn_splits(int M, int N, int K, int* ksplit) {
   const TileCfg tc = kCfgs[pick_cfg(L_TN, M, N, K)];
   long tiles = (long)cdiv(M, tc.bm) * cdiv(N, tc.bn);
-  // workgroup target of the split (tuning override MX_GEMM_SPLIT_TARGET; swept 1024/1536/2048/3072/4096 on the final
-  // code: 150.7 / 149.6 / 148.9 / 149.8 / 149.6 ms per step)
-  static const long split_target = getenv("MX_GEMM_SPLIT_TARGET") ? atol(getenv("MX_GEMM_SPLIT_TARGET")) : 2048;
-  int splits = (int)((split_target + tiles - 1) / tiles);
+  // workgroup target of the split (swept 1024/1536/2048/3072/4096 on the final code: 150.7 / 149.6 / 148.9 / 149.8 / 149.6 ms per step)
+  constexpr long SPLIT_TARGET = 2048;
+  int splits = (int)((SPLIT_TARGET + tiles - 1) / tiles);
   int maxs = cdiv(K, 512);
   if (splits > maxs) splits = maxs;
   if (splits < 1) splits = 1;
@@ -1411,8 +1400,7 @@ static int gemm_common(int layout, GemmArgs& g, int batch, hipStream_t st) {
   g.stamps = mx_gemm_stamps;
   if (layout == L_NT) {
     MX_CHECK_ARG(g.K % 4 == 0, "gemm NT: K=%d must be a multiple of 4", g.K);
-    static const int nt_v2 = getenv("MX_GEMM_NT_V2") ? atoi(getenv("MX_GEMM_NT_V2")) : 1;
-    if (nt_v2 && g.b.mode == MX_PLAIN) dispatch_nt(g, batch, st);
+    if (g.b.mode == MX_PLAIN) dispatch_nt(g, batch, st);        // second-generation NT kernels (profiles/r02_gemm_nt_v2_vs_short.txt)
     else dispatch<L_NT>(g, batch, st);
   } else if (layout == L_NN) {
     MX_CHECK_ARG(g.K % 4 == 0 && g.N % 4 == 0, "gemm NN: K=%d and N=%d must be multiples of 4", g.K, g.N);
@@ -1531,18 +1519,15 @@ int mx_pw_planes_batch(const long* table, int n, int total_tiles, void* stream) 
 
 // 1 when, in the current mode, a forward / data-gradient GEMM of this shape should be run through mx_pw_fwd_planes
 int mx_pw_fwd_uses_planes(int M, int K, int N) {
-  static const int on = getenv("MX_SPLIT2") ? atoi(getenv("MX_SPLIT2")) : 1;
-  static const int early = getenv("MX_SPLIT3_EARLY") ? atoi(getenv("MX_SPLIT3_EARLY")) : 1;
-  static const int tail = getenv("MX_SPLIT3_KTAIL") ? atoi(getenv("MX_SPLIT3_KTAIL")) : 1;
-  if (!on || M <= 0 || K % 16) return 0;
+  if (M <= 0 || K % 16) return 0;
   // K = 48 / 80 (the expand convolutions of stages 2-3 and the project data gradients beside them, 0.1-0.4 M rows): HBM-bound, and
   // the second-generation kernel's register-direct activation stream wins there as well; the half K step it pads costs MFMA time only
-  if (K % 32) return (g_gemm_mode != 0 && tail && K >= 48 && N >= 96) ? 1 : 0;
+  if (K % 32) return (g_gemm_mode != 0 && K >= 48 && N >= 96) ? 1 : 0;
   if (nt_uses_split(N, K)) return 1;
   // the HBM-bound data gradients of stages 2-3 (K = 288 -> 48 at 401 408 rows, 480 -> 80 at 100 352): the second-generation
   // kernel streams their long operand straight into registers and beats the exact-fp32 kernel there too (137 -> 127 us,
   // 102 -> 78 us; tools/hip/gemm_lab planes); narrower outputs / shorter reductions stay where they are (32 -> 32: 73 vs 90 us)
-  return (g_gemm_mode == 1 && early && K >= 192 && N >= 48) ? 1 : 0;
+  return (g_gemm_mode == 1 && K >= 192 && N >= 48) ? 1 : 0;
 }
 
 // C[M,N] = A[M,K] * W[N,K]^T (+bias) (+residual) (relu) with W given as its pre-split image (mx_pw_planes_batch) and a plain A:
@@ -1566,11 +1551,9 @@ int mx_pw_fwd_planes(const float* A, const void* Wplanes, float* C, int M, int K
 
 // 1 when, in the current mode, the project convolution's forward GEMM on swish(scale*A + shift) * gate should go through
 // mx_pw_fwd_planes_act: the narrow outputs of stages 2-3 (K = 192 / 288 -> 48, 288 / 480 -> 80 at 0.1-0.4 M rows), HBM-bound - the
-// register-direct activation stream beats the exact-fp32 kernel's LDS slabs there as it does for the plain form (MX_SPLIT3_ACT=0: off)
+// register-direct activation stream beats the exact-fp32 kernel's LDS slabs there as it does for the plain form
 int mx_pw_fwd_act_uses_planes(int M, int K, int N) {
-  static const int on = getenv("MX_SPLIT3_ACT") ? atoi(getenv("MX_SPLIT3_ACT")) : 1;
-  static const int split2 = getenv("MX_SPLIT2") ? atoi(getenv("MX_SPLIT2")) : 1;
-  return (on && split2 && g_gemm_mode != 0 && M >= 65536 && K % 32 == 0 && K >= 192 && N >= 48 && N <= 128) ? 1 : 0;
+  return (g_gemm_mode != 0 && M >= 65536 && K % 32 == 0 && K >= 192 && N >= 48 && N <= 128) ? 1 : 0;
 }
 
 // C[M,N] = (swish(scale[k]*A[m,k] + shift[k]) * gate[m / rows_per_sample, k]) * W[N,K]^T with W as its pre-split image: the operand

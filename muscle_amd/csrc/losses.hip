@@ -618,8 +618,7 @@ int mx_cls_loss(int mode, const float* x, int ldx, const float* y, int ldy, floa
 int mx_imc(const float* emb, const float* label, int N, int D, int L, float* out2, float* gemb, float* workspace, void* stream) {
   MX_CHECK_ARG(emb && label && out2 && gemb && workspace, "imc: null pointer");
   MX_CHECK_ARG(N > 0 && N <= IMC_MAXN && D > 0 && D <= 1024 && L > 0, "imc: N=%d (<=64) D=%d (<=1024) L=%d", N, D, L);
-  static const int mfma = getenv("MX_IMC_MFMA") ? atoi(getenv("MX_IMC_MFMA")) : 1;
-  if (mfma && D % 16 == 0 && L <= 32 && (((uintptr_t)emb | (uintptr_t)workspace) & 15) == 0) {
+  if (D % 16 == 0 && L <= 32 && (((uintptr_t)emb | (uintptr_t)workspace) & 15) == 0) {
     const int nb = cdiv(N, 16);
     hipLaunchKernelGGL(imc_gram_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, emb, label, N, D, L, workspace);
     MX_LAUNCH_CHECK();
@@ -996,7 +995,7 @@ int mx_er_lr_fwd(const float* cam, const float* sgc, const float* lwb, int N, in
   const int shifts[3] = {21, 10, 0}, bits[3] = {11, 11, 10};
   const unsigned himask[3] = {0u, 0xFFE00000u, 0xFFFFFC00u};
   long HW = (long)H * W;
-  static const int chunk_px = getenv("MX_ER_CHUNK") ? atoi(getenv("MX_ER_CHUNK")) : 1024;   // pixels per workgroup; 4096 / 2048 / 1024 / 512: 0.81 / 0.69 / 0.65 / 0.69 ms (N=16), 1.25 / 1.17 / 1.16 / 1.27 (N=32)
+  constexpr int chunk_px = 1024;   // pixels per workgroup; 4096 / 2048 / 1024 / 512: 0.81 / 0.69 / 0.65 / 0.69 ms (N=16), 1.25 / 1.17 / 1.16 / 1.27 (N=32)
   int chunks = (int)((HW + chunk_px - 1) / chunk_px);
   if (chunks > 256) chunks = 256;
   for (int ps = 0; ps < 3; ++ps) {

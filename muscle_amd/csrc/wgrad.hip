@@ -196,8 +196,8 @@ void mx_launch_parts_reduce(const float* part, int groups, int n, float* dW, hip
 
 static bool wg_plan(int R, int Co, int Ci, WgPlan* p) {
   const int cot = cdiv(Co, 16), cit = cdiv(Ci, 16);
-  static const int rmin = getenv("MX_WGRAD_SMALL_RMIN") ? atoi(getenv("MX_WGRAD_SMALL_RMIN")) : 65536;
-  if (Co % 4 || Ci % 4 || (long)Co * Ci > 40960 || R < rmin) return false;
+  constexpr int RMIN = 65536;                                 // shorter reductions stay with the tiled kernels
+  if (Co % 4 || Ci % 4 || (long)Co * Ci > 40960 || R < RMIN) return false;
   // waves: 4, or 8 when the tiles of one wave would exceed 24 (96 accumulator registers)
   int best_nw = 0, best_wco = 0, best_cost = 1 << 30;
   for (int nw : {4, 8}) {
@@ -227,14 +227,13 @@ static bool wg_plan(int R, int Co, int Ci, WgPlan* p) {
 }
 
 template <int TCO, int TCI, int NW, int GI, int XI, int XMODE, bool GBN = false>
-static void wg_launch_one(const WgArgs& a, const WgPlan& p, hipStream_t st) {
-  static bool big_lds_ok = false;                      // > 64 KB of dynamic LDS needs the attribute, once per kernel
-  if (p.lds_bytes > 64 * 1024 && !big_lds_ok) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_small_kernel<TCO, TCI, NW, GI, XI, XMODE, GBN>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    big_lds_ok = true;
+static int wg_launch_one(const WgArgs& a, const WgPlan& p, hipStream_t st) {
+  if (p.lds_bytes > 64 * 1024) {
+    const int rc = mx_dyn_lds_optin(reinterpret_cast<const void*>(&wgrad_small_kernel<TCO, TCI, NW, GI, XI, XMODE, GBN>), 80 * 1024);
+    if (rc != MX_OK) return rc;
   }
   hipLaunchKernelGGL((wgrad_small_kernel<TCO, TCI, NW, GI, XI, XMODE, GBN>), dim3(p.groups), dim3(NW * 64), p.lds_bytes, st, a);
+  return MX_OK;
 }
 
 // The instantiations that exist: the (Co, Ci, prologue) combinations of EfficientNet-B7's first four stages (project convs
@@ -251,28 +250,24 @@ static void wg_launch_one(const WgArgs& a, const WgPlan& p, hipStream_t st) {
   V(1, 1, 4, 1, 1, MX_BNACT)  /* 32 x 32              project of blocks 1-3                                 */ \
   V(1, 1, 4, 1, 1, MX_PLAIN)  /* 32 x 32              (plain)                                               */
 
-static bool wg_dispatch(const WgArgs& a, const WgPlan& p, hipStream_t st, bool launch) {
+// the launcher of the instantiation that takes (plan, Co, Ci, prologue, fold), or nullptr: there is none
+typedef int (*WgLaunch)(const WgArgs&, const WgPlan&, hipStream_t);
+static WgLaunch wg_dispatch(const WgPlan& p, int Co, int Ci, int x_mode, bool gbn) {
   const int lpr = p.nw * 64 / 16;
-  const int gi = cdiv(a.Co / 4, lpr), xi = cdiv(a.Ci / 4, lpr);
-#define WG_TRY(TCO, TCI, NW, GI, XI, MODE)                                                             \
-  if (p.tco == TCO && p.tci == TCI && p.nw == NW && gi == GI && xi == XI && a.X.mode == MODE) {        \
-    if (launch) wg_launch_one<TCO, TCI, NW, GI, XI, MODE>(a, p, st);                                   \
-    return true;                                                                                       \
-  }
-  if (a.G2) {                       // folded BatchNorm backward apply on G: the expand convs of block 4 and of stage 2 (plain X)
-#define WG_TRY_GBN(TCO, TCI, NW, GI, XI)                                                               \
-    if (p.tco == TCO && p.tci == TCI && p.nw == NW && gi == GI && xi == XI && a.X.mode == MX_PLAIN) {  \
-      if (launch) wg_launch_one<TCO, TCI, NW, GI, XI, MX_PLAIN, true>(a, p, st);                       \
-      return true;                                                                                     \
-    }
+  const int gi = cdiv(Co / 4, lpr), xi = cdiv(Ci / 4, lpr);
+  if (gbn) {                        // folded BatchNorm backward apply on G: the expand convs of block 4 and of stage 2 (plain X)
+#define WG_TRY_GBN(TCO, TCI, NW, GI, XI)                                                                         \
+    if (p.tco == TCO && p.tci == TCI && p.nw == NW && gi == GI && xi == XI && x_mode == MX_PLAIN) return &wg_launch_one<TCO, TCI, NW, GI, XI, MX_PLAIN, true>;
     WG_TRY_GBN(3, 2, 4, 3, 1)       /* 192 x 32 */
     WG_TRY_GBN(5, 3, 4, 5, 1)       /* 288 x 48 */
 #undef WG_TRY_GBN
-    return false;
+    return nullptr;
   }
+#define WG_TRY(TCO, TCI, NW, GI, XI, MODE)                                                                       \
+  if (p.tco == TCO && p.tci == TCI && p.nw == NW && gi == GI && xi == XI && x_mode == MODE) return &wg_launch_one<TCO, TCI, NW, GI, XI, MODE>;
   WG_TABLE(WG_TRY)
 #undef WG_TRY
-  return false;
+  return nullptr;
 }
 
 // =====================================================================================================================
@@ -590,24 +585,18 @@ __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(WtArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Round 5: the split weight gradient as ONE software-pipelined instruction stream (plain operands; the prologue modes keep
-// the kernel above).  Same tile, same loader mapping, same LDS image, same MFMA order as wgrad_split_kernel - the results
-// are bit-identical - but:
-//   * two LDS stages (96 KB, one workgroup = one wave per SIMD per CU) and ONE barrier per 32-row slab;
-//   * the fragments of a 16-row step are read one step AHEAD of their MFMAs (two fragment register sets), so no ds_read
-//     latency sits between a barrier and the matrix pipe; the split + plane stores of slab s+1 are placed BETWEEN the MFMAs of
-//     slab s, ~4 vector instructions per MFMA gap (an MFMA holds the vector issue for 8 of its 32 cycles,
-//     MI355X_MICROARCH.md 'vector-instruction ISSUE cost'); the raw rows of slab s+2 are in flight meanwhile (two raw sets);
-//   * every global load is a buffer load through a descriptor that covers exactly the group's rows: rows past the group's
-//     end and the columns past the matrix read as zeros by the range check - no compares, no branches, so the slab is one
-//     basic block the scheduler can order.
-// The first structure spent ~3500 cycles per slab and CU with three workgroups resident (MFMA work: 1536): a split/store
-// phase, a barrier, and an MFMA phase whose ds_reads were waited for right in front of their MFMAs.
-#ifndef WPIPE_PF
-#define WPIPE_PF 3         // raw row sets: slab s + WPIPE_PF is requested while slab s is multiplied (bytes in flight per CU = 32 KB x (WPIPE_PF - 1))
-#endif
+// Round 5 first rebuilt the split weight gradient as ONE software-pipelined instruction stream (two LDS stages, one barrier per slab,
+// fragments read a step ahead, the split placed between the MFMAs; profiles/r05_wgrad_pipe_lab.txt).  The wave-specialised kernel below
+// superseded it and it is gone; what it introduced and the kernels below keep:
+//   * every global load is a buffer load through a descriptor that covers exactly the group's rows: rows past the group's end and the
+//     columns past the matrix read as zeros by the range check - no compares, no branches;
+//   * the LDS image of one plane: [4 k-groups][4 column classes (col & 3)][36 = 32 columns (col >> 2) + 4 pad] chunks of 16 bytes (8 k of
+//     one column).  A loader pass (16 lanes = 16 consecutive 4-column chunks, one column class) writes 16 consecutive chunks; a fragment
+//     pass (16 consecutive columns of one k-group) reads chunks 36 b + a + 4 m (b = col & 3, a = (col >> 2) & 3): 16 different bank groups
+//     either way.  The first kernel's [128 columns][64 bytes] image is conflict-free for the reads only: its plane stores hit 4 bank
+//     groups per pass (4-way), which made the LDS, not the matrix pipe, the busiest unit.
 #ifndef WPIPE_KNOCK
-#define WPIPE_KNOCK 0      // diagnostic builds of tools/hip/gemm_lab only: 1 no split, 2 no split / plane stores, 3 no MFMA, 4 no fragment reads, 5 no global traffic, 6 split but no plane stores
+#define WPIPE_KNOCK 0      // diagnostic builds of tools/hip/gemm_lab only: 1 = no split in the loader waves
 #endif
 
 static __device__ __forceinline__ __amdgpu_buffer_rsrc_t wbuf_rsrc(const float* base, long bytes) {
@@ -618,217 +607,12 @@ static __device__ __forceinline__ __amdgpu_buffer_rsrc_t wbuf_rsrc(const float* 
   return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)hi << 32) | lo), 0, n, 0x00020000);
 }
 
-#define WPIPE_MFMA(GV, XV, T, EF)                                                                                              \
-  acc[(EF) >> 1][(EF) & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(GV[(EF) >> 1][PG[T]], XV[(EF) & 1][PX[T]], acc[(EF) >> 1][(EF) & 1], 0, 0, 0)
-
 #ifdef WPIPE_STAMPS        // diagnostic builds of tools/hip/gemm_lab only: shader-clock stamps per workgroup (start, loop start, loop end, end, 2 x realtime)
 __device__ unsigned long long* wpipe_stamps;
-#define WPIPE_STAMP(slot) do { if (wpipe_stamps && threadIdx.x == 0) { wpipe_stamps[blockIdx.x * 8l + (slot)] = __builtin_amdgcn_s_memtime(); \
-    if ((slot) == 0 || (slot) == 3) wpipe_stamps[blockIdx.x * 8l + 4 + ((slot) == 3)] = __builtin_amdgcn_s_memrealtime(); } } while (0)
-#else
-#define WPIPE_STAMP(slot) do { } while (0)
 #endif
-__global__ __launch_bounds__(256, 1) void wgrad_split_pipe_kernel(WtArgs a) {
-  // LDS image of one plane: [4 k-groups][4 column classes (col & 3)][36 = 32 columns (col >> 2) + 4 pad] chunks of 16 bytes (8 k of one
-  // column).  A loader pass (16 lanes = 16 consecutive 4-column chunks, one column class) writes 16 consecutive chunks; a fragment
-  // pass (16 consecutive columns of one k-group) reads chunks 36 b + a + 4 m (b = col & 3, a = (col >> 2) & 3): 16 different bank groups
-  // either way.  The first kernel's [128 columns][64 bytes] image is conflict-free for the reads only: its plane stores hit 4 bank
-  // groups per pass (4-way), which made the LDS, not the matrix pipe, the busiest unit (profiles/r05_wgrad_pipe_lab.txt).
-  constexpr int PLANE = 4 * 144 * 16, STAGE = 6 * PLANE;    // G h/m/l, X h/m/l per stage
-  extern __shared__ __attribute__((aligned(16))) unsigned char wp_smem[];      // 2 * STAGE
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // wave-uniform facts in SGPRs
-  const int l31 = lane & 31, hf = lane >> 5;
-  const int wco = wave >> 1, wci = wave & 1;
-  const int tiles = a.tiles_co * a.tiles_ci;
-  const int L = blockIdx.x, xcd = L & 7, j = L >> 3;
-  const int group = (j / tiles) * 8 + xcd, tile = j % tiles;
-  if (group >= a.groups) return;
-  const int co0 = (tile / a.tiles_ci) * 128, ci0 = (tile % a.tiles_ci) * 128;
-  const long r_beg = (long)group * a.rows_per_group;
-  const long r_end = min((long)a.R, r_beg + a.rows_per_group);
-  const int rows = (int)(r_end - r_beg);
-
-  // loader: waves 0-1 move G, 2-3 move X; thread = (4-column chunk c of 32, row group rg of 4): rows 8 rg .. 8 rg + 7 of the slab
-  const bool isx = wave >= 2;
-  const int lt = tid & 127, c = lt & 31, rg = lt >> 5;
-  const int col0 = (isx ? ci0 : co0) + 4 * c;
-  const bool colok = col0 < (isx ? a.Ci : a.Co);
-  const int ld = __builtin_amdgcn_readfirstlane(isx ? a.ldx : a.ldg);
-  const __amdgpu_buffer_rsrc_t rs = wbuf_rsrc((isx ? a.X.p : a.G) + r_beg * ld, WPIPE_KNOCK == 5 ? 0 : (long)rows * ld * 4);
-  const unsigned vbase = colok ? (unsigned)((8 * rg * ld + col0) * 4) : 0x7f000000u;      // past every record: reads as zero
-  const unsigned slab_bytes = (unsigned)(32 * ld * 4), row_bytes = (unsigned)(ld * 4);
-
-  typedef float wf4 __attribute__((ext_vector_type(4)));
-  wf4 raw[WPIPE_PF][8];
-  auto gload = [&](wf4 (&rv)[8], int s) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-      rv[i] = __builtin_bit_cast(wf4, __builtin_amdgcn_raw_buffer_load_b128(rs, vbase + (unsigned)i * row_bytes, (unsigned)s * slab_bytes, 0));
-  };
-  // split of column 4 c + jc, row pair q (rows 2 q, 2 q + 1 of the thread's eight): slices A / B / C of 4 / 4 / 3 vector instructions
-  unsigned sh_[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, sm_[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, sl_[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};      // two columns' planes
-  float r0_, r1_, s0_, s1_;
-  unsigned u0_, u1_, v0_, v1_;
-  unsigned char* const wbase = wp_smem + (isx ? 3 * PLANE : 0);
-  const int woff0 = (rg * 144 + c) * 16;                     // + 36 * 16 per column class
-
-#define WPIPE_X(RV, JC, Q, ROW) ((JC) == 0 ? RV[2 * (Q) + (ROW)][0] : (JC) == 1 ? RV[2 * (Q) + (ROW)][1] : (JC) == 2 ? RV[2 * (Q) + (ROW)][2] : RV[2 * (Q) + (ROW)][3])
-#define WPIPE_SLICE_A(RV, JC, Q)                                                              \
-  { const float x0 = WPIPE_X(RV, JC, Q, 0), x1 = WPIPE_X(RV, JC, Q, 1);                       \
-    u0_ = __float_as_uint(x0) & 0xffff0000u; u1_ = __float_as_uint(x1) & 0xffff0000u;        \
-    r0_ = x0 - __uint_as_float(u0_); r1_ = x1 - __uint_as_float(u1_); }
-#define WPIPE_SLICE_B()                                                                       \
-  { v0_ = __float_as_uint(r0_) & 0xffff0000u; v1_ = __float_as_uint(r1_) & 0xffff0000u;      \
-    s0_ = r0_ - __uint_as_float(v0_); s1_ = r1_ - __uint_as_float(v1_); }
-#define WPIPE_SLICE_C(B, Q)                                                                   \
-  { sh_[B][Q] = __builtin_amdgcn_perm(u1_, u0_, 0x07060302u); sm_[B][Q] = __builtin_amdgcn_perm(v1_, v0_, 0x07060302u); \
-    sl_[B][Q] = __builtin_amdgcn_perm(__float_as_uint(s1_), __float_as_uint(s0_), 0x07060302u); }
-#define WPIPE_WRITE(STG, JC)                                                                                  \
-  { unsigned char* o_ = wbase + (STG) * STAGE + woff0 + (JC) * 576;                                                    \
-    *reinterpret_cast<uint4*>(o_) = make_uint4(sh_[0][0], sh_[0][1], sh_[0][2], sh_[0][3]);                   \
-    *reinterpret_cast<uint4*>(o_ + PLANE) = make_uint4(sm_[0][0], sm_[0][1], sm_[0][2], sm_[0][3]);           \
-    *reinterpret_cast<uint4*>(o_ + 2 * PLANE) = make_uint4(sl_[0][0], sl_[0][1], sl_[0][2], sl_[0][3]); }
-
-  wf32x16 acc[2][2];
-#pragma unroll
-  for (int e = 0; e < 2; ++e)
-#pragma unroll
-    for (int f = 0; f < 2; ++f)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[e][f][r] = 0.f;
-  wbf16x8 gv0[2][3], xv0[2][3], gv1[2][3], xv1[2][3];
-#pragma unroll
-  for (int e = 0; e < 2; ++e)
-#pragma unroll
-    for (int p = 0; p < 3; ++p)
-#pragma unroll
-      for (int i = 0; i < 8; ++i) { gv1[e][p][i] = (__bf16)0.f; xv1[e][p][i] = (__bf16)0.f; }
-  const int fro = (hf * 144 + (l31 & 3) * 36 + (l31 >> 2)) * 16;         // this lane's chunk of k-group hf, column l31 of a 32-column block
-  const int cgo = fro + wco * 256, cxo = fro + 3 * PLANE + wci * 256;       // + 128 per 32-column block e, + 2 * 144 * 16 per 16-row step
-  auto frd = [&](const unsigned char* st, int ks, wbf16x8 (&gv)[2][3], wbf16x8 (&xv)[2][3]) {
-    if (WPIPE_KNOCK == 4) return;
-#pragma unroll
-    for (int p = 0; p < 3; ++p)
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        gv[e][p] = *reinterpret_cast<const wbf16x8*>(st + cgo + p * PLANE + e * 128 + ks * 4608);
-        xv[e][p] = *reinterpret_cast<const wbf16x8*>(st + cxo + p * PLANE + e * 128 + ks * 4608);
-      }
-  };
-  constexpr int PG[6] = {0, 2, 1, 0, 1, 0}, PX[6] = {2, 0, 1, 1, 0, 0};
-
-  const int ns = (rows + 31) / 32;
-  WPIPE_STAMP(0);
-  // prologue: slab 0 split into stage 0, slab 1 in flight
-  gload(raw[0], 0);
-  gload(raw[1], 1);
-  if (WPIPE_PF >= 3) gload(raw[WPIPE_PF >= 3 ? 2 : 0], 2);
-  if (WPIPE_PF >= 4) gload(raw[WPIPE_PF >= 4 ? 3 : 0], 3);
-#pragma unroll
-  for (int jc = 0; jc < 4; ++jc) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) { WPIPE_SLICE_A(raw[0], jc, q); WPIPE_SLICE_B(); WPIPE_SLICE_C(0, q); }
-    WPIPE_WRITE(0, jc);
-  }
-  __builtin_amdgcn_s_waitcnt(0xc07f);      /* lgkmcnt(0), as a builtin: the compiler's own wait counting sees it */
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-
-  // One slab: MFMAs of (slab s - 1, second step) from set 1, then of (slab s, first step) from set 0; between them the split of the raw
-  // set RB (slab s + 1) into the other stage.  48 MFMAs, 32 row pairs: a pair's three slices go behind three consecutive MFMAs,
-  // a column's three plane stores behind its fourth pair.
-  // Every gap (the 24 cycles an MFMA leaves the vector issue free) gets one slice of the split (3-4 vector instructions) and at most one
-  // memory instruction: the 12 fragment reads of the NEXT 16-row step in gaps 0-11 (consumption order), 4 of the 8 raw-row requests of
-  // slab s + WPIPE_PF in gaps 13 / 16 / 19 / 22, and the three plane stores of a finished column two gaps apart behind it (second register
-  // set, so the next column's split goes on).  Bursts cost: 8 x 1 KB requests in a row hold the CU's one address unit for ~130 cycles, a
-  // 16-byte LDS store takes its wave's issue for >= 13 (MI355X_MICROARCH.md, LDS table) - neither fits into one gap.
-#define WPIPE_FRD1(ST, KS, R, GVT, XVT)                                                                       \
-  { const int g_ = (R) >> 2, e_ = (R) & 1;                                                                     \
-    if (WPIPE_KNOCK != 4) {                                                                                    \
-      if ((((R) >> 1) & 1) == 0) GVT[e_][g_ == 0 ? 0 : g_ == 1 ? 2 : 1] = *reinterpret_cast<const wbf16x8*>((ST) + cgo + (g_ == 0 ? 0 : g_ == 1 ? 2 : 1) * PLANE + e_ * 128 + (KS) * 4608); \
-      else XVT[e_][g_ == 0 ? 2 : g_ == 1 ? 0 : 1] = *reinterpret_cast<const wbf16x8*>((ST) + cxo + (g_ == 0 ? 2 : g_ == 1 ? 0 : 1) * PLANE + e_ * 128 + (KS) * 4608); } }
-#define WPIPE_GLD1(RVT, I, S)                                                                                 \
-  RVT[I] = __builtin_bit_cast(wf4, __builtin_amdgcn_raw_buffer_load_b128(rs, vbase + (unsigned)(I) * row_bytes, (unsigned)(S) * slab_bytes, 0));
-#define WPIPE_WRITE1(STG, JC, P)                                                                              \
-  if (WPIPE_KNOCK == 6) { _Pragma("unroll") for (int k_ = 0; k_ < 4; ++k_) asm volatile("" :: "v"((P) == 0 ? sh_[(JC) & 1][k_] : (P) == 1 ? sm_[(JC) & 1][k_] : sl_[(JC) & 1][k_])); } else \
-  { unsigned char* o_ = wbase + (STG) * STAGE + woff0 + (JC) * 576 + (P) * PLANE;                              \
-    if ((P) == 0) *reinterpret_cast<uint4*>(o_) = make_uint4(sh_[(JC) & 1][0], sh_[(JC) & 1][1], sh_[(JC) & 1][2], sh_[(JC) & 1][3]);      \
-    else if ((P) == 1) *reinterpret_cast<uint4*>(o_) = make_uint4(sm_[(JC) & 1][0], sm_[(JC) & 1][1], sm_[(JC) & 1][2], sm_[(JC) & 1][3]); \
-    else *reinterpret_cast<uint4*>(o_) = make_uint4(sl_[(JC) & 1][0], sl_[(JC) & 1][1], sl_[(JC) & 1][2], sl_[(JC) & 1][3]); }
-  // HALF: 24 MFMAs on the fragment set (GV, XV); reads the other set (GVN, XVN) for step KSN of stage STN; splits columns JC0, JC0 + 1 of RV
-  // into stage NSTG; requests rows I0 .. I0 + 3 of slab SL into RVL
-#define WPIPE_HALF(GV, XV, GVN, XVN, STN, KSN, RV, JC0, NSTG, RVL, I0, SL)                                    \
-  _Pragma("unroll") for (int n_ = 0; n_ < 24; ++n_) {                                                         \
-    if (WPIPE_KNOCK != 3) { WPIPE_MFMA(GV, XV, n_ >> 2, n_ & 3); }                                            \
-    const int jc_ = (JC0) + n_ / 12, q_ = (n_ % 12) / 3, sl3_ = n_ % 3;                                       \
-    if (n_ < 12) { WPIPE_FRD1(STN, KSN, n_, GVN, XVN); }                                                      \
-    else if (n_ % 3 == 1) { WPIPE_GLD1(RVL, (I0) + (n_ - 13) / 3, SL); }                                      \
-    if (WPIPE_KNOCK != 1 && WPIPE_KNOCK != 2) {                                                               \
-      if (sl3_ == 0) { WPIPE_SLICE_A(RV, jc_, q_); }                                                          \
-      else if (sl3_ == 1) { WPIPE_SLICE_B(); }                                                                \
-      else { WPIPE_SLICE_C(jc_ & 1, q_); }                                                                    \
-    }                                                                                                         \
-    if (WPIPE_KNOCK != 2) {                                                                                   \
-      if ((JC0) == 2 && (n_ == 1 || n_ == 3 || n_ == 5)) { WPIPE_WRITE1(NSTG, 1, (n_ - 1) / 2); }             \
-      if (n_ == 13 || n_ == 15 || n_ == 17) { WPIPE_WRITE1(NSTG, JC0, (n_ - 13) / 2); }                       \
-      if ((JC0) == 2 && n_ == 23) { WPIPE_WRITE1(NSTG, 3, 0); WPIPE_WRITE1(NSTG, 3, 1); WPIPE_WRITE1(NSTG, 3, 2); } \
-    }                                                                                                         \
-    __builtin_amdgcn_sched_barrier(0);                                                                        \
-  }
-#define WPIPE_BODY(S, RB)                                                                                     \
-  {                                                                                                           \
-    const unsigned char* st_ = wp_smem + ((S) & 1) * STAGE;                                                   \
-    const int nstg_ = ((S) + 1) & 1;                                                                          \
-    WPIPE_HALF(gv1, xv1, gv0, xv0, st_, 0, raw[RB], 0, nstg_, raw[((RB) + WPIPE_PF - 1) % WPIPE_PF], 0, (S) + WPIPE_PF) \
-    WPIPE_HALF(gv0, xv0, gv1, xv1, st_, 1, raw[RB], 2, nstg_, raw[((RB) + WPIPE_PF - 1) % WPIPE_PF], 4, (S) + WPIPE_PF) \
-    __builtin_amdgcn_s_waitcnt(0xc07f);      /* lgkmcnt(0), as a builtin: the compiler's own wait counting sees it */ \
-    __builtin_amdgcn_s_barrier();                                                                             \
-    asm volatile("" ::: "memory");                                                                            \
-  }
-  WPIPE_STAMP(1);
-  for (int s = 0; s < ns; s += WPIPE_PF) {        // unrolled by the number of raw sets: their indices are compile-time constants
-    WPIPE_BODY(s, 1)
-    if (s + 1 < ns) WPIPE_BODY(s + 1, 2 % WPIPE_PF)
-    if (WPIPE_PF >= 3 && s + 2 < ns) WPIPE_BODY(s + 2, 3 % WPIPE_PF)
-    if (WPIPE_PF >= 4 && s + 3 < ns) WPIPE_BODY(s + 3, 0)
-  }
-  WPIPE_STAMP(2);
-  // the last slab's second step
-#pragma unroll
-  for (int n_ = 0; n_ < 24; ++n_) { WPIPE_MFMA(gv1, xv1, n_ >> 2, n_ & 3); }
-#undef WPIPE_BODY
-#undef WPIPE_HALF
-#undef WPIPE_FRD1
-#undef WPIPE_GLD1
-#undef WPIPE_WRITE1
-#undef WPIPE_WRITE
-#undef WPIPE_SLICE_A
-#undef WPIPE_SLICE_B
-#undef WPIPE_SLICE_C
-#undef WPIPE_X
-
-  // acc[e][f][4 g + r] = dW[co0 + 64 wco + 32 e + 8 g + 4 hf + r][ci0 + 64 wci + 32 f + l31]
-  float* out = a.part + (a.accumulate ? 0 : (long)group * a.Co * a.Ci);
-#pragma unroll
-  for (int e = 0; e < 2; ++e)
-#pragma unroll
-    for (int f = 0; f < 2; ++f) {
-      const int ci = ci0 + 64 * wci + 32 * f + l31;
-      if (ci >= a.Ci) continue;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int co = co0 + 64 * wco + 32 * e + 8 * (r >> 2) + 4 * hf + (r & 3);
-        if (co >= a.Co) continue;
-        float* o = out + (long)co * a.Ci + ci;
-        *o = a.accumulate ? *o + acc[e][f][r] : acc[e][f][r];
-      }
-    }
-  WPIPE_STAMP(3);
-}
-#undef WPIPE_MFMA
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The same product with the two kinds of work on DIFFERENT waves (round 5).  Stamps of the single-stream kernel above say what the
+// The same product with the two kinds of work on DIFFERENT waves (round 5).  Stamps of the single-stream kernel it replaced say what the
 // matrix pipe tolerates beside it in ONE wave (cycles per 32-row slab and workgroup, floor 48 MFMAs x 32 = 1536): MFMAs + fragment
 // reads + row requests 1585; + the plane stores 1824; + the 176 vector instructions of the split 2298 with the stores left out, 2538
 // with them - in one wave's stream a vector instruction adds its 4 issue cycles to the MFMA's 32 instead of hiding under them.
@@ -856,7 +640,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_split_pipe_kernel(WtArgs a) {
 // BOTH consumers, no GEMM kernel carries a second operand stream in its matrix waves.
 template <bool GBN>
 __global__ __launch_bounds__(512, 1) void wgrad_split_ws_kernel(WtArgs a) {
-  constexpr int PLANE = 4 * 144 * 16, STAGE = 6 * PLANE;    // the image of wgrad_split_pipe_kernel
+  constexpr int PLANE = 4 * 144 * 16, STAGE = 6 * PLANE;    // the LDS image described above wbuf_rsrc
   constexpr int PF = WWS_PF;                                // raw row sets (the folded form holds two tensors' rows in each)
   extern __shared__ __attribute__((aligned(16))) unsigned char ws_smem[];      // 2 * STAGE
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1257,15 +1041,21 @@ __global__ __launch_bounds__(512, 1) void wgrad_f32_ws_kernel(WtArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-struct WtPlan { int te, tf, tiles_co, tiles_ci, groups, rows_per_group, f32ws; };
-int mx_wgrad_pipe_override = -1;      // lab hook (tools/hip/gemm_lab.hip): 0 / 1 selects the first / pipelined split kernel per call
-
-static int wt_order() {
-  static const int order = getenv("MX_WGRAD_TILE_ORDER") ? atoi(getenv("MX_WGRAD_TILE_ORDER")) : 0;
-  return order;
-}
+// ONE plan per launch: which kernel runs and over which tiles and row groups.  Every entry point and every query below asks it.
+enum WtKernel {
+  WT_TILE_F32,       // wgrad_tile_kernel: exact fp32, any prologue, 128 / 64-wide tiles
+  WT_SPLIT,          // wgrad_split_kernel: split arithmetic, any prologue, with or without the BatchNorm fold on G
+  WT_SPLIT_WS,       // wgrad_split_ws_kernel<false>: split arithmetic, plain operands, persistent wave-specialised workgroups
+  WT_SPLIT_WS_BN,    // wgrad_split_ws_kernel<true>: the same with the BatchNorm fold on G (and, optionally, dZ written)
+  WT_F32_WS,         // wgrad_f32_ws_kernel: exact fp32, plain operands, persistent wave-specialised workgroups
+};
+struct WtPlan { WtKernel kernel; int te, tf, tiles_co, tiles_ci, groups, rows_per_group; };
 
 extern "C" int mx_get_gemm_mode(void);
+
+static int g_wgrad_kernel = 2;         // mx_set_wgrad_kernel: 0 wgrad_split_kernel, 2 wgrad_split_ws_kernel take the plain-operand split launches
+static int g_wgrad_groups = 0;         // mx_set_wgrad_kernel: > 0 fixes the row groups of the plain split launches
+static int g_wgrad_f32ws = 1;          // lab hook (tools/hip/gemm_lab.hip wgradf32): 0 sends the exact-fp32 plain launches to the tiled kernel
 
 static bool wt_use_split(int Co, int Ci) {
   if (mx_get_gemm_mode() < 1) return false;
@@ -1273,25 +1063,62 @@ static bool wt_use_split(int Co, int Ci) {
   // 128 x 128 tiles only.  0.8 until late round 4 (not where they pad much); with the row groups filling the chip for few-tile outputs
   // (wt_plan) the padded shapes win as well - 960 x 160 and 480 x 80 (0.59 of their tiles used): 105 -> 76 us and 136 -> 77 us, and the
   // step 96.9 -> 95.15 ms on one box (profiles/r04_knob_sweep.txt)
-  static const double min_eff = getenv("MX_WGRAD_SPLIT_EFF") ? atof(getenv("MX_WGRAD_SPLIT_EFF")) : 0.55;
-  return mx_get_gemm_mode() == 2 || eff >= min_eff;
+  constexpr double MIN_EFF = 0.55;
+  return mx_get_gemm_mode() == 2 || eff >= MIN_EFF;
 }
 
-// which split weight-gradient kernel takes the plain-operand launches: 0 wgrad_split_kernel, 1 wgrad_split_pipe_kernel, 2 wgrad_split_ws_kernel
-static int wt_pipe_mode() {
-  static const int pipe_env = getenv("MX_WGRAD_PIPE") ? atoi(getenv("MX_WGRAD_PIPE")) : 2;
-  return mx_wgrad_pipe_override >= 0 ? mx_wgrad_pipe_override : pipe_env;
+// The wave-specialised kernels address a row group, and store a partial tile, through 32-bit buffer offsets: the group's rows (plus the
+// slabs requested ahead) x the wider leading dimension, and Co x Ci, in bytes, must stay far below 2^31.
+static bool wt_ws_offsets_fit(int rows_per_group, int Co, int Ci, int ldg, int ldx) {
+  return ((long)rows_per_group + 96) * (ldg > ldx ? ldg : ldx) * 4 < (1l << 30) && (long)Co * Ci * 4 < (1l << 30);
 }
-static int g_wgrad_groups = 0;         // mx_set_wgrad_kernel: > 0 fixes the row groups of the plain split launches
-static int g_wgrad_f32ws = getenv("MX_WGRAD_F32_WS") ? atoi(getenv("MX_WGRAD_F32_WS")) : 1;      // exact-fp32 mode: wgrad_f32_ws_kernel for the 128 x 128 tiles (0: the tiled kernel)
 
-static bool wt_plan(int R, int Co, int Ci, int x_mode, WtPlan* p) {
+// Row groups of a wave-specialised kernel: ONE persistent workgroup per CU deals the (group, tile) items out evenly, so the count that
+// matters is items / 256 rounded up.  Cost model from the kernels' own stamps at the clock they hold (~1.75 GHz): slab_us per 32-row slab,
+// 3.4 us per item (first slabs + storing the partial tile), and the partial matrices once more through the reduce kernel.  A group holds
+// at most CHAINS chains of 1568 rows, flushed inside the kernel (fewer items and partial tiles); that is the floor, and e.g. 54 tiles
+// take 18 groups (3.8 rounds) instead of 16 (3.4 -> 4 rounds).  Every count up to 128-row groups is priced:
+// outputs of a few tiles - 672 x 112 at 12 544 rows, B0 at batch 16 - fill the 256 workgroups only with 40+ groups.
+static int wt_ws_groups(int R, int tiles, double slab_us, int Co, int Ci) {
+  constexpr int CHAINS = 3;
+  const int maxg = R / 128 > 0 ? R / 128 : 1;
+  int gmin = cdiv(R, 1568 * CHAINS);
+  if (gmin > maxg) gmin = maxg;
+  int best_g = gmin;
+  double best_t = 1e30;
+  for (int g = gmin; g <= maxg; ++g) {
+    const int rpg = cdiv(cdiv(R, g), 32) * 32, ga = cdiv(R, rpg);
+    if (ga != g) continue;                                   // (the rounding of the rows makes some counts unreachable)
+    const double t = cdiv(tiles * g, 256) * (rpg / 32 * slab_us + 3.4) + g * ((double)Co * Ci * 4.0 / 4e6);
+    if (t < best_t - 1e-9) { best_t = t; best_g = g; }
+  }
+  return best_g;
+}
+
+static void wt_set_groups(WtPlan* p, int R, int groups, int row_multiple) {
+  p->rows_per_group = cdiv(cdiv(R, groups), row_multiple) * row_multiple;
+  p->groups = cdiv(R, p->rows_per_group);
+}
+
+// bn_fold: the G operand is c1*G + c2*G2 + c3 (mx_pw_wgrad_tile_bnbwd*).  ldg / ldx only decide whether a wave-specialised kernel can
+// address the operands; where it cannot, the launch gets the kernel and the groups of the rule below it.
+static bool wt_plan(int R, int Co, int Ci, int x_mode, bool bn_fold, int ldg, int ldx, WtPlan* p) {
   if (Co % 4 || Ci % 4 || R < 1024 || (long)Co * Ci < 16384) return false;
-  p->f32ws = 0;
+  const bool forced = g_wgrad_groups > 0 && x_mode == MX_PLAIN;
   if (wt_use_split(Co, Ci)) {
     p->te = p->tf = 4;
     p->tiles_co = cdiv(Co, 128); p->tiles_ci = cdiv(Ci, 128);
-    // Row groups of the split kernel.  Standalone, many small work items are fastest (g = 32 at up to ~100 tiles: 1344 x 224 132 ->
+    const int tiles = p->tiles_co * p->tiles_ci;
+    const int maxg = R / 128 > 0 ? R / 128 : 1;
+    if (x_mode == MX_PLAIN && g_wgrad_kernel == 2) {
+      // (1.09 us per 32-row slab: wgrad_split_ws_kernel's own stamps)
+      wt_set_groups(p, R, forced ? (g_wgrad_groups < maxg ? g_wgrad_groups : maxg) : wt_ws_groups(R, tiles, 1.09, Co, Ci), 32);
+      if (wt_ws_offsets_fit(p->rows_per_group, Co, Ci, ldg, ldx)) {
+        p->kernel = bn_fold ? WT_SPLIT_WS_BN : WT_SPLIT_WS;
+        return true;
+      }
+    }
+    // Row groups of the first split kernel.  Standalone, many small work items are fastest (g = 32 at up to ~100 tiles: 1344 x 224 132 ->
     // 118 us; profiles/r04_wgrad_split_groups.txt) - but the weight gradients run on the side stream BESIDE the HBM-bound kernels
     // of the backward chain, and there every extra group is a partial matrix written and read back through the memory system
     // those kernels live on: in the step FEWER groups win (B7 / 448 / batch 32, one box, every shape at g = 2 / 4 / 6 / 8 / 16 / 24 /
@@ -1302,59 +1129,41 @@ static bool wt_plan(int R, int Co, int Ci, int x_mode, WtPlan* p) {
     // ids) keep every tested shape level with the fp32 kernel and are within 0.3 ms per step of g = 8.
     // The bound is on the CHAIN, not on the count: at most 1568 rows per group, so R = 50 176 (B7 at batch 64, or batch 32 at larger
     // images) takes 32 groups instead of running 3136-row chains at 16 (tests/test_gpu_split.py has R = 50 176 and 62 720 cases).
-    const int maxg = R / 128 > 0 ? R / 128 : 1;
-    if (x_mode == MX_PLAIN && wt_pipe_mode() >= 2) {
-      // wgrad_split_ws_kernel: ONE persistent workgroup per CU deals the (group, tile) items out evenly, so the count that matters is
-      // items / 256 rounded up.  Cost model from the kernel's own stamps at the clock it holds (~1.75 GHz): 1.09 us per 32-row slab,
-      // 3.4 us per item (first slabs + storing the partial tile), and the partial matrices once more through the reduce kernel.
-      // The chain bound (<= 1568 rows per group) is the floor; 54 tiles take 18 groups (3.8 rounds) instead of 16 (3.4 -> 4 rounds).
-      const int tiles = p->tiles_co * p->tiles_ci;
-      // (a group may hold up to MX_WGRAD_WS_CHAINS chains of 1568 rows, flushed inside the kernel: fewer items and partial tiles)
-      static const int chains = getenv("MX_WGRAD_WS_CHAINS") ? atoi(getenv("MX_WGRAD_WS_CHAINS")) : 3;
-      int gmin = cdiv(R, 1568 * (chains > 0 ? chains : 1));
-      if (gmin < 1) gmin = 1;
-      if (gmin > maxg) gmin = maxg;
-      int best_g = gmin;
-      double best_t = 1e30;
-      // (every count up to 128-row groups is priced: outputs of a few tiles - 672 x 112 at 12 544 rows, B0 at batch 16 - fill the 256
-      //  workgroups only with 40+ groups; the search used to stop at 3 gmin + 8)
-      static const int wide = getenv("MX_WGRAD_WS_WIDE") ? atoi(getenv("MX_WGRAD_WS_WIDE")) : 1;
-      for (int g = gmin; g <= maxg && (wide || g <= 3 * gmin + 8); ++g) {
-        const int rpg = cdiv(cdiv(R, g), 32) * 32, ga = cdiv(R, rpg);
-        if (ga != g) continue;                                 // (the rounding of the rows makes some counts unreachable)
-        const double t = cdiv(tiles * g, 256) * (rpg / 32 * 1.09 + 3.4) + g * ((double)Co * Ci * 4.0 / 4e6);
-        if (t < best_t - 1e-9) { best_t = t; best_g = g; }
-      }
-      static const int forced_env = getenv("MX_WGRAD_WS_GROUPS") ? atoi(getenv("MX_WGRAD_WS_GROUPS")) : 0;
-      const int forced_ws = g_wgrad_groups > 0 ? g_wgrad_groups : forced_env;
-      if (forced_ws > 0) best_g = forced_ws < maxg ? forced_ws : maxg;
-      p->rows_per_group = cdiv(cdiv(R, best_g), 32) * 32;
-      p->groups = cdiv(R, p->rows_per_group);
-      return true;
-    }
     int groups = (cdiv(R, 1568) + 7) / 8 * 8;
     if (groups < 16) groups = 16;
-    // few output tiles (960 x 160: 16, 480 x 80: 4 - taken by this kernel when MX_WGRAD_SPLIT_EFF admits their padding): their partial
-    // matrices are small, so the groups are what fills the chip - ~768 workgroups, at most 128 groups of at least 512 rows
-    static const int fill = getenv("MX_WGRAD_SPLIT_FILL") ? atoi(getenv("MX_WGRAD_SPLIT_FILL")) : 1;
-    const int tiles = p->tiles_co * p->tiles_ci;
-    if (fill && tiles < 48) {
+    // few output tiles (960 x 160: 16, 480 x 80: 4): their partial matrices are small, so the groups are what fills the chip - ~768
+    // workgroups, at most 128 groups of at least 512 rows
+    if (tiles < 48) {
+      constexpr int MIN_ROWS = 512;
       int want = (cdiv(768, tiles) + 7) / 8 * 8;
-      static const int minrows = getenv("MX_WGRAD_SPLIT_MINROWS") ? atoi(getenv("MX_WGRAD_SPLIT_MINROWS")) : 512;
-      const int cap = R / minrows >= 8 ? R / minrows / 8 * 8 : 8;
+      const int cap = R / MIN_ROWS >= 8 ? R / MIN_ROWS / 8 * 8 : 8;
       if (want > 128) want = 128;
       if (want > cap) want = cap;
       if (want > groups) groups = want;
     }
     if (groups > maxg) groups = maxg >= 8 ? maxg / 8 * 8 : maxg;
-    static const int forced_split = getenv("MX_WGRAD_SPLIT_GROUPS") ? atoi(getenv("MX_WGRAD_SPLIT_GROUPS")) : 0;
-    if (forced_split > 0) groups = forced_split < maxg ? forced_split : maxg;
-    if (g_wgrad_groups > 0 && x_mode == MX_PLAIN) groups = g_wgrad_groups < maxg ? g_wgrad_groups : maxg;
-    p->rows_per_group = cdiv(cdiv(R, groups), 32) * 32;
-    p->groups = cdiv(R, p->rows_per_group);
+    if (forced) groups = g_wgrad_groups < maxg ? g_wgrad_groups : maxg;
+    wt_set_groups(p, R, groups, 32);
+    p->kernel = WT_SPLIT;
     return true;
   }
-  // tile: least padded area, ties to the larger tile
+  // exact-fp32 arithmetic (mx_set_gemm_mode(0)), plain operands: wgrad_f32_ws_kernel.  Its tile is 128 x 128, or 128 x 64 / 64 x 128 where
+  // that pads less MFMA work (960 x 160, 480 x 80 and mirrors); 0.55 us per slab and 64 x 64 of tile (16 K steps x E x F MFMAs of 64 cycles
+  // per wave and slab, at the clock the chip holds: 2.15 us for the 128 x 128 tile).
+  if (g_wgrad_f32ws && mx_get_gemm_mode() == 0 && x_mode == MX_PLAIN && g_wgrad_groups <= 0) {
+    int be = 2, bf = 2;
+    long bw = (long)cdiv(Co, 128) * cdiv(Ci, 128) * 4;
+    if ((long)cdiv(Co, 128) * cdiv(Ci, 64) * 2 < bw) { bw = (long)cdiv(Co, 128) * cdiv(Ci, 64) * 2; be = 2; bf = 1; }
+    if ((long)cdiv(Co, 64) * cdiv(Ci, 128) * 2 < bw) { bw = (long)cdiv(Co, 64) * cdiv(Ci, 128) * 2; be = 1; bf = 2; }
+    p->te = 2 * be; p->tf = 2 * bf;
+    p->tiles_co = cdiv(Co, 64 * be); p->tiles_ci = cdiv(Ci, 64 * bf);
+    wt_set_groups(p, R, wt_ws_groups(R, p->tiles_co * p->tiles_ci, 0.55 * be * bf, Co, Ci), 32);
+    if (wt_ws_offsets_fit(p->rows_per_group, Co, Ci, ldg, ldx)) {
+      p->kernel = WT_F32_WS;
+      return true;
+    }
+  }
+  // tile of wgrad_tile_kernel: least padded area, ties to the larger tile
   long best = -1;
   for (int te : {4, 2})
     for (int tf : {4, 2}) {
@@ -1364,93 +1173,144 @@ static bool wt_plan(int R, int Co, int Ci, int x_mode, WtPlan* p) {
     }
   p->tiles_co = cdiv(Co, 32 * p->te); p->tiles_ci = cdiv(Ci, 32 * p->tf);
   const int tiles = p->tiles_co * p->tiles_ci;
-  // exact-fp32 arithmetic (mx_set_gemm_mode(0)), 128 x 128 tiles, plain operands: wgrad_f32_ws_kernel - one persistent workgroup per CU, so
-  // the row groups come from the same 256-slot model as the split kernel's (2.15 us per 32-row slab: 64 MFMAs of 64 cycles per wave at the
-  // clock the chip holds; 3.4 us per item; chains of 1568 rows flushed inside the kernel)
-  if (g_wgrad_f32ws && mx_get_gemm_mode() == 0 && x_mode == MX_PLAIN && g_wgrad_groups <= 0) {
-    // tile of the wave-specialised fp32 kernel: 128 x 128, or 128 x 64 / 64 x 128 where that pads less MFMA work (960 x 160, 480 x 80 and mirrors)
-    int be = 2, bf = 2;
-    long bw = (long)cdiv(Co, 128) * cdiv(Ci, 128) * 4;
-    if ((long)cdiv(Co, 128) * cdiv(Ci, 64) * 2 < bw) { bw = (long)cdiv(Co, 128) * cdiv(Ci, 64) * 2; be = 2; bf = 1; }
-    if ((long)cdiv(Co, 64) * cdiv(Ci, 128) * 2 < bw) { bw = (long)cdiv(Co, 64) * cdiv(Ci, 128) * 2; be = 1; bf = 2; }
-    p->te = 2 * be; p->tf = 2 * bf;
-    p->tiles_co = cdiv(Co, 64 * be); p->tiles_ci = cdiv(Ci, 64 * bf);
-    const int tiles = p->tiles_co * p->tiles_ci;
-    const double slab_us = 0.55 * be * bf;                   // 16 K steps x E x F MFMAs of 64 cycles per wave and slab, at the clock the chip holds
-    const int maxg = R / 128 > 0 ? R / 128 : 1;
-    int gmin = cdiv(R, 1568 * 3);
-    if (gmin > maxg) gmin = maxg;
-    int best_g = gmin;
-    double best_t = 1e30;
-    for (int g = gmin; g <= maxg; ++g) {
-      const int rpg = cdiv(cdiv(R, g), 32) * 32, ga = cdiv(R, rpg);
-      if (ga != g) continue;
-      const double t = cdiv(tiles * g, 256) * (rpg / 32 * slab_us + 3.4) + g * ((double)Co * Ci * 4.0 / 4e6);
-      if (t < best_t - 1e-9) { best_t = t; best_g = g; }
-    }
-    p->rows_per_group = cdiv(cdiv(R, best_g), 32) * 32;
-    p->groups = cdiv(R, p->rows_per_group);
-    p->f32ws = 1;
-    return true;
-  }
   // Row groups: tiles x groups should fill a whole number of residency rounds (256 CUs x 4 workgroups, 3 for the 128 x 128
   // tile with the BN+SiLU+gate prologue).  1026 workgroups on 1024 slots cost 25 % (two stragglers run alone after a full
   // round); every extra group costs a partial matrix written and read back.
-  static const int forced = getenv("MX_WGRAD_TILE_GROUPS") ? atoi(getenv("MX_WGRAD_TILE_GROUPS")) : 0;
   const int slots = 256 * ((p->te * p->tf >= 16 && x_mode == MX_BNACT) ? 3 : 4);
   const int maxg = R / 256 > 0 ? R / 256 : 1;
   int groups = 1;
   double best_score = -1.0;
-  static const int rmin = getenv("MX_WGRAD_TILE_RMIN") ? atoi(getenv("MX_WGRAD_TILE_RMIN")) : 2;    // measured in the step: 1 / 2 / 3 -> 132.7 / 131.5 / 131.6 ms
-  for (int rounds = rmin; rounds <= rmin + 2; ++rounds) {
+  constexpr int MIN_ROUNDS = 2;                               // measured in the step: 1 / 2 / 3 -> 132.7 / 131.5 / 131.6 ms
+  for (int rounds = MIN_ROUNDS; rounds <= MIN_ROUNDS + 2; ++rounds) {
     int g = slots * rounds / tiles;
     if (g < 1) g = 1;
     if (g > maxg) g = maxg;
-    if (wt_order() == 0 && g >= 8) g = g / 8 * 8;             // XCD-aware ids hand out groups eight at a time
+    if (g >= 8) g = g / 8 * 8;                                // XCD-aware ids hand out groups eight at a time
     const double fill = (double)tiles * g / ((double)slots * cdiv(tiles * g, slots));
     const double score = fill - 0.0025 * g;
     if (score > best_score + 1e-9) { best_score = score; groups = g; }
   }
-  if (forced > 0) groups = forced < maxg ? forced : maxg;
-  p->rows_per_group = cdiv(cdiv(R, groups), 16) * 16;
-  p->groups = cdiv(R, p->rows_per_group);
+  wt_set_groups(p, R, groups, 16);
+  p->kernel = WT_TILE_F32;
   return true;
 }
 
+// the plan of a contiguous launch (ldg = Co, ldx = Ci): what the queries that take no leading dimensions ask
+static bool wt_plan(int R, int Co, int Ci, int x_mode, WtPlan* p) { return wt_plan(R, Co, Ci, x_mode, false, Co, Ci, p); }
+
 template <int TE, int TF>
 static void wt_launch(const WtArgs& a, hipStream_t st) {
-  // MX_WGRAD_TILE_PERSIST = n > 0: at most 256 * n persistent workgroups (n per CU) instead of one per id - leaves wave
-  // slots and LDS to the main stream's kernels while this one runs beside them on the side stream
-  static const int persist = getenv("MX_WGRAD_TILE_PERSIST") ? atoi(getenv("MX_WGRAD_TILE_PERSIST")) : 0;
-  WtArgs b = a;
-  b.total = 8 * cdiv(a.groups, 8) * a.tiles_co * a.tiles_ci;
-  int g = b.total;
-  if (persist > 0 && g > 256 * persist) g = 256 * persist;
-  const dim3 grid(g);
-  const WtArgs& a_ = b;
-  if (a.X.mode == MX_PLAIN) hipLaunchKernelGGL((wgrad_tile_kernel<TE, TF, MX_PLAIN>), grid, dim3(256), 0, st, a_);
-  else if (a.X.mode == MX_BNACT) hipLaunchKernelGGL((wgrad_tile_kernel<TE, TF, MX_BNACT>), grid, dim3(256), 0, st, a_);
-  else hipLaunchKernelGGL((wgrad_tile_kernel<TE, TF, MX_AFFINE>), grid, dim3(256), 0, st, a_);
+  const dim3 grid(a.total);
+  if (a.X.mode == MX_PLAIN) hipLaunchKernelGGL((wgrad_tile_kernel<TE, TF, MX_PLAIN>), grid, dim3(256), 0, st, a);
+  else if (a.X.mode == MX_BNACT) hipLaunchKernelGGL((wgrad_tile_kernel<TE, TF, MX_BNACT>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((wgrad_tile_kernel<TE, TF, MX_AFFINE>), grid, dim3(256), 0, st, a);
+}
+
+// one persistent workgroup per CU (a multiple of 8 of them, fewer for a short item list) with its dynamic LDS opted in
+template <typename K>
+static int wt_launch_ws(K kernel, int lds, const WtArgs& a, hipStream_t st) {
+  const int rc = mx_dyn_lds_optin(reinterpret_cast<const void*>(kernel), lds);
+  if (rc != MX_OK) return rc;
+  const int items = a.groups * a.tiles_co * a.tiles_ci;
+  hipLaunchKernelGGL(kernel, dim3(items < 256 ? 8 * cdiv(items, 8) : 256), dim3(512), lds, st, a);
+  return MX_OK;
+}
+
+// dW[Co,Ci] += G'[R,Co]^T X'[R,Ci] by the kernel and the groups of wt_plan (G2 / gcoef: the BatchNorm fold on G; dz: that operand stored)
+static int wgrad_tile_impl(const float* G, const float* G2, const float* gcoef, const float* X, int x_mode, const float* x_scale,
+                           const float* x_shift, const float* x_gate, int rows_per_sample, float* dW, int R, int Co, int Ci, int ldg,
+                           int ldx, void* ws, long ws_bytes, void* stream, float* dz = nullptr) {
+  MX_CHECK_ARG(G && X && dW && ws, "wgrad_tile: null pointer");
+  MX_CHECK_ARG(((uintptr_t)dW & 15) == 0 && ((uintptr_t)ws & 15) == 0 && ((uintptr_t)G & 15) == 0 && ((uintptr_t)X & 15) == 0,
+               "wgrad_tile: pointers must be 16-byte aligned");
+  MX_CHECK_ARG(ldg % 4 == 0 && ldx % 4 == 0, "wgrad_tile: leading dimensions must be multiples of 4");
+  MX_CHECK_ARG(x_mode == MX_PLAIN || (x_scale && x_shift && rows_per_sample > 0), "wgrad_tile: prologue needs scale/shift");
+  WtPlan p;
+  MX_CHECK_ARG(wt_plan(R, Co, Ci, x_mode, G2 != nullptr, ldg, ldx, &p), "wgrad_tile: shape R=%d Co=%d Ci=%d not supported", R, Co, Ci);
+  MX_CHECK_ARG(!dz || p.kernel == WT_SPLIT_WS_BN, "wgrad_tile_bnbwd_dz: shape R=%d Co=%d Ci=%d not taken (mx_pw_wgrad_tile_bnbwd_dz_ok)", R, Co, Ci);
+  MX_CHECK_ARG(p.groups == 1 || ws_bytes >= (long)p.groups * Co * Ci * 4, "wgrad_tile: workspace too small");
+  WtArgs a{};
+  a.G = G; a.X = MxOperand{X, x_scale, x_shift, x_gate, x_mode, rows_per_sample};
+  a.R = R; a.Co = Co; a.Ci = Ci; a.ldg = ldg; a.ldx = ldx;
+  a.rows_per_group = p.rows_per_group; a.groups = p.groups; a.tiles_co = p.tiles_co; a.tiles_ci = p.tiles_ci;
+  a.accumulate = p.groups == 1;
+  a.total = 8 * cdiv(a.groups, 8) * a.tiles_co * a.tiles_ci;  // XCD-aware workgroup ids (a.order == 0)
+  a.G2 = G2; a.gcoef = gcoef; a.dz = dz;
+  a.part = a.accumulate ? dW : (float*)ws;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(a.total);
+  constexpr int split_ws_lds = 12 * 4 * 144 * 16, f32_ws_lds = WF32_NST * 2 * 32 * 512;
+  int rc = MX_OK;
+  switch (p.kernel) {
+    case WT_SPLIT_WS_BN: rc = wt_launch_ws(&wgrad_split_ws_kernel<true>, split_ws_lds, a, st); break;
+    case WT_SPLIT_WS: rc = wt_launch_ws(&wgrad_split_ws_kernel<false>, split_ws_lds, a, st); break;
+    case WT_SPLIT:
+      if (a.G2) hipLaunchKernelGGL((wgrad_split_kernel<MX_PLAIN, true>), grid, dim3(256), 0, st, a);
+      else if (x_mode == MX_PLAIN) hipLaunchKernelGGL((wgrad_split_kernel<MX_PLAIN, false>), grid, dim3(256), 0, st, a);
+      else if (x_mode == MX_BNACT) hipLaunchKernelGGL((wgrad_split_kernel<MX_BNACT, false>), grid, dim3(256), 0, st, a);
+      else hipLaunchKernelGGL((wgrad_split_kernel<MX_AFFINE, false>), grid, dim3(256), 0, st, a);
+      break;
+    case WT_F32_WS:
+      if (p.te == 4 && p.tf == 4) rc = wt_launch_ws(&wgrad_f32_ws_kernel<2, 2>, f32_ws_lds, a, st);
+      else if (p.te == 4) rc = wt_launch_ws(&wgrad_f32_ws_kernel<2, 1>, f32_ws_lds, a, st);
+      else rc = wt_launch_ws(&wgrad_f32_ws_kernel<1, 2>, f32_ws_lds, a, st);
+      break;
+    case WT_TILE_F32:
+      if (p.te == 4 && p.tf == 4) wt_launch<4, 4>(a, st);
+      else if (p.te == 4) wt_launch<4, 2>(a, st);
+      else if (p.tf == 4) wt_launch<2, 4>(a, st);
+      else wt_launch<2, 2>(a, st);
+      break;
+  }
+  if (rc != MX_OK) return rc;
+  MX_LAUNCH_CHECK();
+  if (!a.accumulate) {
+    hipLaunchKernelGGL(wgrad_parts_reduce_kernel, dim3(cdiv((long)Co * Ci, 64)), dim3(256), 0, st, (const float*)ws, p.groups, Co * Ci, dW);
+    MX_LAUNCH_CHECK();
+  }
+  return MX_OK;
+}
+
+// mx_pw_wgrad_small and mx_pw_wgrad_small_bnbwd (G2 / gcoef set: dZ = c1*G + c2*G2 + c3 formed in the loader)
+static int wgrad_small_impl(const float* G, const float* G2, const float* gcoef, const MxOperand& X, float* dW, int R, int Co, int Ci,
+                            int ldg, int ldx, void* ws, long ws_bytes, void* stream) {
+  MX_CHECK_ARG(G && X.p && dW && ws, "wgrad_small: null pointer");
+  MX_CHECK_ARG(((uintptr_t)dW & 15) == 0 && ((uintptr_t)ws & 15) == 0, "wgrad_small: dW / workspace must be 16-byte aligned");
+  MX_CHECK_ARG(ldg % 4 == 0 && ldx % 4 == 0, "wgrad_small: leading dimensions must be multiples of 4");
+  WgPlan p;
+  MX_CHECK_ARG(wg_plan(R, Co, Ci, &p), "wgrad_small: shape R=%d Co=%d Ci=%d not supported", R, Co, Ci);
+  MX_CHECK_ARG(ws_bytes >= (long)p.groups * Co * Ci * 4, "wgrad_small: workspace too small");
+  const WgLaunch launch = wg_dispatch(p, Co, Ci, X.mode, G2 != nullptr);
+  MX_CHECK_ARG(launch, "wgrad_small: no kernel for Co=%d Ci=%d mode=%d fold=%d (ask mx_pw_wgrad_small_ws / mx_pw_wgrad_small_bnbwd_ok first)", Co, Ci,
+               X.mode, G2 != nullptr);
+  WgArgs a{};
+  a.G = G; a.X = X; a.G2 = G2; a.gcoef = gcoef;
+  a.part = (float*)ws; a.R = R; a.Co = Co; a.Ci = Ci; a.ldg = ldg; a.ldx = ldx;
+  a.rows_per_wg = p.rows_per_wg; a.WCO = p.wco; a.WCI = p.wci; a.SG = p.SG; a.SX = p.SX;
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = launch(a, p, st);
+  if (rc != MX_OK) return rc;
+  MX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(wgrad_parts_reduce_kernel, dim3(cdiv((long)Co * Ci, 64)), dim3(256), 0, st, (const float*)ws, p.groups, Co * Ci, dW);
+  MX_LAUNCH_CHECK();
+  return MX_OK;
 }
 
 extern "C" {
 
 int mx_set_wgrad_kernel(int kernel, int groups) {
-  MX_CHECK_ARG(kernel >= -1 && kernel <= 2, "set_wgrad_kernel: kernel %d (0 first split kernel, 1 pipelined, 2 wave-specialised, -1 keep)", kernel);
+  MX_CHECK_ARG(kernel == -1 || kernel == 0 || kernel == 2, "set_wgrad_kernel: kernel %d (0 first split kernel, 2 wave-specialised, -1 keep)", kernel);
   MX_CHECK_ARG(groups >= -1, "set_wgrad_kernel: groups %d (> 0 fixed, 0 planner, -1 keep)", groups);
-  if (kernel >= 0) mx_wgrad_pipe_override = kernel;
+  if (kernel >= 0) g_wgrad_kernel = kernel;
   if (groups >= 0) g_wgrad_groups = groups;
   return MX_OK;
 }
-int mx_get_wgrad_kernel(void) { return wt_pipe_mode(); }
+int mx_get_wgrad_kernel(void) { return g_wgrad_kernel; }
 
 // bytes of scratch mx_pw_wgrad_small needs for (R, Co, Ci, x_mode), or 0 when the shape is not one it takes
 long mx_pw_wgrad_small_ws(int R, int Co, int Ci, int x_mode) {
   WgPlan p;
-  if (!wg_plan(R, Co, Ci, &p)) return 0;
-  WgArgs a{};
-  a.Co = Co; a.Ci = Ci; a.X.mode = x_mode;
-  if (!wg_dispatch(a, p, nullptr, false)) return 0;
+  if (!wg_plan(R, Co, Ci, &p) || !wg_dispatch(p, Co, Ci, x_mode, false)) return 0;
   return (long)p.groups * Co * Ci * 4;
 }
 
@@ -1459,54 +1319,23 @@ long mx_pw_wgrad_small_ws(int R, int Co, int Ci, int x_mode) {
 int mx_pw_wgrad_small(const float* G, const float* X, int x_mode, const float* x_scale, const float* x_shift,
                       const float* x_gate, int rows_per_sample, float* dW, int R, int Co, int Ci, int ldg, int ldx,
                       void* ws, long ws_bytes, void* stream) {
-  MX_CHECK_ARG(G && X && dW && ws, "wgrad_small: null pointer");
-  MX_CHECK_ARG(((uintptr_t)dW & 15) == 0 && ((uintptr_t)ws & 15) == 0, "wgrad_small: dW / workspace must be 16-byte aligned");
-  MX_CHECK_ARG(ldg % 4 == 0 && ldx % 4 == 0, "wgrad_small: leading dimensions must be multiples of 4");
   MX_CHECK_ARG(x_mode == MX_PLAIN || (x_scale && x_shift && rows_per_sample > 0), "wgrad_small: prologue needs scale/shift");
-  WgPlan p;
-  MX_CHECK_ARG(wg_plan(R, Co, Ci, &p), "wgrad_small: shape R=%d Co=%d Ci=%d not supported", R, Co, Ci);
-  MX_CHECK_ARG(ws_bytes >= (long)p.groups * Co * Ci * 4, "wgrad_small: workspace too small");
-  WgArgs a{};
-  a.G = G; a.X = MxOperand{X, x_scale, x_shift, x_gate, x_mode, rows_per_sample};
-  a.part = (float*)ws; a.R = R; a.Co = Co; a.Ci = Ci; a.ldg = ldg; a.ldx = ldx;
-  a.rows_per_wg = p.rows_per_wg; a.WCO = p.wco; a.WCI = p.wci; a.SG = p.SG; a.SX = p.SX;
-  hipStream_t st = (hipStream_t)stream;
-  MX_CHECK_ARG(wg_dispatch(a, p, st, true), "wgrad_small: no kernel for Co=%d Ci=%d mode=%d (ask mx_pw_wgrad_small_ws first)", Co, Ci, x_mode);
-  MX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(wgrad_parts_reduce_kernel, dim3(cdiv((long)Co * Ci, 64)), dim3(256), 0, st, (const float*)ws, p.groups, Co * Ci, dW);
-  MX_LAUNCH_CHECK();
-  return MX_OK;
+  return wgrad_small_impl(G, nullptr, nullptr, MxOperand{X, x_scale, x_shift, x_gate, x_mode, rows_per_sample}, dW, R, Co, Ci, ldg, ldx, ws, ws_bytes, stream);
 }
 
 // 1 when mx_pw_wgrad_small_bnbwd takes this shape (a small-output kernel with the folded G operand exists), else 0
 int mx_pw_wgrad_small_bnbwd_ok(int R, int Co, int Ci) {
   WgPlan p;
-  if (!wg_plan(R, Co, Ci, &p)) return 0;
-  WgArgs a{};
-  a.Co = Co; a.Ci = Ci; a.X.mode = MX_PLAIN; a.G2 = reinterpret_cast<const float*>(16);
-  return wg_dispatch(a, p, nullptr, false) ? 1 : 0;
+  return wg_plan(R, Co, Ci, &p) && wg_dispatch(p, Co, Ci, MX_PLAIN, true) ? 1 : 0;
 }
 
 // dW[Co,Ci] += dZ[R,Co]^T X[R,Ci] with dZ = c1*G + c2*G2 + c3 per column formed in the loader (small outputs, HBM-bound: the fold
 // saves the 2R + 1W pass that materialised dZ); scratch: mx_pw_wgrad_small_ws(R, Co, Ci, 0) bytes
 int mx_pw_wgrad_small_bnbwd(const float* G, const float* G2, const float* coef, const float* X, float* dW, int R, int Co, int Ci,
                             int ldg, int ldx, void* ws, long ws_bytes, void* stream) {
-  MX_CHECK_ARG(G && G2 && coef && X && dW && ws, "wgrad_small_bnbwd: null pointer");
-  MX_CHECK_ARG((((uintptr_t)dW | (uintptr_t)ws | (uintptr_t)G2 | (uintptr_t)coef) & 15) == 0, "wgrad_small_bnbwd: pointers must be 16-byte aligned");
-  MX_CHECK_ARG(ldg % 4 == 0 && ldx % 4 == 0, "wgrad_small_bnbwd: leading dimensions must be multiples of 4");
-  WgPlan p;
-  MX_CHECK_ARG(wg_plan(R, Co, Ci, &p), "wgrad_small_bnbwd: shape R=%d Co=%d Ci=%d not supported", R, Co, Ci);
-  MX_CHECK_ARG(ws_bytes >= (long)p.groups * Co * Ci * 4, "wgrad_small_bnbwd: workspace too small");
-  WgArgs a{};
-  a.G = G; a.X = MxOperand{X, nullptr, nullptr, nullptr, MX_PLAIN, 1}; a.G2 = G2; a.gcoef = coef;
-  a.part = (float*)ws; a.R = R; a.Co = Co; a.Ci = Ci; a.ldg = ldg; a.ldx = ldx;
-  a.rows_per_wg = p.rows_per_wg; a.WCO = p.wco; a.WCI = p.wci; a.SG = p.SG; a.SX = p.SX;
-  hipStream_t st = (hipStream_t)stream;
-  MX_CHECK_ARG(wg_dispatch(a, p, st, true), "wgrad_small_bnbwd: no kernel for Co=%d Ci=%d (mx_pw_wgrad_small_bnbwd_ok)", Co, Ci);
-  MX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(wgrad_parts_reduce_kernel, dim3(cdiv((long)Co * Ci, 64)), dim3(256), 0, st, (const float*)ws, p.groups, Co * Ci, dW);
-  MX_LAUNCH_CHECK();
-  return MX_OK;
+  MX_CHECK_ARG(G2 && coef, "wgrad_small_bnbwd: null pointer");
+  MX_CHECK_ARG((((uintptr_t)G2 | (uintptr_t)coef) & 15) == 0, "wgrad_small_bnbwd: pointers must be 16-byte aligned");
+  return wgrad_small_impl(G, G2, coef, MxOperand{X, nullptr, nullptr, nullptr, MX_PLAIN, 1}, dW, R, Co, Ci, ldg, ldx, ws, ws_bytes, stream);
 }
 
 bool mx_wgrad_uses_split(int R, int Co, int Ci) {
@@ -1514,19 +1343,17 @@ bool mx_wgrad_uses_split(int R, int Co, int Ci) {
   // 480 x 80 has a plan but no kernel, and goes to the tiled kernels
   if (mx_pw_wgrad_small_ws(R, Co, Ci, MX_PLAIN) > 0 || mx_pw_wgrad_small_ws(R, Co, Ci, MX_BNACT) > 0) return false;
   WtPlan p;
-  return wt_plan(R, Co, Ci, MX_PLAIN, &p) && wt_use_split(Co, Ci);
+  return wt_plan(R, Co, Ci, MX_PLAIN, &p) && p.kernel != WT_TILE_F32 && p.kernel != WT_F32_WS;
 }
 
-// bytes of scratch mx_pw_wgrad_tile needs (0 = shape not taken; a single row group accumulates straight into dW)
+// bytes of scratch mx_pw_wgrad_tile needs for contiguous operands (0 = shape not taken; a single row group accumulates straight into
+// dW).  Operands strided so far apart that a wave-specialised kernel cannot address them (wt_ws_offsets_fit) may plan more groups: the
+// launch then reports the workspace as too small.
 long mx_pw_wgrad_tile_ws(int R, int Co, int Ci, int x_mode) {
   WtPlan p;
   if (!wt_plan(R, Co, Ci, x_mode, &p)) return 0;
   return p.groups > 1 ? (long)p.groups * Co * Ci * 4 : 16;
 }
-
-static int wgrad_tile_impl(const float* G, const float* G2, const float* gcoef, const float* X, int x_mode, const float* x_scale,
-                           const float* x_shift, const float* x_gate, int rows_per_sample, float* dW, int R, int Co, int Ci, int ldg,
-                           int ldx, void* ws, long ws_bytes, void* stream, float* dz = nullptr);
 
 // dW[Co,Ci] += G[R,Co]^T X'[R,Ci], large outputs: tiled, deterministic (partial tiles per row group, fixed-order reduce).
 int mx_pw_wgrad_tile(const float* G, const float* X, int x_mode, const float* x_scale, const float* x_shift,
@@ -1535,7 +1362,7 @@ int mx_pw_wgrad_tile(const float* G, const float* X, int x_mode, const float* x_
   return wgrad_tile_impl(G, nullptr, nullptr, X, x_mode, x_scale, x_shift, x_gate, rows_per_sample, dW, R, Co, Ci, ldg, ldx, ws, ws_bytes, stream);
 }
 
-// 1 when mx_pw_wgrad_tile_bnbwd takes this shape in the current mode (the split-arithmetic tiled kernel), else 0
+// 1 when mx_pw_wgrad_tile_bnbwd takes this shape in the current mode (a split-arithmetic tiled kernel), else 0
 int mx_pw_wgrad_tile_bnbwd_ok(int R, int Co, int Ci) { return mx_wgrad_uses_split(R, Co, Ci) ? 1 : 0; }
 
 // dW[Co,Ci] += dZ[R,Co]^T X[R,Ci] with dZ = c1*G + c2*G2 + c3 per column (coef = [3][Co], as mx_bn_bwd_finalize leaves it) formed in
@@ -1545,15 +1372,14 @@ int mx_pw_wgrad_tile_bnbwd(const float* G, const float* G2, const float* coef, c
                            int ldg, int ldx, void* ws, long ws_bytes, void* stream) {
   MX_CHECK_ARG(G2 && coef, "wgrad_tile_bnbwd: null pointer");
   MX_CHECK_ARG((((uintptr_t)G2 | (uintptr_t)coef) & 15) == 0, "wgrad_tile_bnbwd: pointers must be 16-byte aligned");
-  MX_CHECK_ARG(mx_wgrad_uses_split(R, Co, Ci), "wgrad_tile_bnbwd: shape R=%d Co=%d Ci=%d is not one the split kernel takes (mx_pw_wgrad_tile_bnbwd_ok)", R, Co, Ci);
+  MX_CHECK_ARG(mx_wgrad_uses_split(R, Co, Ci), "wgrad_tile_bnbwd: shape R=%d Co=%d Ci=%d is not one the split kernels take (mx_pw_wgrad_tile_bnbwd_ok)", R, Co, Ci);
   return wgrad_tile_impl(G, G2, coef, X, MX_PLAIN, nullptr, nullptr, nullptr, 1, dW, R, Co, Ci, ldg, ldx, ws, ws_bytes, stream);
 }
 
 // 1 when mx_pw_wgrad_tile_bnbwd_dz can leave dZ for this shape (the wave-specialised kernel takes it), else 0
 int mx_pw_wgrad_tile_bnbwd_dz_ok(int R, int Co, int Ci, int ldg, int ldx) {
   WtPlan p;
-  if (!mx_wgrad_uses_split(R, Co, Ci) || wt_pipe_mode() < 2 || !wt_plan(R, Co, Ci, MX_PLAIN, &p)) return 0;
-  return (((long)p.rows_per_group + 96) * (ldg > ldx ? ldg : ldx) * 4 < (1l << 30) && (long)Co * Ci * 4 < (1l << 30)) ? 1 : 0;
+  return mx_wgrad_uses_split(R, Co, Ci) && wt_plan(R, Co, Ci, MX_PLAIN, true, ldg, ldx, &p) && p.kernel == WT_SPLIT_WS_BN ? 1 : 0;
 }
 
 // The same, and dZ[R, ldg] = c1*G + c2*G2 + c3 is also WRITTEN (round 5): the weight gradient runs FIRST and its loader waves leave the
@@ -1569,84 +1395,3 @@ int mx_pw_wgrad_tile_bnbwd_dz(const float* G, const float* G2, const float* coef
 }
 
 }  // extern "C"
-
-static int wgrad_tile_impl(const float* G, const float* G2, const float* gcoef, const float* X, int x_mode, const float* x_scale,
-                           const float* x_shift, const float* x_gate, int rows_per_sample, float* dW, int R, int Co, int Ci, int ldg,
-                           int ldx, void* ws, long ws_bytes, void* stream, float* dz) {
-  MX_CHECK_ARG(G && X && dW && ws, "wgrad_tile: null pointer");
-  MX_CHECK_ARG(((uintptr_t)dW & 15) == 0 && ((uintptr_t)ws & 15) == 0 && ((uintptr_t)G & 15) == 0 && ((uintptr_t)X & 15) == 0,
-               "wgrad_tile: pointers must be 16-byte aligned");
-  MX_CHECK_ARG(ldg % 4 == 0 && ldx % 4 == 0, "wgrad_tile: leading dimensions must be multiples of 4");
-  MX_CHECK_ARG(x_mode == MX_PLAIN || (x_scale && x_shift && rows_per_sample > 0), "wgrad_tile: prologue needs scale/shift");
-  WtPlan p;
-  MX_CHECK_ARG(wt_plan(R, Co, Ci, x_mode, &p), "wgrad_tile: shape R=%d Co=%d Ci=%d not supported", R, Co, Ci);
-  MX_CHECK_ARG(p.groups == 1 || ws_bytes >= (long)p.groups * Co * Ci * 4, "wgrad_tile: workspace too small");
-  WtArgs a{};
-  a.G = G; a.X = MxOperand{X, x_scale, x_shift, x_gate, x_mode, rows_per_sample};
-  a.R = R; a.Co = Co; a.Ci = Ci; a.ldg = ldg; a.ldx = ldx;
-  a.rows_per_group = p.rows_per_group; a.groups = p.groups; a.tiles_co = p.tiles_co; a.tiles_ci = p.tiles_ci;
-  a.accumulate = p.groups == 1;
-  a.order = wt_order();
-  a.G2 = G2; a.gcoef = gcoef; a.dz = dz;
-  a.part = a.accumulate ? dW : (float*)ws;
-  hipStream_t st = (hipStream_t)stream;
-  if (wt_use_split(Co, Ci)) {
-    const dim3 grid(8 * cdiv(a.groups, 8) * a.tiles_co * a.tiles_ci);
-    a.total = grid.x;
-    // experiment knob: unused dynamic LDS caps the kernel's workgroups per CU (32 KB -> 2 per CU, 64 KB -> 1), leaving wave slots
-    // and registers to the main stream's kernels it runs beside
-    static const int pad = getenv("MX_WGRAD_SPLIT_LDS_PAD") ? atoi(getenv("MX_WGRAD_SPLIT_LDS_PAD")) : 0;
-    // the pipelined kernel addresses a group through 32-bit buffer offsets: (rows + 64) * ld * 4 bytes must stay far below 2^31
-    const int pipe = wt_pipe_mode();
-    // (and the partial tile is stored through 32-bit buffer offsets as well: Co x Ci x 4 bytes)
-    const bool pipe_ok = pipe && !a.G2 && a.X.mode == MX_PLAIN && ((long)a.rows_per_group + 96) * (a.ldg > a.ldx ? a.ldg : a.ldx) * 4 < (1l << 30) &&
-                         (long)a.Co * a.Ci * 4 < (1l << 30);
-    const bool ws_gbn = pipe >= 2 && a.G2 && a.X.mode == MX_PLAIN && ((long)a.rows_per_group + 96) * (a.ldg > a.ldx ? a.ldg : a.ldx) * 4 < (1l << 30) &&
-                        (long)a.Co * a.Ci * 4 < (1l << 30);
-    MX_CHECK_ARG(!a.dz || ws_gbn, "wgrad_tile_bnbwd: the dZ output exists in the wave-specialised kernel only (mx_set_wgrad_kernel 2, rows per group x ld < 2^28)");
-    if (ws_gbn) {
-      static const int once = (hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_split_ws_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 12 * 4 * 144 * 16), 0);
-      (void)once;
-      const int items = a.groups * a.tiles_co * a.tiles_ci;
-      hipLaunchKernelGGL(wgrad_split_ws_kernel<true>, dim3(items < 256 ? 8 * cdiv(items, 8) : 256), dim3(512), 12 * 4 * 144 * 16, st, a);
-    } else if (pipe_ok && pipe >= 2) {
-      static const int once = (hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_split_ws_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 12 * 4 * 144 * 16), 0);
-      (void)once;
-      const int items = a.groups * a.tiles_co * a.tiles_ci;
-      hipLaunchKernelGGL(wgrad_split_ws_kernel<false>, dim3(items < 256 ? 8 * cdiv(items, 8) : 256), dim3(512), 12 * 4 * 144 * 16, st, a);
-    } else if (pipe_ok) {
-      static const int once = (hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_split_pipe_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 12 * 4 * 144 * 16), 0);
-      (void)once;
-      hipLaunchKernelGGL(wgrad_split_pipe_kernel, grid, dim3(256), 12 * 4 * 144 * 16, st, a);
-    } else if (a.G2) hipLaunchKernelGGL((wgrad_split_kernel<MX_PLAIN, true>), grid, dim3(256), 0, st, a);
-    else if (a.X.mode == MX_PLAIN) hipLaunchKernelGGL((wgrad_split_kernel<MX_PLAIN, false>), grid, dim3(256), pad, st, a);
-    else if (a.X.mode == MX_BNACT) hipLaunchKernelGGL((wgrad_split_kernel<MX_BNACT, false>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((wgrad_split_kernel<MX_AFFINE, false>), grid, dim3(256), 0, st, a);
-  } else if (p.f32ws && ((long)a.rows_per_group + 96) * (a.ldg > a.ldx ? a.ldg : a.ldx) * 4 < (1l << 30) && (long)a.Co * a.Ci * 4 < (1l << 30)) {
-    const int items = a.groups * a.tiles_co * a.tiles_ci;
-    const dim3 grid(items < 256 ? 8 * cdiv(items, 8) : 256);
-    constexpr int lds = WF32_NST * 2 * 32 * 512;
-    if (p.te == 4 && p.tf == 4) {
-      static const int once = (hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_f32_ws_kernel<2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds), 0);
-      (void)once;
-      hipLaunchKernelGGL((wgrad_f32_ws_kernel<2, 2>), grid, dim3(512), lds, st, a);
-    } else if (p.te == 4) {
-      static const int once = (hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_f32_ws_kernel<2, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds), 0);
-      (void)once;
-      hipLaunchKernelGGL((wgrad_f32_ws_kernel<2, 1>), grid, dim3(512), lds, st, a);
-    } else {
-      static const int once = (hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_f32_ws_kernel<1, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds), 0);
-      (void)once;
-      hipLaunchKernelGGL((wgrad_f32_ws_kernel<1, 2>), grid, dim3(512), lds, st, a);
-    }
-  } else if (p.te == 4 && p.tf == 4) wt_launch<4, 4>(a, st);
-  else if (p.te == 4) wt_launch<4, 2>(a, st);
-  else if (p.tf == 4) wt_launch<2, 4>(a, st);
-  else wt_launch<2, 2>(a, st);
-  MX_LAUNCH_CHECK();
-  if (!a.accumulate) {
-    hipLaunchKernelGGL(wgrad_parts_reduce_kernel, dim3(cdiv((long)Co * Ci, 64)), dim3(256), 0, st, (const float*)ws, p.groups, Co * Ci, dW);
-    MX_LAUNCH_CHECK();
-  }
-  return MX_OK;
-}

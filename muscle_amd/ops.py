@@ -139,7 +139,7 @@ def get_gemm_mode() -> int:
 
 def set_wgrad_kernel(kernel: int = -1, groups: int = -1):
     """Which kernel takes the plain-operand split weight gradients (include/muscle_hip.h, mx_set_wgrad_kernel): 0 = the first split
-    kernel, 1 = the single-stream pipeline, 2 = the wave-specialised persistent kernel (default); `groups` > 0 fixes their row groups
+    kernel, 2 = the wave-specialised persistent kernel (default); `groups` > 0 fixes their row groups
     (0 = planner).  -1 leaves a setting as it is.  Tests and measurement only."""
     call("mx_set_wgrad_kernel", int(kernel), int(groups))
 

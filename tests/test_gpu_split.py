@@ -300,9 +300,8 @@ def test_split_wgrad_matches_fp64_as_well_as_fp32_mfma(R, Co, Ci, mode):
 @pytest.mark.parametrize("R,Co,Ci,groups", [(25088, 384, 2304, 16), (12544 + 7, 1344, 224, 9), (5003, 640, 384, 4), (3136, 256, 132, 2), (1536, 256, 256, 1),
                                               (6272, 2304, 384, 5)])
 def test_wgrad_kernels_of_round_5_equal_the_first_split_kernel_bit_for_bit(R, Co, Ci, groups):
-    """wgrad_split_pipe_kernel (one software-pipelined stream) and wgrad_split_ws_kernel (4 MFMA waves + 4 loader waves, persistent)
-    keep the first split kernel's tiles, MFMA order and fixed-order sum of the row groups: with the group count held equal the three
-    give the same bits - on ragged row counts (the last slab and the last group are short) and on outputs that pad their tiles.  The
+    """wgrad_split_ws_kernel (4 MFMA waves + 4 loader waves, persistent) keeps the first split kernel's tiles, MFMA order and
+    fixed-order sum of the row groups: with the group count held equal (groups of at most 1568 rows) the two give the same bits - on ragged row counts (the last slab and the last group are short) and on outputs that pad their tiles.  The
     fp64 bound of the planner's own group count is test_split_wgrad_matches_fp64_as_well_as_fp32_mfma's."""
     import muscle_amd
     from muscle_amd import ops
@@ -314,7 +313,7 @@ def test_wgrad_kernels_of_round_5_equal_the_first_split_kernel_bit_for_bit(R, Co
     was = ops.get_wgrad_kernel()
     outs = []
     try:
-        for kern in (0, 1, 2):
+        for kern in (0, 2):
             ops.set_wgrad_kernel(kern, groups)
             dW = base.clone()
             ops.pw_wgrad(G, X, dW)
@@ -322,9 +321,9 @@ def test_wgrad_kernels_of_round_5_equal_the_first_split_kernel_bit_for_bit(R, Co
     finally:
         ops.set_wgrad_kernel(was, 0)
         muscle_amd.set_gemm_mode(0)
-    assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
+    assert torch.equal(outs[0], outs[1])
     ref = base.double() + G.double().t() @ X.double()
-    assert (outs[2].double() - ref).abs().max().item() <= 3e-5 * ref.abs().max().item()
+    assert (outs[1].double() - ref).abs().max().item() <= 3e-5 * ref.abs().max().item()
 
 
 @pytest.mark.parametrize("M,K,N", [(25088, 960, 160), (12544 + 5, 2304, 384), (6272, 1344, 224), (3136 * 3, 3840, 640)])

@@ -379,8 +379,7 @@ static int run_wgradf32(int R, int Co, int Ci) {
   return 0;
 }
 
-static int wlab_mode() { return getenv("WLAB_MODE") ? atoi(getenv("WLAB_MODE")) : 2; }
-// wgrad [R Co Ci]: the first split weight-gradient kernel against the round-5 ones (WLAB_MODE = 1 single-stream pipeline, 2 wave-specialised), same process: time, bits
+// wgrad [R Co Ci]: the first split weight-gradient kernel against the wave-specialised one (mx_set_wgrad_kernel 0 / 2), same process: time, bits
 static int run_wgrad(int R, int Co, int Ci) {
   if (!ws) CK(hipMalloc(&ws, ws_bytes));
   float* G = dalloc((long)R * Co, 11, 1.f); float* X = dalloc((long)R * Ci, 12, 1.f);
@@ -389,7 +388,7 @@ static int run_wgrad(int R, int Co, int Ci) {
   const double fl = 2.0 * R * Co * Ci;
   float t[2];
   for (int v = 0; v < 2; ++v) {
-    mx_wgrad_pipe_override = v ? wlab_mode() : 0;
+    mx_set_wgrad_kernel(v ? 2 : 0, -1);
     float* d = v ? d1 : d0;
     CK(hipMemset(d, 0, (long)Co * Ci * 4));
     if (mx_pw_wgrad_tile(G, X, 0, nullptr, nullptr, nullptr, 1, d, R, Co, Ci, Co, Ci, ws, ws_bytes, nullptr)) { printf("error: %s\n", mx_last_error()); return 1; }
@@ -399,23 +398,22 @@ static int run_wgrad(int R, int Co, int Ci) {
       best = std::min(best, time_us([&] { mx_pw_wgrad_tile(G, X, 0, nullptr, nullptr, nullptr, 1, d, R, Co, Ci, Co, Ci, ws, ws_bytes, nullptr); }, 5));
     t[v] = best;
   }
-  mx_wgrad_pipe_override = -1;
+  mx_set_wgrad_kernel(2, -1);
   // bits: one fresh call each into zeroed outputs
   std::vector<float> h0((long)Co * Ci), h1((long)Co * Ci);
   for (int v = 0; v < 2; ++v) {
-    mx_wgrad_pipe_override = v ? wlab_mode() : 0;
+    mx_set_wgrad_kernel(v ? 2 : 0, -1);
     float* d = v ? d1 : d0;
     CK(hipMemset(d, 0, (long)Co * Ci * 4));
     mx_pw_wgrad_tile(G, X, 0, nullptr, nullptr, nullptr, 1, d, R, Co, Ci, Co, Ci, ws, ws_bytes, nullptr);
     CK(hipMemcpy((v ? h1 : h0).data(), d, (long)Co * Ci * 4, hipMemcpyDeviceToHost));
   }
-  mx_wgrad_pipe_override = -1;
+  mx_set_wgrad_kernel(2, -1);
 #ifdef WPIPE_STAMPS
   {
     const long nwg = 1 << 16;
     unsigned long long* st; CK(hipMalloc(&st, nwg * 8 * sizeof(unsigned long long))); CK(hipMemset(st, 0, nwg * 8 * sizeof(unsigned long long)));
     CK(hipMemcpyToSymbol(HIP_SYMBOL(wpipe_stamps), &st, sizeof(st)));
-    mx_wgrad_pipe_override = wlab_mode();
     for (int i = 0; i < 200; ++i) mx_pw_wgrad_tile(G, X, 0, nullptr, nullptr, nullptr, 1, d1, R, Co, Ci, Co, Ci, ws, ws_bytes, nullptr);     // the clock the chip HOLDS
     CK(hipDeviceSynchronize());
     std::vector<unsigned long long> h(nwg * 8);
@@ -432,13 +430,12 @@ static int run_wgrad(int R, int Co, int Ci) {
     printf("    stamps: %zu workgroups, %d slabs each: loop %.0f cycles = %.1f per slab (%.1f per MFMA), prologue %.0f, whole %.0f, clock %.2f GHz\n", loop.size(), ns,
            med(loop), med(loop) / ns, med(loop) / ns / 48, med(pro), med(tot), med(ghz));
     unsigned long long* z = nullptr; CK(hipMemcpyToSymbol(HIP_SYMBOL(wpipe_stamps), &z, sizeof(z)));
-    mx_wgrad_pipe_override = -1;
     CK(hipFree(st));
   }
 #endif
   double md = 0, mx = 0;
   for (long i = 0; i < (long)Co * Ci; ++i) { md = std::max(md, (double)fabsf(h0[i] - h1[i])); mx = std::max(mx, (double)fabsf(h0[i])); }
-  printf("  R=%d Co=%d Ci=%d: v1 %7.1f us %6.1f TF | pipe %7.1f us %6.1f TF | max|d| = %g (max|v1| = %g)\n", R, Co, Ci, t[0], fl / t[0] / 1e6, t[1],
+  printf("  R=%d Co=%d Ci=%d: v1 %7.1f us %6.1f TF | ws %7.1f us %6.1f TF | max|d| = %g (max|v1| = %g)\n", R, Co, Ci, t[0], fl / t[0] / 1e6, t[1],
          fl / t[1] / 1e6, md, mx);
   fflush(stdout);
   for (float* p : {G, X, d0, d1}) CK(hipFree(p));
