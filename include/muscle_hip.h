@@ -633,6 +633,39 @@ int mx_resize_planar_halfpixel(const float* src, float* dst, int C, int Hs, int 
 int mx_irn_net_finish(const float* e, int lde, const float* d, int ldd, const float* mean, int Hf, int Wf, int h, int w, float* edge,
                       float* dp, void* stream);
 
+/* ---- training the IRN heads (src/backbones/resnet50_irn.py:143-212, AffinityDisplacementLoss; csrc/irn_train.hip).  The backbone is
+ * frozen (:109-114 detach every stage, :138-140), so only the loss head and the twelve 1x1-conv + GroupNorm heads have a backward.
+ * Fixed summation order, fp64 loss sums, no floating-point atomics: two steps from the same state give the same bits. */
+
+/* The loss head, forward (:204-212 + the combination of the public IRN training loop, which the reference does not ship).
+ * E [N,H,W] logits with leading dimension lde (fc_edge6's 4-column GEMM output), D [N,H,W,2] with leading dimension ldd, label uint8
+ * [N,H,W] (0..20, 255 = ignore): the affinity labels of src/data.py:611-637 are derived per pair, never stored.  Path table of
+ * indexing.PathIndex(radius, (H,W)) as offsets: pts[2*(poff[d]+k)] = (dy,dx) of point k of path d (point 0 = the destination,
+ * 0 <= dy <= radius-1, |dx| <= radius-1), plen[d] points, nd paths (:153-159, to_affinity :161-174, to_pair_displacement :176-192).
+ * Sources are the (H-rf) x (W-2rf) window, rf = radius-1.  amax [N,nd,(H-rf)*(W-2rf)] bytes: position of the path maximum (first wins).
+ * res[16] doubles: {pos_aff, neg_aff, dp_fg, dp_bg, total, n_bg, n_fg, n_neg, 5 backward coefficients, 0...} with
+ * pos_aff = S(bg*pos)/(n_bg+1e-5)/2 + S(fg*pos)/(n_fg+1e-5)/2, neg_aff = S(neg*neg)/(n_neg+1e-5), dp_fg = S(fg*|pd-dst|)/(2 n_fg+1e-5),
+ * dp_bg = S(bg*|pd|)/(2 n_bg+1e-5), total = (pos_aff+neg_aff)/2 + (dp_fg+dp_bg)/2.  ws: mx_irn_loss_ws bytes.  radius <= 16. */
+long mx_irn_loss_ws(int N, int H, int W, int radius);
+int mx_irn_loss_fwd(const float* E, int lde, const float* D, int ldd, const unsigned char* label, const int* pts, const int* poff,
+                    const int* plen, int nd, int radius, int N, int H, int W, unsigned char* amax, void* ws, long ws_bytes, double* res,
+                    void* stream);
+/* Backward of `total` as a gather: dE [N*H*W,4] (column 0 = d total / d E, columns 1-3 zero), dD [N*H*W,4] (columns 0,1), the
+ * operands of the 4-row data- and weight-gradient GEMMs of fc_edge6 and fc_dp7's last convolution. */
+int mx_irn_loss_bwd(const float* E, int lde, const float* D, int ldd, const unsigned char* label, const int* pts, const int* poff,
+                    const int* plen, int nd, int radius, int N, int H, int W, const unsigned char* amax, const double* res, float* dE,
+                    float* dD, void* stream);
+
+/* Adjoint of mx_gn_resize (:32-37,118-120): gdst = gradient of the concatenation [N,Hd,Wd,ldd], fdst = the stored forward
+ * concatenation (ReLU mask: > 0), slice [coff, coff+C); dY [N,Hs,Ws,C] = gradient at the GroupNorm output. */
+int mx_gn_resize_bwd(const float* gdst, const float* fdst, float* dY, int N, int Hs, int Ws, int C, int scale, int Hd, int Wd, int ldd,
+                     int coff, void* stream);
+/* nn.GroupNorm(G, C) backward on X [N,HW,C] (the 1x1 convolution's output) with stat from mx_gn_stats: dX (may alias dY), dgamma[C],
+ * dbeta[C] (written, not added).  fp64 sums in a fixed order.  ws: mx_gn_bwd_ws bytes.  C % 32 == 0, (C/G) % 4 == 0. */
+long mx_gn_bwd_ws(int N, int HW, int C, int G);
+int mx_gn_bwd(const float* dY, const float* X, const float* stat, const float* gamma, int N, int HW, int C, int G, void* ws, long ws_bytes,
+              float* dX, float* dgamma, float* dbeta, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

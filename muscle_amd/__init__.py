@@ -22,3 +22,5 @@ from .graph import GraphedStep  # noqa: F401,E402
 from .ops import get_gemm_mode, set_gemm_mode  # noqa: F401,E402
 from . import data  # noqa: F401,E402  (input path: two-view sampler + device-side color_norm / crop stage)
 from .irn import EdgeDisplacement  # noqa: F401,E402  (the IRN edge / displacement network of infer_irn.py)
+from .irn import AffinityDisplacementLoss, irn_step  # noqa: F401,E402  (training the IRN heads; script: muscle_amd.train_irn)
+from .optim import PolyOptimizer  # noqa: F401,E402

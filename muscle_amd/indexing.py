@@ -90,3 +90,42 @@ def finish_semseg(rw: torch.Tensor, H: int, W: int, bg_thres: float, soft_output
     scratch = torch.empty(1, dtype=torch.int32, device=rw.device)
     call("mx_irn_finish", ptr(r), C, h, w, H, W, float(bg_thres), ptr(scratch), ptr(label), ptr(soft), stream())
     return (label, soft) if soft_output else label
+
+
+class PathIndex:
+    """src/indexing.py:5-74 for any integer radius and any (H, W): `search_paths` (arrays [n_paths, length, 2] grouped by path
+    length), `search_dst` [n_dst, 2] as (dy, dx), and the flat index arrays `path_indices` / `src_indices` / `dst_indices` over the
+    (H - rf) x (W - 2 rf) source window, rf = radius - 1.  The kernels use the offsets (`offsets_table`), the flat arrays exist for
+    AffinityDisplacementLoss's `path_indices{i}` buffers, which a reference checkpoint carries."""
+
+    def __init__(self, radius: int, default_size):
+        self.radius = int(radius)
+        self.radius_floor = int(np.ceil(radius) - 1)
+        self.size = (int(default_size[0]), int(default_size[1]))
+        paths = search_paths(self.radius)
+        by_len = {}
+        for p in paths:
+            by_len.setdefault(len(p), []).append(p)
+        self.search_paths = [np.asarray(by_len[k]) for k in sorted(by_len)]
+        self.search_dst = np.concatenate([p[:, 0] for p in self.search_paths], axis=0)
+        H, W = self.size
+        rf = self.radius_floor
+        ch, cw = H - rf, W - 2 * rf
+        if ch <= 0 or cw <= 0:
+            raise ValueError(f"PathIndex: a {H}x{W} map has no source window at radius {radius}")
+        full = np.arange(H * W, dtype=np.int64).reshape(H, W)
+        self.path_indices = [np.array([[full[dy:dy + ch, rf + dx:rf + dx + cw].reshape(-1) for dy, dx in p] for p in grp])
+                             for grp in self.search_paths]
+        self.src_indices = full[:ch, rf:rf + cw].reshape(-1)
+        self.dst_indices = np.concatenate([p[:, 0] for p in self.path_indices], axis=0)
+
+    def offsets_table(self, device):
+        """(pts int32 [2 * points], poff int32 [n_dst], plen int32 [n_dst], n_dst) on the device, paths in search_dst's order."""
+        flat = [p for grp in self.search_paths for p in grp]
+        pc = np.array([c for p in flat for c in p], np.int32).reshape(-1, 2)
+        rf = self.radius_floor
+        if pc[:, 0].min() < 0 or pc[:, 0].max() > rf or np.abs(pc[:, 1]).max() > rf:
+            raise MuscleHipError("PathIndex: a path point leaves the halo the loss kernels stage")
+        ln = np.array([len(p) for p in flat], np.int32)
+        off = np.concatenate([[0], np.cumsum(ln)[:-1]]).astype(np.int32)
+        return tuple(torch.from_numpy(a).to(device) for a in (pc.reshape(-1).copy(), off, ln)) + (len(flat),)

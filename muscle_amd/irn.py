@@ -8,7 +8,7 @@ times (resnet50.* / stage1..5.* / backbone.*, fc_edge* / edge_layers.*, fc_dp* /
 its checkpoints carry every tensor under two or three names; the containers here are shared in the same way, which gives
 the same state_dict() key set and lets such a checkpoint load under strict=True.
 
-Forward (inference only, NHWC fp32): stem = mx_stem7_im2col + the 1x1 GEMM with the folded BatchNorm + ReLU, mx_maxpool3s2;
+Forward (NHWC fp32): stem = mx_stem7_im2col + the 1x1 GEMM with the folded BatchNorm + ReLU, mx_maxpool3s2;
 every bottleneck = GEMM, mx_conv3x3_fwd, GEMM with `+ residual, relu` in its epilogue (stride-2 down-sample branches read
 their rows through mx_gather_s2); every head = GEMM, mx_gn_stats, mx_gn_resize straight into its slice of the
 concatenation; mx_irn_net_finish.  The 1x1 GEMMs follow the GEMM arithmetic mode, the 3x3 convolution is exact fp32.
@@ -214,8 +214,8 @@ class EdgeDisplacement(nn.Module):
         o = _pw(x.view(-1, C), hd["w"], hd["co"]).view(N, H, W, hd["co"])
         ops.gn_resize(o, ops.gn_stats(o, hd["g"], hd["eps"]), hd["gamma"], hd["beta"], dst, coff, scale, relu=True)
 
-    def features(self, x: torch.Tensor):
-        """resnet50_irn.py:109-130 on the zero-padded frame, NHWC: ([x1..x5], edge_cat, dp_cat1, dp_cat2)."""
+    def stages(self, x: torch.Tensor):
+        """resnet50_irn.py:110-114 on the zero-padded frame, NHWC: [x1..x5] of the frozen, folded backbone."""
         p = self._prep or self.prepare()
         if x.dim() != 4 or x.shape[1] != 3 or not x.is_cuda:
             raise MuscleHipError("EdgeDisplacement.forward takes a CUDA [N,3,H,W] tensor")
@@ -232,6 +232,13 @@ class EdgeDisplacement(nn.Module):
             for d in blocks:
                 h = self._bottleneck(h, d)
             xs.append(h)
+        return xs
+
+    def features(self, x: torch.Tensor):
+        """resnet50_irn.py:109-130 on the zero-padded frame, NHWC: ([x1..x5], edge_cat, dp_cat1, dp_cat2)."""
+        p = self._prep or self.prepare()
+        xs = self.stages(x)
+        N = x.shape[0]
         dev = x.device
         _, h2, w2, _ = xs[1].shape
         _, h3, w3, _ = xs[2].shape
@@ -250,7 +257,7 @@ class EdgeDisplacement(nn.Module):
     def forward(self, x: torch.Tensor):
         """x: the [2,3,H,W] pair (image, flipped image).  Returns (edge [1,h,w], dp [2,h,w]), h = (H-1)//stride + 1, on the device."""
         if self.training:
-            raise MuscleHipError("EdgeDisplacement is inference only (the reference ships no IRN training script): call .eval()")
+            raise MuscleHipError("EdgeDisplacement is the inference network: call .eval(), or train the heads with AffinityDisplacementLoss / irn_step")
         if x.shape[0] != 2:
             raise ValueError("EdgeDisplacement.forward takes the pair [image, flipped image] (resnet50_irn.py:229)")
         with torch.no_grad():
@@ -265,6 +272,177 @@ class EdgeDisplacement(nn.Module):
             self._head(cat2, p["dp"][6], o7, 0, 1)
             do = ops.pw_fwd(o7.view(-1, 256), p["dp7_w"], 4).view(N, h2, w2, 4)
             return ops.irn_net_finish(eo, do, p["mean"], fh, fw)
+
+
+class AffinityDisplacementLoss(EdgeDisplacement):
+    """resnet50_irn.py:143-212 on the HIP path: the network with its loss head, for training the twelve 1x1-conv + GroupNorm heads,
+    fc_edge6 and the tail of fc_dp7.  Same containers and state_dict() keys as the reference class (the `path_indices{i}` and
+    `disp_target` buffers included), so a checkpoint saved here loads into EdgeDisplacement with strict=False as infer_irn.py:41
+    loads the reference's.
+
+    The backbone stays frozen and folded (:109-114 detach every stage, :138-140 keep it in eval()): train() / eval() do not drop
+    the folded weights, load_state_dict() and .to() do.  The head parameters are read live on every call.  The unreduced loss
+    tensors of the reference's forward(x, True) do not exist here: `loss_backward` returns the four reduced terms and the total
+    (the combination of the public IRN training loop; include/muscle_hip.h, mx_irn_loss_fwd) and leaves the gradients in .grad."""
+
+    path_indices_prefix = "path_indices"
+
+    def __init__(self, path_index, crop_size: int = 512):
+        super().__init__(crop_size=crop_size)
+        self.path_index = path_index
+        self.n_path_lengths = len(path_index.path_indices)
+        for i, pi in enumerate(path_index.path_indices):
+            self.register_buffer(self.path_indices_prefix + str(i), torch.from_numpy(pi))
+        self.register_buffer("disp_target", torch.from_numpy(path_index.search_dst).transpose(1, 0).unsqueeze(0).unsqueeze(-1).float())
+        self._table = None
+        self.train()
+
+    def train(self, mode: bool = True):                                  # :138-140, without dropping the folded backbone
+        nn.Module.train(self, mode)
+        self.backbone.eval()
+        return self
+
+    def _apply(self, fn, *a, **k):
+        self._table = None
+        return super()._apply(fn, *a, **k)
+
+    def trainable_parameters(self):                                      # :134-136
+        return tuple(self.edge_layers.parameters()), tuple(self.dp_layers.parameters())
+
+    # -- forward with the live head parameters; keeps what the backward needs --------------------------------------------
+    @staticmethod
+    def _live_head(x, seq, dst, coff, scale):
+        conv, gn = seq[0], seq[1]
+        N, H, W, C = x.shape
+        co = conv.out_channels
+        o = _pw(x.view(-1, C), _chunks(conv.weight.detach().reshape(co, -1)), co).view(N, H, W, co)
+        stat = ops.gn_stats(o, gn.num_groups, gn.eps)
+        ops.gn_resize(o, stat, gn.weight.detach(), gn.bias.detach(), dst, coff, scale, relu=True)
+        return dict(seq=seq, x=x, o=o, stat=stat, dst=dst, coff=coff, scale=scale)
+
+    def _run(self, x: torch.Tensor):
+        xs = self.stages(x)
+        N, dev = x.shape[0], x.device
+        _, h2, w2, _ = xs[1].shape
+        _, h3, w3, _ = xs[2].shape
+        ecat = torch.empty(N, h2, w2, 160, dtype=torch.float32, device=dev)
+        cat1 = torch.empty(N, h3, w3, 768, dtype=torch.float32, device=dev)
+        cat2 = torch.empty(N, h2, w2, 448, dtype=torch.float32, device=dev)
+        o7 = torch.empty(N, h2, w2, 256, dtype=torch.float32, device=dev)
+        ctx = {"edge": [self._live_head(xs[i], getattr(self, f"fc_edge{i + 1}"), ecat, 32 * i, _EDGE_UP[i]) for i in range(5)]}
+        dp = [None] * 7
+        for j, i in enumerate((2, 3, 4)):
+            dp[i] = self._live_head(xs[i], getattr(self, f"fc_dp{i + 1}"), cat1, 256 * j, _DP_UP[i])
+        dp[0] = self._live_head(xs[0], self.fc_dp1, cat2, 0, 1)
+        dp[1] = self._live_head(xs[1], self.fc_dp2, cat2, 64, 1)
+        dp[5] = self._live_head(cat1, self.fc_dp6, cat2, 192, _DP_UP[5])
+        dp[6] = self._live_head(cat2, self.fc_dp7, o7, 0, 1)
+        we = torch.zeros(4, 160, device=dev)                              # the 1- and 2-channel tails as 4-column GEMMs (zero rows)
+        we[:1] = self.fc_edge6.weight.detach().reshape(1, 160)
+        be = torch.zeros(4, device=dev)
+        be[:1] = self.fc_edge6.bias.detach()
+        wd = torch.zeros(4, 256, device=dev)
+        wd[:2] = self.fc_dp7[3].weight.detach().reshape(2, 256)
+        eo = ops.pw_fwd(ecat.view(-1, 160), we, 4, bias=be).view(N, h2, w2, 4)
+        do = ops.pw_fwd(o7.view(-1, 256), wd, 4).view(N, h2, w2, 4)
+        ctx.update(xs=xs, dp=dp, ecat=ecat, cat1=cat1, cat2=cat2, o7=o7, we=we, wd=wd, eo=eo, do=do)
+        return ctx
+
+    def features(self, x: torch.Tensor):
+        """([x1..x5], edge_cat, dp_cat1, dp_cat2) like EdgeDisplacement.features, but from the LIVE head parameters: the head
+        weights that prepare() snapshots go stale with the first optimizer step (train() keeps the folded backbone on purpose)."""
+        with torch.no_grad():
+            c = self._run(x)
+        return c["xs"], c["ecat"], c["cat1"], c["cat2"]
+
+    def forward(self, x: torch.Tensor):
+        """(edge_out [N,1,h,w] logits, dp_out [N,2,h,w]) of resnet50_irn.py:109-132 on the crop_size frame, no gradient; the mean
+        shift is the identity in training mode and `- running_mean` in eval mode (:104-107)."""
+        with torch.no_grad():
+            c = self._run(x)
+            edge = c["eo"][..., :1].permute(0, 3, 1, 2).contiguous()
+            dp = c["do"][..., :2].permute(0, 3, 1, 2).contiguous()
+            if not self.training:
+                dp = dp - self.mean_shift.running_mean.view(1, 2, 1, 1)
+            return edge, dp
+
+    def _path_table(self, device):
+        if self._table is None or self._table[0].device != device:
+            self._table = self.path_index.offsets_table(device)
+        return self._table
+
+    @staticmethod
+    def _head_backward(h, gdst):
+        """Backward of one head from the gradient of the concatenation it wrote into: sets .grad of its convolution and GroupNorm,
+        returns dX of the convolution's output (for a data gradient below, where a trainable head sits there)."""
+        conv, gn = h["seq"][0], h["seq"][1]
+        N, Hs, Ws, co = h["o"].shape
+        dY = ops.gn_resize_bwd(gdst, h["dst"], h["coff"], co, Hs, Ws, h["scale"])
+        dX, dgamma, dbeta = ops.gn_bwd(dY, h["o"], h["stat"], gn.weight.detach())
+        gn.weight.grad, gn.bias.grad = dgamma, dbeta
+        x2 = h["x"].view(-1, h["x"].shape[3])
+        dW = torch.zeros(co, x2.shape[1], dtype=torch.float32, device=x2.device)
+        ops.pw_wgrad(dX.view(-1, co), x2, dW)
+        conv.weight.grad = dW.view_as(conv.weight)
+        return dX.view(-1, co)
+
+    def loss_backward(self, img: torch.Tensor, label: torch.Tensor) -> torch.Tensor:
+        """Forward, loss and backward for img [N,3,S,S] and the reduced label map uint8 [N,S/4,S/4] (0..20, 255 = ignore).  Returns
+        the device tensor float64 [5] = (pos_aff, neg_aff, dp_fg, dp_bg, total); every trainable parameter gets a fresh .grad.
+        Every sum runs in this library's kernels in a fixed order except one: fc_edge6's bias gradient is torch's column sum of
+        dE, whose order is torch's (a tree reduction without atomics, the same bits from run to run on one build of torch).
+        Data gradients are formed only where a trainable head sits below (fc_dp7 -> cat2 -> fc_dp6 -> cat1); none into x1..x5."""
+        if not self.training:
+            raise MuscleHipError("AffinityDisplacementLoss.loss_backward: call .train() first (the mean shift is the identity in training)")
+        with torch.no_grad():
+            c = self._run(img)
+            eo, do = c["eo"], c["do"]
+            N, H, W, _ = eo.shape
+            if label.dtype != torch.uint8 or tuple(label.shape) != (N, H, W) or not label.is_cuda:
+                raise ValueError(f"label must be a CUDA uint8 [{N},{H},{W}] map (got {label.dtype} {tuple(label.shape)})")
+            if tuple(self.path_index.size) != (H, W):
+                raise ValueError(f"path_index was built for {self.path_index.size}, the network's output is {(H, W)}")
+            label = label.contiguous()
+            table, radius = self._path_table(img.device), self.path_index.radius
+            res, amax = ops.irn_loss_fwd(eo, do, label, table, radius)
+            dE, dD = ops.irn_loss_bwd(eo, do, label, table, radius, amax, res)
+            del amax
+            # fc_edge6 (160 -> 1, bias) as a 4-row weight
+            dW = torch.zeros(4, 160, device=img.device)
+            ops.pw_wgrad(dE, c["ecat"].view(-1, 160), dW)
+            self.fc_edge6.weight.grad = dW[:1].reshape(1, 160, 1, 1).clone()
+            self.fc_edge6.bias.grad = dE.sum(0)[:1]
+            g_ecat = ops.pw_dgrad(dE, c["we"], 160).view(N, H, W, 160)
+            for h in c["edge"]:
+                self._head_backward(h, g_ecat)
+            # the tail of fc_dp7 (256 -> 2), then fc_dp7 -> cat2 -> fc_dp1, fc_dp2, fc_dp6 -> cat1 -> fc_dp3..5
+            dW = torch.zeros(4, 256, device=img.device)
+            ops.pw_wgrad(dD, c["o7"].view(-1, 256), dW)
+            self.fc_dp7[3].weight.grad = dW[:2].reshape(2, 256, 1, 1).clone()
+            g_o7 = ops.pw_dgrad(dD, c["wd"], 256).view(N, H, W, 256)
+            dp = c["dp"]
+            dX7 = self._head_backward(dp[6], g_o7)
+            g_cat2 = ops.pw_dgrad(dX7, self.fc_dp7[0].weight.detach().reshape(256, 448), 448).view(N, H, W, 448)
+            self._head_backward(dp[0], g_cat2)
+            self._head_backward(dp[1], g_cat2)
+            dX6 = self._head_backward(dp[5], g_cat2)
+            cat1 = dp[5]["x"]
+            g_cat1 = ops.pw_dgrad(dX6, self.fc_dp6[0].weight.detach().reshape(256, 768), 768).view(cat1.shape)
+            for i in (2, 3, 4):
+                self._head_backward(dp[i], g_cat1)
+            return res[:5]
+
+
+_LOSS_NAMES = ("pos_aff_loss", "neg_aff_loss", "dp_fg_loss", "dp_bg_loss", "loss")
+
+
+def irn_step(model: AffinityDisplacementLoss, optimizer, batch) -> Dict[str, torch.Tensor]:
+    """One training step of the IRN heads: forward, loss, backward (gradients in .grad of the head parameters), optimizer.step().
+    batch: {"img": [N,3,S,S] float, "label": uint8 [N,S/4,S/4]} on the device.  Returns the four loss terms and their total
+    `loss` = (pos_aff + neg_aff)/2 + (dp_fg + dp_bg)/2 as device scalars (float64); nothing is read back to the host."""
+    res = model.loss_backward(batch["img"], batch["label"])
+    optimizer.step()
+    return {k: res[i] for i, k in enumerate(_LOSS_NAMES)}
 
 
 def cam_stack(cam_dict, H: int, W: int, device) -> torch.Tensor:

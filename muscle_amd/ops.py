@@ -766,3 +766,53 @@ def irn_net_finish(e, d, mean, h, w):
     dp = _f32(2, h, w, device=e.device)
     call("mx_irn_net_finish", ptr(e), lde, ptr(d), d.shape[3], ptr(mean), Hf, Wf, h, w, ptr(edge), ptr(dp), stream())
     return edge, dp
+
+
+# ---- training the IRN heads (csrc/irn_train.hip) ---------------------------------------------------------------
+def irn_loss_fwd(E, D, label, table, radius):
+    """E [N,H,W,lde] (column 0 = the edge logit), D [N,H,W,ldd] (columns 0,1 = the displacement), label uint8 [N,H,W], table = the
+    device path table (pts, poff, plen, n_dst) of indexing.PathIndex.offsets_table.  Returns (res float64 [16], amax uint8 [N,n_dst,n_src]):
+    res[:5] = pos_aff, neg_aff, dp_fg, dp_bg, total; the rest feeds irn_loss_bwd."""
+    N, H, W, lde = E.shape
+    pts, poff, plen, nd = table
+    rf = radius - 1
+    nbytes = int(lib().mx_irn_loss_ws(N, H, W, radius))
+    if nbytes < 0:
+        raise ValueError(f"irn_loss: geometry N={N} H={H} W={W} radius={radius}")
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=E.device)
+    amax = torch.empty(N, nd, (H - rf) * (W - 2 * rf), dtype=torch.uint8, device=E.device)
+    res = torch.empty(16, dtype=torch.float64, device=E.device)
+    call("mx_irn_loss_fwd", ptr(E), lde, ptr(D), D.shape[3], ptr(label), ptr(pts), ptr(poff), ptr(plen), nd, radius, N, H, W, ptr(amax),
+         ptr(ws), nbytes, ptr(res), stream())
+    return res, amax
+
+
+def irn_loss_bwd(E, D, label, table, radius, amax, res):
+    """d total / d E and / d D as the 4-column GEMM operands dE, dD [N*H*W, 4] (columns past the first / second are zero)."""
+    N, H, W, lde = E.shape
+    pts, poff, plen, nd = table
+    dE = _f32(N * H * W, 4, device=E.device)
+    dD = _f32(N * H * W, 4, device=E.device)
+    call("mx_irn_loss_bwd", ptr(E), lde, ptr(D), D.shape[3], ptr(label), ptr(pts), ptr(poff), ptr(plen), nd, radius, N, H, W, ptr(amax),
+         ptr(res), ptr(dE), ptr(dD), stream())
+    return dE, dD
+
+
+def gn_resize_bwd(gdst, fdst, coff, C, Hs, Ws, scale):
+    """Adjoint of gn_resize: gradient gdst and stored forward fdst of the concatenation [N,Hd,Wd,ldd], slice [coff, coff+C) ->
+    gradient at the GroupNorm output [N,Hs,Ws,C]."""
+    N, Hd, Wd, ldd = gdst.shape
+    dY = _f32(N, Hs, Ws, C, device=gdst.device)
+    call("mx_gn_resize_bwd", ptr(gdst), ptr(fdst), ptr(dY), N, Hs, Ws, C, int(scale), Hd, Wd, ldd, int(coff), stream())
+    return dY
+
+
+def gn_bwd(dY, X, stat, gamma):
+    """nn.GroupNorm backward on X [N,H,W,C]: dY is overwritten with dX and returned with (dgamma, dbeta)."""
+    N, H, W, C = X.shape
+    G = stat.shape[1]
+    nbytes = int(lib().mx_gn_bwd_ws(N, H * W, C, G))
+    ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=X.device)
+    dgamma, dbeta = _f32(C, device=X.device), _f32(C, device=X.device)
+    call("mx_gn_bwd", ptr(dY), ptr(X), ptr(stat), ptr(gamma), N, H * W, C, G, ptr(ws), nbytes, ptr(dY), ptr(dgamma), ptr(dbeta), stream())
+    return dY, dgamma, dbeta

@@ -211,3 +211,27 @@ class FusedAdam(torch.optim.Optimizer):
                     touched.append(q)
                 i = j
         return None
+
+
+class PolyOptimizer(torch.optim.SGD):
+    """The optimizer the reference trains the IRN heads with (src/torchutils.py:11-33), behaviour for behaviour, quirk included:
+    the value passed as `weight_decay` goes to torch.optim.SGD as its third POSITIONAL argument, which is SGD's `momentum`.  So
+    the reference trains with momentum = 1e-4 and zero weight decay, and this class does the same on purpose: a run here follows
+    the reference's trajectory, not the one the argument names suggest.  The `momentum` argument of this class is only the
+    exponent of the poly schedule: before step t < max_step every group's lr is its initial lr times (1 - t / max_step) ** 0.9;
+    from max_step on the last lr stays.  The step itself is torch's SGD on the 1.4 M head parameters (plumbing, no kernel)."""
+
+    def __init__(self, params, lr, weight_decay, max_step, momentum=0.9):
+        super().__init__(params, lr, weight_decay)       # positional on purpose: weight_decay lands in SGD's momentum slot
+        self.global_step, self.max_step = 0, max_step
+        self.momentum = self.power = momentum            # `momentum` is the reference's attribute name for the schedule's exponent
+        self._base_lrs = [g["lr"] for g in self.param_groups]
+
+    def step(self, closure=None):
+        if self.global_step < self.max_step:
+            decay = (1 - self.global_step / self.max_step) ** self.power
+            for group, base in zip(self.param_groups, self._base_lrs):
+                group["lr"] = base * decay
+        out = super().step(closure)
+        self.global_step += 1
+        return out
