@@ -591,6 +591,35 @@ int mx_crf_normalizers(const unsigned char* rgb, int H, int W, float sxy_g, floa
 int mx_crf_inference(const unsigned char* rgb, const float* prob, int L, int H, int W, int t, float confidence, float sxy_g, float w_g,
                      float sxy_b, float srgb, float w_b, float trunc, void* workspace, float* q_out, unsigned char* pred, void* stream);
 
+/* ---- IR labels from CAMs: the label CRF (src/imutils.py:477-491, crf_inference_label) and IRN's cam_to_ir_label around it;
+ * csrc/ir_label.hip -------------------------------------------------------------------------------------------------------- */
+
+/* The model of the section above (same k_m, n_m, window R_m = ceil(trunc * sxy_m) and update; the window is part of the model, so
+ * label maps are not bit-identical with pydensecrf's lattice filter) with the unary of unary_from_labels(zero_unsure=False) for L
+ * labels, formed in fp32:
+ *   U[l,i] = -log(gt_prob) if l == label(i) else -log((1 - gt_prob) / (L - 1));   Q_0 = softmax_l(-U)
+ * and the result argmax_l Q_t (first maximum wins).  src/imutils.py:477-491 fixes t = 10, gt_prob = 0.7, sxy_g = 3, w_g = 3,
+ * sxy_b = 50, srgb = 5, w_b = 10; here they are arguments.  cam_to_ir_label runs it twice per image, on
+ *   lab_fg = argmax([fg_thres, cams...], axis 0),  lab_bg = argmax([bg_thres, cams...], axis 0)     (first maximum wins: a CAM
+ *                                                                                  value equal to the threshold is background)
+ * with L = C + 1, maps both results through keys [L] (keys[0] = 0, keys[c+1] = class index of cams[c] + 1) and combines
+ *   conf = fg;  conf[fg == 0] = 255;  conf[bg + fg == 0] = 0.
+ * The two problems share the image, hence every k_m(i,j), both normalisers and the window walk: with fused = 1 and L <= 16 they run
+ * as the columns of ONE stencil-GEMM per pass (problem g in columns g*L .. g*L+L-1 of 32, softmax per problem); otherwise one
+ * problem per pass (17 <= L <= 21 always).  Both ways give the same bits.  2 <= L <= 21.  fp32, no atomics, fixed summation
+ * order.  ws: mx_ir_label_ws(L, H, W) bytes, 16-byte aligned, contents need not survive between calls. */
+long mx_ir_label_ws(int L, int H, int W);                               /* < 0: bad arguments */
+/* src/imutils.py:477-491 twice + the combination: rgb uint8 [H,W,3], cams [C,H,W], keys int [C+1] (device) -> conf uint8 [H,W].
+ * Optional: pred2 [2,H,W] = the two problems' argmax (label indices 0..C, before keys), q_out [2,L,H,W] = their Q_t.  t = 0
+ * returns Q_0 / the thresholded label maps. */
+int mx_ir_label(const unsigned char* rgb, const float* cams, const int* keys, int C, int H, int W, float fg_thres, float bg_thres, int t,
+                float gt_prob, float sxy_g, float w_g, float sxy_b, float srgb, float w_b, float trunc, int fused, void* ws,
+                unsigned char* conf, unsigned char* pred2, float* q_out, void* stream);
+/* src/imutils.py:477-491 once: labels int [H,W] (a value outside 0..L-1 has no own label: every entry of its unary is the
+ * "other" energy) -> pred uint8 [H,W] = argmax_l Q_t and/or q_out [L,H,W] = Q_t; at least one of the two */
+int mx_crf_label(const unsigned char* rgb, const int* labels, int L, int H, int W, int t, float gt_prob, float sxy_g, float w_g,
+                 float sxy_b, float srgb, float w_b, float trunc, void* ws, unsigned char* pred, float* q_out, void* stream);
+
 /* ---- the IRN edge / displacement network of infer_irn.py:66 (src/backbones/resnet50_irn.py:215-232 on src/backbones/resnet50.py),
  * inference only.  Its 1x1 convolutions are mx_pw_fwd calls; these are the pieces the EfficientNet path has no use for.
  * fp32, fixed summation order, no atomics. */

@@ -24,3 +24,5 @@ from . import data  # noqa: F401,E402  (input path: two-view sampler + device-si
 from .irn import EdgeDisplacement  # noqa: F401,E402  (the IRN edge / displacement network of infer_irn.py)
 from .irn import AffinityDisplacementLoss, irn_step  # noqa: F401,E402  (training the IRN heads; script: muscle_amd.train_irn)
 from .optim import PolyOptimizer  # noqa: F401,E402
+from .crf import crf_inference_label  # noqa: F401,E402  (src/imutils.py:477; the label CRF)
+from .ir_label import cam_to_ir_label, combine_conf  # noqa: F401,E402  (IR labels from CAMs; script: muscle_amd.cam_to_ir_label)

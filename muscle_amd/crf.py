@@ -86,3 +86,57 @@ def crf_inference(img, probs, t: int = 2, scale_factor: float = 1.5, labels: int
     numpy array or tensor (it may be un-normalised: the formula is applied as it stands).  Returns Q_t fp32 [labels,H,W] on
     the device."""
     return crf_run(img, probs, t, scale_factor, labels, confidence, trunc)[0]
+
+
+# imutils.py:487-488: addPairwiseGaussian(sxy=3, compat=3), addPairwiseBilateral(sxy=50, srgb=5, compat=10)
+LABEL_GAUSS_SXY, LABEL_GAUSS_W = 3.0, 3.0
+LABEL_BILATERAL_SXY, LABEL_BILATERAL_SRGB, LABEL_BILATERAL_W = 50.0, 5.0, 10.0
+LABEL_MODEL = (LABEL_GAUSS_SXY, LABEL_GAUSS_W, LABEL_BILATERAL_SXY, LABEL_BILATERAL_SRGB, LABEL_BILATERAL_W)
+
+_label_ws: Dict[Tuple[int, int, int], torch.Tensor] = {}
+
+
+def label_workspace(dev: torch.device, H: int, W: int) -> torch.Tensor:
+    """The workspace of mx_ir_label / mx_crf_label for an image size (it does not depend on L); one is kept per size."""
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(), H, W)
+    ws = _label_ws.get(key)
+    if ws is None:
+        nbytes = lib().mx_ir_label_ws(2, H, W)
+        if nbytes < 0:
+            raise MuscleHipError(f"mx_ir_label_ws failed: {lib().mx_last_error().decode()}")
+        if len(_label_ws) >= 4:                                # a few image sizes at most stay resident
+            _label_ws.pop(next(iter(_label_ws)))
+        ws = _label_ws[key] = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
+    return ws
+
+
+def crf_label_run(img, labels, t: int, n_labels: int, gt_prob: float, trunc: float, want_q: bool = False,
+                  want_pred: bool = True) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """One enqueue of mx_crf_label on the current stream; returns (Q_t fp32 [L,H,W] or None, argmax uint8 [H,W] or None)."""
+    lab = labels if torch.is_tensor(labels) else torch.from_numpy(np.ascontiguousarray(labels))
+    if lab.dim() != 2 or lab.dtype.is_floating_point or lab.dtype == torch.bool:
+        raise ValueError(f"labels must be an integer map [H,W] (got {lab.dtype} {tuple(lab.shape)})")
+    dev = lab.device if lab.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    lab = lab.to(dev, torch.int32).contiguous()
+    H, W = lab.shape
+    im = _device_image(img, dev)
+    if tuple(im.shape[:2]) != (H, W):
+        raise ValueError(f"img is {tuple(im.shape[:2])}, labels {(H, W)}")
+    L = int(n_labels)
+    with torch.cuda.device(dev):
+        ws = label_workspace(dev, H, W)
+        q = torch.empty(L, H, W, dtype=torch.float32, device=dev) if want_q else None
+        pred = torch.empty(H, W, dtype=torch.uint8, device=dev) if want_pred else None
+        call("mx_crf_label", ptr(im), ptr(lab), L, H, W, int(t), float(gt_prob), *LABEL_MODEL, float(trunc), ptr(ws), ptr(pred),
+             ptr(q), stream())
+    return q, pred
+
+
+def crf_inference_label(img, labels, t: int = 10, n_labels: int = 21, gt_prob: float = 0.7, *, trunc: float = 4.0) -> torch.Tensor:
+    """src/imutils.py:477 (same name, arguments and defaults): the CRF whose unary is unary_from_labels(labels, n_labels, gt_prob,
+    zero_unsure=False), Gaussian term sxy 3 / weight 3, bilateral term sxy 50, srgb 5 / weight 10.  img: uint8 [H,W,3] numpy array
+    or tensor; labels: int [H,W] numpy array or tensor with values 0..n_labels-1.  Returns argmax_l Q_t as a uint8 [H,W] tensor on
+    the device.  As for crf_inference, the sums run exactly over the window R_m = ceil(trunc * sxy_m), which is part of the model:
+    label maps are not bit-identical with pydensecrf's; what is pinned is this model against an fp64 restatement
+    (tests/ir_label_ref.py)."""
+    return crf_label_run(img, labels, t, n_labels, gt_prob, trunc)[1]

@@ -41,11 +41,12 @@ class NpyWriter:
     """np.save on one thread behind a bounded queue.  put() blocks only when `depth` files are pending; close() drains the
     queue, joins the thread and re-raises the first error a write met (put() does too, so a full disk ends the run early)."""
 
-    def __init__(self, depth: int = 16):
+    def __init__(self, depth: int = 16, save=np.save):
         import queue
         import threading
         self._q = queue.Queue(maxsize=depth)
         self._err: Optional[BaseException] = None
+        self._save = save                                      # (path, object) -> None; np.save here, a PNG writer elsewhere
         self._t = threading.Thread(target=self._run, name="npy-writer", daemon=True)
         self._t.start()
 
@@ -56,7 +57,7 @@ class NpyWriter:
                 if job is None:
                     return
                 if self._err is None:
-                    np.save(job[0], job[1])
+                    self._save(job[0], job[1])
             except BaseException as e:  # noqa: BLE001  (handed to the main thread)
                 self._err = e
             finally:

@@ -9,7 +9,8 @@
 What a caller should know:
   * --backbone_weights names a ResNet-50 state dict (torchvision names, `conv1.weight` ...) or an IRN state dict
     (`resnet50.conv1.weight` ...); nothing is downloaded.  The backbone is frozen, as in the reference;
-  * --ir_label_dir holds the IR label PNGs (0..20, 255 = ignore), one per name of --train_list; generating them is another stage;
+  * --ir_label_dir holds the IR label PNGs (0..20, 255 = ignore), one per name of --train_list; `python -m muscle_amd.cam_to_ir_label`
+    writes them from the CAM dicts of `infer_mcl`;
   * the loader is the host-side restatement of VOC12AffinityDataset with PIL and numpy, draws in the reference's order; it ships
     the reduced uint8 label map [crop/4, crop/4], never the three [n_dst, n_src] float label tensors - the loss kernel derives
     the pair labels on the fly.
