@@ -404,6 +404,22 @@ int mx_irn_transition(float* dense, int n4, int ld, float beta, float* colsum, v
  * values themselves as the script's --soft_output writes them.  max_scratch: one uint32. */
 int mx_irn_finish(const float* rw, int C, int h, int w, int H, int W, float bg_thres, unsigned* max_scratch, unsigned char* label,
                   void* soft_half, void* stream);
+/* The same walk without the matrix (csrc/irn_walk.hip): x . T^steps as `steps` stencil applications, O(nd * n) memory.
+ * mx_irn_walk_weights (indexing.py:77-93 + :116-118; same path table as mx_irn_affinity, n = h*w):
+ *   W[nd][n] fp32, direction-major: W[d][p] = (1 - max of the edge along the straight path p -> p+d)^beta, 0 where p+d lies
+ *   outside the image (what the padding with 1.0 of :124 and the crop of :131-133 amount to); the power as mx_irn_transition
+ *   forms it, so the non-zero weights are that path's dense^beta entries bit for bit.
+ *   cs[n] fp64 = 1 + sum_d (W[d][j] + W[d][j-d]), the column sums of dense^beta, gathered in a fixed order.
+ * mx_irn_walk (indexing.py:119-120 + :145-147): state 0 = (double)(x * (1 - edge)) with the product in fp32, then `steps` times
+ *   v'[c][j] = (v[c][j] + sum_d (v[c][j+d] W[d][j] + v[c][j-d] W[d][j-d])) / cs[j], fp64 sums in one fixed order per pixel,
+ *   taps outside the image skipped; the last step writes rw[C][n] rounded to fp32.  x [C][n] fp32; state_a, state_b: two
+ *   distinct fp64 [C][n] buffers of mx_irn_walk_ws(C, n) bytes EACH, contents need not survive between calls.  All `steps`
+ *   launches are enqueued by the one call.  1 <= steps <= 4096, radius >= 1. */
+int mx_irn_walk_weights(const float* edge, int h, int w, int radius, const int* pcoord, const int* poff, const int* plen, int nd,
+                        float beta, float* W, double* cs, void* stream);
+long mx_irn_walk_ws(int C, int n);                                       /* < 0: bad arguments */
+int mx_irn_walk(const float* x, const float* edge, const float* W, const double* cs, int h, int w, int radius, const int* pcoord,
+                const int* poff, const int* plen, int nd, int C, int steps, double* state_a, double* state_b, float* rw, void* stream);
 
 /* ---- per-epoch rapid evaluation (train_mcl.py:286-318 + src/evaluation.py:19-52), one image:
  * for each threshold t: predict = argmax_k [t, half(pred_k*label_k)] (first maximum wins); over pixels with gt < 255:

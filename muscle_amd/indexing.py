@@ -7,6 +7,10 @@ dense symmetric affinity matrix directly from the edge map, one pass turns it in
 2^exp_times-step walk is exp_times fp32 MFMA GEMMs (`mx_bgemm`) ping-ponging between two buffers; the class maps are
 propagated with one more GEMM.  For a VOC image at the IRN's 1/4 resolution (≈94x125 = 11.7k vertices) that is
 8 x 2 x 11.7k^3 = 25.7 TFLOP per image, by far the dominant cost of infer_irn.py.
+
+`method="stencil"` computes the same x . T^(2^exp_times) without the matrix: T has at most 2 nd + 1 non-zeros per column
+(nd = 34 one-sided search directions at radius 5), so it is applied 2^exp_times times as a stencil on an fp64 state
+(`mx_irn_walk_weights`, `mx_irn_walk`; DESIGN.md, "IRN random-walk propagation").  The dense path stays the default.
 """
 from __future__ import annotations
 
@@ -51,11 +55,28 @@ def _path_table(radius: int, device):
     return _tables[key]
 
 
-def propagate_to_edge(x: torch.Tensor, edge: torch.Tensor, radius: int = 5, beta: float = 10, exp_times: int = 8) -> torch.Tensor:
+WALK_METHODS = ("dense", "stencil")
+
+
+def propagate_to_edge(x: torch.Tensor, edge: torch.Tensor, radius: int = 5, beta: float = 10, exp_times: int = 8,
+                      method: str = "dense") -> torch.Tensor:
     """x: [..., C, h, w] class maps (any leading 1s), edge: [1,h,w] or [h,w] boundary probability, both CUDA.
-    Returns rw [C,1,h,w] like the reference."""
+    Returns rw [C,1,h,w] like the reference.  method="dense" squares the n x n transition matrix exp_times times as the
+    reference does; method="stencil" applies it 2^exp_times times as a stencil (csrc/irn_walk.hip): O(nd * n) memory, fp64 state,
+    0 <= exp_times <= 12."""
+    if method not in WALK_METHODS:
+        raise ValueError(f"propagate_to_edge: method must be one of {WALK_METHODS} (got {method!r})")
+    if method == "stencil" and (int(exp_times) != exp_times or not 0 <= exp_times <= 12):
+        raise ValueError(f"propagate_to_edge: the stencil walk takes exp_times 0..12, 2^exp_times steps (got {exp_times!r})")
     if not x.is_cuda or not edge.is_cuda:
         raise MuscleHipError("propagate_to_edge runs on the HIP kernels only")
+    if method == "stencil":
+        h, w = x.shape[-2:]
+        e = edge.reshape(h, w).contiguous().float()
+        table = _path_table(radius, x.device)
+        W, cs = ops.irn_walk_weights(e, table, radius, beta)
+        rw = ops.irn_walk(x.reshape(-1, h, w).contiguous().float(), e, W, cs, table, radius, 2 ** int(exp_times))
+        return rw.reshape(-1, 1, h, w)
     h, w = x.shape[-2:]
     n = h * w
     n4 = (n + 3) // 4 * 4                         # GEMM operands need leading dimensions that are multiples of 4

@@ -5,7 +5,8 @@ colour map, and with --soft_output 1 instead `<sem_seg_out_dir>/<name>.npy`, flo
 Differences a caller can see:
   * --irn_network is accepted and ignored: the one network the reference ships (src.backbones.resnet50_irn) is built in;
   * nothing is downloaded: --irn_weights_name must name a checkpoint (the reference fetches ImageNet weights first and then
-    overwrites them with the checkpoint).
+    overwrites them with the checkpoint);
+  * --walk stencil (not in the reference) runs the random walk matrix-free; the default, dense, is the reference's way.
 """
 from __future__ import annotations
 
@@ -29,6 +30,9 @@ def parse_args(argv: Optional[List[str]] = None):
     ap.add_argument("--voc12_root", default="data/VOC2012", type=str)
     ap.add_argument("--infer_list", default="data/train.txt", type=str)
     ap.add_argument("--soft_output", default=0, type=int, help="write float16 soft pseudo labels instead of the PNG")
+    ap.add_argument("--walk", default="dense", choices=("dense", "stencil"),
+                    help="the random walk: dense = exp_times squarings of the n x n transition matrix (the reference's way), "
+                         "stencil = 2^exp_times matrix-free steps on an fp64 state (O(n) memory)")
     args = ap.parse_args(argv)
     if args.irn_network != ap.get_default("irn_network"):
         print(f"[muscle_amd] note: --irn_network {args.irn_network} ignored; the ResNet-50 IRN is the one network built here",
@@ -58,7 +62,7 @@ def main(argv: Optional[List[str]] = None) -> int:
         pair = torch.cat(stager(img, (1.0,)), dim=0)                                                 # image + flip, color_norm'ed
         cam = load_cam_dict(os.path.join(args.cam_dir, name + ".npy"))
         res = infer_irn(model, pair, cam, beta=args.beta, exp_times=args.exp_times, bg_thres=args.sem_seg_bg_thres,
-                        soft_output=bool(args.soft_output))
+                        soft_output=bool(args.soft_output), method=args.walk)
         if args.soft_output:
             np.save(os.path.join(args.sem_seg_out_dir, name + ".npy"), res[1].cpu().numpy())
         else:

@@ -454,16 +454,17 @@ def cam_stack(cam_dict, H: int, W: int, device) -> torch.Tensor:
 
 
 def infer_irn(model: EdgeDisplacement, img_pair: torch.Tensor, cam_dict, *, beta=8, exp_times=6, bg_thres=0.35,
-              soft_output: bool = False):
+              soft_output: bool = False, method: str = "dense"):
     """infer_irn.py:64-92 for one image: the network, the CAM down-scaling (:76), the random walk (:77) and the label step
     (:79-92).  img_pair: [2,3,H,W] on the device; cam_dict: {class index: float32 [H,W]}.  Returns the uint8 label map [H,W]
-    (and the fp16 [H,W,21] array with soft_output) on the device."""
+    (and the fp16 [H,W,21] array with soft_output) on the device.  method: the walk of indexing.propagate_to_edge, "dense"
+    (matrix squarings) or "stencil" (matrix-free)."""
     H, W = img_pair.shape[2:]
     edge, _dp = model(img_pair)
     with torch.no_grad():
         cams = cam_stack(cam_dict, H, W, img_pair.device)
         down = ops.resize_planar_halfpixel(cams, edge.shape[1], edge.shape[2])
-        rw = indexing.propagate_to_edge(down, edge, beta=beta, exp_times=exp_times, radius=5)
+        rw = indexing.propagate_to_edge(down, edge, beta=beta, exp_times=exp_times, radius=5, method=method)
         return indexing.finish_semseg(rw, H, W, bg_thres, soft_output=soft_output)
 
 

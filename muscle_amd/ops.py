@@ -768,6 +768,32 @@ def irn_net_finish(e, d, mean, h, w):
     return edge, dp
 
 
+def irn_walk_weights(edge, table, radius, beta):
+    """edge [h,w] fp32, table = the device path table (pcoord, poff, plen, nd) of indexing._path_table.  Returns (W fp32 [nd,n],
+    cs fp64 [n]): the one-sided stencil weights affinity^beta and the column sums of the matrix they stand for."""
+    h, w = edge.shape
+    pc, off, ln, nd = table
+    W = _f32(nd, h * w, device=edge.device)
+    cs = torch.empty(h * w, dtype=torch.float64, device=edge.device)
+    call("mx_irn_walk_weights", ptr(edge), h, w, radius, ptr(pc), ptr(off), ptr(ln), nd, float(beta), ptr(W), ptr(cs), stream())
+    return W, cs
+
+
+def irn_walk(x, edge, W, cs, table, radius, steps):
+    """x [C,h,w] fp32, edge [h,w] fp32 -> rw fp32 [C,h,w] = (x * (1 - edge)) . T^steps, `steps` stencil applications on an fp64
+    state (two [C,n] buffers), all enqueued by one call."""
+    C, h, w = x.shape
+    pc, off, ln, nd = table
+    nbytes = int(lib().mx_irn_walk_ws(C, h * w))
+    if nbytes < 0:
+        raise ValueError(f"irn_walk: geometry C={C} h={h} w={w}")
+    state = torch.empty(2, nbytes // 8, dtype=torch.float64, device=x.device)
+    rw = _f32(C, h, w, device=x.device)
+    call("mx_irn_walk", ptr(x), ptr(edge), ptr(W), ptr(cs), h, w, radius, ptr(pc), ptr(off), ptr(ln), nd, C, int(steps),
+         ptr(state[0]), ptr(state[1]), ptr(rw), stream())
+    return rw
+
+
 # ---- training the IRN heads (csrc/irn_train.hip) ---------------------------------------------------------------
 def irn_loss_fwd(E, D, label, table, radius):
     """E [N,H,W,lde] (column 0 = the edge logit), D [N,H,W,ldd] (columns 0,1 = the displacement), label uint8 [N,H,W], table = the
