@@ -271,6 +271,17 @@ int mx_dwconv_bwd_fused_bn0(const float* dA, const float* D, const float* gate, 
                             int pad_lo, void* ws, long ws_bytes, double count, const float* gamma, const float* mean, const float* rstd,
                             int training, float* dgamma, float* dbeta, float* o1, float* o2, float* o3, void* stream);
 
+/* The same fusion for a stride-2 depthwise convolution with the static TF-"same" padding (pad_lo before; Ho, Wo as the forward made them;
+ * K = 3: pad_lo 0 or 1, K = 5: 1 or 2), dA / D [N,Ho,Wo,C], X / gX [N,H,Wd,C].  The depthwise input
+ * always sits behind BatchNorm-0 + SiLU (a0, b0 required; a plain-input stride-2 block keeps mx_bn_bwd_apply + mx_dwconv_bwd_weight +
+ * mx_dwconv_bwd_data): gX = dwconv^T(dd) * swish'(a0*X+b0); dW += sum dd*swish(a0*X+b0) (dW == NULL: left to mx_dw_parts_reduce);
+ * part[mx_dwconv_bwd_fused_s2_parts()][2][C] = (sum g, sum g*X) of the written gX, dw_scratch[parts][C*K*K] workspace.  parts <= 1024. */
+int mx_dwconv_bwd_fused_s2_parts(int N, int H, int Wd, int C, int K);
+int mx_dwconv_bwd_fused_s2(const float* dA, const float* D, const float* gate, const float* add, const float* a1, const float* b1,
+                           const float* c1, const float* c2, const float* c3, const float* X, const float* a0, const float* b0,
+                           const float* W, float* gX, float* dW, float* dw_scratch, float* part, int N, int H, int Wd, int C, int K,
+                           int pad_lo, int Ho, int Wo, void* stream);
+
 int mx_dw_parts_reduce(const float* part, int P, int n, float* dW, void* stream);
 
 /* ---- SE excitation (model.py:83-84) and stem patches (model.py:131,175) -------------------------------- */

@@ -837,6 +837,218 @@ __global__ __launch_bounds__(256, (TH == 7) ? 3 : (K == 5 || TH != 8) ? 2 : 3) v
   }
 }
 
+// ---------------------------------------------------------------------------
+// The same fusion for the stride-2 blocks (static TF-"same" padding, the depthwise input always behind BN0 + SiLU):
+//   dd = c1*((dA*gate + add)*swish'(a1*d + b1)) + c2*d + c3 formed while the OUTPUT-resolution tile is staged, never written;
+//   gX = dwconv^T(dd) * swish'(a0*x + b0), dW partial rows, BN0 backward partial rows (sum g, sum g*x) - one kernel instead of
+//   bn_bwd_apply + dw_bwd_weight<K,2> + dw_bwd_data<K,2> + the BN0 reduction with swish' recomputed.
+// Tile: 8 x 32 INPUT pixels x 32 channels, origin chosen so that (iy0 + pad) and (ix0 + pad) are even.  Input pixel (u, v) of the
+// tile then meets tap (ky, kx) iff ky = u, kx = v (mod 2), at dd[(u - ky)/2 + h][(v - kx)/2 + h] of the staged tile (h = (K-1)/2):
+// a thread owns 2 channels x (2 rows x 8 pixels) = 4 whole 2 x 2 parity blocks, every tap set and LDS offset a compile-time constant,
+// and the K*K (pixel, tap) pairs of a 2 x 2 block feed the data gradient and the K*K weight-gradient sums from the same read.
+// The staged rows are pitched at an odd number of pixels: the two row pairs of a half-wave then sit on different LDS bank halves.
+// ---------------------------------------------------------------------------
+struct DwFusedS2Args {
+  const float* dA; const float* d;                    // [N,Ho,Wo,C] each
+  const float* gate; const float* add;                // [N,C]
+  const float* a1; const float* b1;                   // BN1 scale / shift
+  const float* c1; const float* c2; const float* c3;  // BN1 backward coefficients
+  const float* x; const float* a0; const float* b0;   // dw input (raw) [N,H,W,C] and its BN0 scale / shift
+  const float* w;                                     // [C,1,K,K]
+  float* gx; float* dwpart; float* part;              // gX [N,H,W,C], dW partial rows [groups][C*K*K], BN0 partial sums [groups][2][C]
+  int N, H, W, Ho, Wo, C, pad, tiles_x, tiles_y, tiles_per_block;
+};
+
+template <int K>
+__global__ __launch_bounds__(256, K == 3 ? 3 : 2) void dw_bwd_fused_s2_kernel(DwFusedS2Args a) {
+  constexpr int TH = 8, TW = 32, HK = (K - 1) / 2;
+  constexpr int OH = TH / 2 + HK, OW = TW / 2 + HK, OWP = OW | 1;      // dd rows / columns a tile's taps reach; odd row pitch
+  constexpr int TOT = OH * OW * C4B, PER = (TOT + 255) / 256;
+  constexpr int C2B = CB / 2, PX = 8, QB = PX / 2;                     // compute: 2 channels x 2 rows x PX pixels per thread
+  static_assert((TH / 2) * (TW / PX) * C2B == 256, "thread mapping");
+  __shared__ float4 td[OH * OWP * C4B];    // dd with halo; at the end the per-wave partial rows of dW and of the BN0 sums
+  static_assert(OH * OWP * C4B * 4 >= 4 * K * K * CB, "the per-wave partial rows reuse the staged tile");
+  __shared__ __attribute__((aligned(16))) float wl[K * K * CB];
+  __shared__ __attribute__((aligned(16))) float cst[9 * CB];   // a1 b1 c1 c2 c3 a0 b0 | gate add (per tile)
+  const int tid = threadIdx.x, c0 = blockIdx.y * CB;
+  const int c4 = tid % C4B;                        // staging: 4 channels per thread
+  const int c = c0 + 4 * c4;
+  const bool cok = c < a.C;
+  const int c2 = tid % C2B, pq = tid / C2B;
+  const int rp = pq % (TH / 2), seg = pq / (TH / 2);   // row pair and 8-pixel segment: a wave holds 4 row pairs of one segment
+  const int cc2 = c0 + 2 * c2;
+  const bool cok2 = cc2 < a.C;
+  const int ntile = a.tiles_x * a.tiles_y;
+  const long t_beg = (long)blockIdx.x * a.tiles_per_block;
+  const long t_end = min((long)a.N * ntile, t_beg + a.tiles_per_block);
+  for (int i = tid; i < K * K * CB; i += 256) {
+    int cc = i % CB, tap = i / CB;
+    wl[i] = (c0 + cc < a.C) ? a.w[(long)(c0 + cc) * K * K + tap] : 0.f;
+  }
+  for (int i = tid; i < 7 * CB; i += 256) {
+    int cc = i % CB, j = i / CB;
+    const float* src = j == 0 ? a.a1 : j == 1 ? a.b1 : j == 2 ? a.c1 : j == 3 ? a.c2 : j == 4 ? a.c3 : j == 5 ? a.a0 : a.b0;
+    cst[i] = (c0 + cc < a.C) ? src[c0 + cc] : 0.f;
+  }
+  float2 part[K * K];
+#pragma unroll
+  for (int t = 0; t < K * K; ++t) part[t] = make_float2(0, 0);
+  float2 s0 = make_float2(0, 0), s1 = s0;
+  const int par = a.pad & 1;
+  for (long t = t_beg; t < t_end; ++t) {
+    const int n = (int)(t / ntile), rem = (int)(t % ntile);
+    const int iy0 = (rem / a.tiles_x) * TH - par, ix0 = (rem % a.tiles_x) * TW - par;     // (iy0 + pad), (ix0 + pad): even, >= 0
+    const int oy_lo = (iy0 + a.pad) / 2 - HK, ox_lo = (ix0 + a.pad) / 2 - HK;
+    __syncthreads();
+    if (tid < 2 * CB) {
+      int cc = tid % CB;
+      cst[7 * CB + tid] = (c0 + cc < a.C) ? (tid < CB ? a.gate : a.add)[(long)n * a.C + c0 + cc] : 0.f;
+    }
+    // this thread's 2 x 8 centre pixels of X (raw), requested before the staging loop so they land under it: clamped addresses,
+    // masked at use
+    float2 xr[2][PX];
+    const int iyb = iy0 + 2 * rp, ixb = ix0 + PX * seg;
+#pragma unroll
+    for (int pu = 0; pu < 2; ++pu) {
+      const float* row = a.x + (((long)n * a.H + min(max(iyb + pu, 0), a.H - 1)) * a.W) * a.C + (cok2 ? cc2 : 0);
+#pragma unroll
+      for (int j = 0; j < PX; ++j) xr[pu][j] = *reinterpret_cast<const float2*>(row + min(max(ixb + j, 0), a.W - 1) * a.C);
+    }
+    __syncthreads();
+    // stage dd: all of a thread's float4 pairs in flight; out-of-image / out-of-range elements read a clamped (valid) address and
+    // are multiplied by 0
+    {
+      float4 vg[PER], vd[PER];
+      unsigned okm = 0;
+#pragma unroll
+      for (int k = 0; k < PER; ++k) {
+        const int i = min(tid + 256 * k, TOT - 1), pix = i / C4B;
+        int oy = oy_lo + pix / OW, ox = ox_lo + pix % OW;
+        okm |= (oy >= 0 && oy < a.Ho && ox >= 0 && ox < a.Wo && cok) ? (1u << k) : 0u;
+        oy = min(max(oy, 0), a.Ho - 1); ox = min(max(ox, 0), a.Wo - 1);
+        const long off = (((long)n * a.Ho + oy) * a.Wo + ox) * a.C + (cok ? c : 0);
+        vg[k] = ld4(a.dA + off); vd[k] = ld4(a.d + off);
+      }
+      const float4 A1 = ld4(cst + 4 * c4), B1 = ld4(cst + CB + 4 * c4), C1 = ld4(cst + 2 * CB + 4 * c4),
+                   C2 = ld4(cst + 3 * CB + 4 * c4), C3 = ld4(cst + 4 * CB + 4 * c4),
+                   G = ld4(cst + 7 * CB + 4 * c4), AD = ld4(cst + 8 * CB + 4 * c4);
+#define DD1(f) dd.f = okf * (C1.f * ((vg[k].f * G.f + AD.f) * swish_gradf_(A1.f * vd[k].f + B1.f)) + C2.f * vd[k].f + C3.f);
+#pragma unroll
+      for (int k = 0; k < PER; ++k) {
+        const int i = min(tid + 256 * k, TOT - 1), pix = i / C4B;   // duplicates of the last element rewrite the same value
+        const float okf = ((okm >> k) & 1u) ? 1.f : 0.f;
+        float4 dd;
+        DD1(x) DD1(y) DD1(z) DD1(w)
+        td[((pix / OW) * OWP + pix % OW) * C4B + c4] = dd;
+      }
+#undef DD1
+    }
+    __syncthreads();
+    const float2 A0 = *reinterpret_cast<const float2*>(cst + 5 * CB + 2 * c2), B0 = *reinterpret_cast<const float2*>(cst + 6 * CB + 2 * c2);
+    const float2* tdg = reinterpret_cast<const float2*>(td) + (rp * OWP + seg * QB) * C2B + c2;
+    const float2* wl2 = reinterpret_cast<const float2*>(wl) + c2;
+#pragma unroll
+    for (int pu = 0; pu < 2; ++pu) {
+      const int iy = iyb + pu;
+      const bool rok = cok2 && iy >= 0 && iy < a.H;
+      float2 xa[PX], df[PX], ah[PX];
+      bool img[PX];
+#pragma unroll
+      for (int j = 0; j < PX; ++j) {
+        const float2 r = xr[pu][j];
+        img[j] = rok && ixb + j >= 0 && ixb + j < a.W;
+        const float zx = A0.x * r.x + B0.x, zy = A0.y * r.y + B0.y;
+        const float sx = sigmoidf_(zx), sy = sigmoidf_(zy);
+        xa[j] = img[j] ? make_float2(zx * sx, zy * sy) : make_float2(0.f, 0.f);
+        df[j] = make_float2(sx * (1.0f + zx * (1.0f - sx)), sy * (1.0f + zy * (1.0f - sy)));   // swish'(z) from the same sigma
+        ah[j] = make_float2(0.f, 0.f);
+      }
+      // kernel rows ky = pu, pu + 2, ...: dd row rp + h - m of the tile, columns 4 seg .. 4 seg + 3 + h
+#pragma unroll
+      for (int m = 0; pu + 2 * m < K; ++m) {
+        const int ky = pu + 2 * m;
+        float2 in[QB + HK];
+#pragma unroll
+        for (int q = 0; q < QB + HK; ++q) in[q] = tdg[((HK - m) * OWP + q) * C2B];
+#pragma unroll
+        for (int kx = 0; kx < K; ++kx) {
+          const int pv = kx & 1, mx = kx >> 1;
+          const float2 w = wl2[(ky * K + kx) * C2B];
+          float2& p = part[ky * K + kx];
+#pragma unroll
+          for (int jb = 0; jb < QB; ++jb) {
+            const float2 v = in[jb + HK - mx];
+            const int j = 2 * jb + pv;
+            ah[j].x += w.x * v.x; ah[j].y += w.y * v.y;
+            p.x += xa[j].x * v.x; p.y += xa[j].y * v.y;
+          }
+        }
+      }
+      const long rowoff = (((long)n * a.H + min(max(iy, 0), a.H - 1)) * a.W) * a.C + cc2;
+#pragma unroll
+      for (int j = 0; j < PX; ++j) {
+        if (img[j]) {
+          const float2 r = xr[pu][j];
+          float2 v = ah[j];
+          v.x *= df[j].x; v.y *= df[j].y;
+          s0.x += v.x; s0.y += v.y;
+          s1.x += v.x * r.x; s1.y += v.y * r.y;
+          *reinterpret_cast<float2*>(a.gx + rowoff + (long)(ixb + j) * a.C) = v;
+        }
+      }
+    }
+  }
+  // leave as dw_bwd_fused_kernel does: each wave folds its lanes and writes one row into the (now free) tile memory, the four rows
+  // are added in wave order, one dW row and one BN0 row per workgroup.  No atomics: the same bits every run.
+  __syncthreads();
+  float* slots = reinterpret_cast<float*>(td);             // [4][K*K*CB]
+  const int wave = tid >> 6;
+#pragma unroll
+  for (int t = 0; t < K * K; ++t) {
+    float2 p = part[t];
+    p.x += __shfl_xor(p.x, 16, 64); p.y += __shfl_xor(p.y, 16, 64);
+    p.x += __shfl_xor(p.x, 32, 64); p.y += __shfl_xor(p.y, 32, 64);
+    if ((tid & 63) < C2B) *reinterpret_cast<float2*>(slots + (wave * K * K + t) * CB + 2 * c2) = p;
+  }
+  __syncthreads();
+  for (int i = tid; i < K * K * CB; i += 256) {
+    int cc = i % CB, tap = i / CB;
+    if (c0 + cc < a.C)
+      a.dwpart[(long)blockIdx.x * a.C * K * K + (long)(c0 + cc) * K * K + tap] =
+          ((slots[i] + slots[K * K * CB + i]) + slots[2 * K * K * CB + i]) + slots[3 * K * K * CB + i];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int o = 16; o < 64; o <<= 1) {
+    s0.x += __shfl_xor(s0.x, o, 64); s0.y += __shfl_xor(s0.y, o, 64);
+    s1.x += __shfl_xor(s1.x, o, 64); s1.y += __shfl_xor(s1.y, o, 64);
+  }
+  if ((tid & 63) < C2B) {
+    *reinterpret_cast<float2*>(slots + wave * 2 * CB + 2 * c2) = s0;
+    *reinterpret_cast<float2*>(slots + wave * 2 * CB + CB + 2 * c2) = s1;
+  }
+  __syncthreads();
+  if (tid < 2 * CB) {
+    const int cc = tid % CB;
+    if (c0 + cc < a.C)
+      a.part[(long)blockIdx.x * 2 * a.C + (tid / CB) * a.C + c0 + cc] =
+          ((slots[tid] + slots[2 * CB + tid]) + slots[4 * CB + tid]) + slots[6 * CB + tid];
+  }
+}
+
+// groups = workgroups per channel chunk = partial rows written (<= 1024 for every shape: BN0 then finalises in one launch).  The count
+// must not depend on pad_lo (mx_dwconv_bwd_fused_s2_parts does not know it) while the tiling does (the origin's parity): it is taken
+// from the tiles of the unshifted tiling, never more than the real number; a group is tpb consecutive tiles of the (sample, tile)
+// sequence, and a group the sequence does not reach writes rows of zeros.
+static int dw_fused_s2_groups(int N, int H, int Wd, int C, int K) {
+  const long ntiles = (long)N * cdiv(Wd, 32) * cdiv(H, 8);
+  long g = (K == 5 ? 2048 : 4096) / cdiv(C, CB);      // as dw_fused_geom: the 5x5 form's leave is the heavier one
+  if (g > 1024) g = 1024;
+  if (g < 1) g = 1;
+  if (g > ntiles) g = ntiles;
+  return cdiv(ntiles, cdiv(ntiles, g));               // no group left idle by the rounding of tiles per group
+}
+
 // dW[i] += sum_g part[g][i]: one workgroup = 16 consecutive elements x 16 row lanes (lane l adds rows l, l+16, ... with four
 // loads in flight), the 16 lane sums are added in lane order: one owner per element, no atomics, same bits every run.
 __global__ __launch_bounds__(256) void dw_parts_reduce_kernel(const float* __restrict__ part, int P, int n, float* __restrict__ dW) {
@@ -1132,6 +1344,44 @@ static int dw_bwd_fused_impl(const float* dA, const float* D, const float* gate,
   }
   MX_LAUNCH_CHECK();
   if (dW) {                        // dW == null: the caller adds the partial rows later (mx_dw_parts_reduce), e.g. off the critical path
+    launch_dw_parts_reduce(dw_scratch, groups, C * K * K, dW, (hipStream_t)stream);
+    MX_LAUNCH_CHECK();
+  }
+  return MX_OK;
+}
+
+// number of partial rows mx_dwconv_bwd_fused_s2 writes (BN0 sums [rows][2][C] and dW scratch [rows][C*K*K]); at most 1024
+int mx_dwconv_bwd_fused_s2_parts(int N, int H, int Wd, int C, int K) {
+  if (N <= 0 || H <= 0 || Wd <= 0 || C <= 0 || (K != 3 && K != 5)) return MX_EARG;
+  return dw_fused_s2_groups(N, H, Wd, C, K);
+}
+
+// Stride-2 backward of BN0+SiLU -> dwconv (static TF-"same" padding) -> BN1 -> SiLU -> SE gate fused (see dw_bwd_fused_s2_kernel):
+//   gX = dwconv^T(dd) * swish'(a0*X+b0);  dW += sum dd*swish(a0*X+b0);  part = BN0 backward partial sums
+int mx_dwconv_bwd_fused_s2(const float* dA, const float* D, const float* gate, const float* add, const float* a1, const float* b1,
+                           const float* c1, const float* c2, const float* c3, const float* X, const float* a0, const float* b0,
+                           const float* W, float* gX, float* dW, float* dw_scratch, float* part, int N, int H, int Wd, int C, int K,
+                           int pad_lo, int Ho, int Wo, void* stream) {
+  MX_CHECK_ARG(a0 && b0, "dwconv_bwd_fused_s2: the BatchNorm-0 form only (a0, b0 required)");
+  MX_CHECK_ARG(dA && D && gate && add && a1 && b1 && c1 && c2 && c3 && X && W && gX && dw_scratch && part, "dwconv_bwd_fused_s2: null pointer");
+  MX_CHECK_ARG(K == 3 || K == 5, "dwconv_bwd_fused_s2: kernel %d unsupported (3 or 5)", K);
+  MX_CHECK_ARG(N > 0 && H > 0 && Wd > 0 && C > 0 && C % 4 == 0, "dwconv_bwd_fused_s2: bad extents N=%d H=%d W=%d C=%d", N, H, Wd, C);
+  MX_CHECK_ARG((pad_lo == (K - 1) / 2 || pad_lo == (K - 1) / 2 - 1) && Ho > 0 && Wo > 0 && (Ho - 1) * 2 + K - pad_lo <= H + K &&
+               (Wo - 1) * 2 + K - pad_lo <= Wd + K,
+               "dwconv_bwd_fused_s2: inconsistent static same padding / output size (K=%d pad=%d H=%d W=%d Ho=%d Wo=%d)", K, pad_lo, H, Wd, Ho, Wo);
+  DwFusedS2Args a{};
+  a.dA = dA; a.d = D; a.gate = gate; a.add = add; a.a1 = a1; a.b1 = b1; a.c1 = c1; a.c2 = c2; a.c3 = c3;
+  a.x = X; a.a0 = a0; a.b0 = b0; a.w = W; a.gx = gX; a.dwpart = dw_scratch; a.part = part;
+  a.N = N; a.H = H; a.W = Wd; a.Ho = Ho; a.Wo = Wo; a.C = C; a.pad = pad_lo;
+  // tile origins at 8 ty - (pad & 1), 32 tx - (pad & 1): (origin + pad) is even
+  a.tiles_x = cdiv(Wd + (pad_lo & 1), 32); a.tiles_y = cdiv(H + (pad_lo & 1), 8);
+  const int groups = dw_fused_s2_groups(N, H, Wd, C, K);
+  a.tiles_per_block = cdiv((long)N * a.tiles_x * a.tiles_y, groups);
+  dim3 grid(groups, cdiv(C, CB), 1);
+  if (K == 3) hipLaunchKernelGGL((dw_bwd_fused_s2_kernel<3>), grid, dim3(256), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL((dw_bwd_fused_s2_kernel<5>), grid, dim3(256), 0, (hipStream_t)stream, a);
+  MX_LAUNCH_CHECK();
+  if (dW) {                        // dW == null: the caller adds the partial rows later (mx_dw_parts_reduce)
     launch_dw_parts_reduce(dw_scratch, groups, C * K * K, dW, (hipStream_t)stream);
     MX_LAUNCH_CHECK();
   }

@@ -16,7 +16,8 @@ Per block, backward:
     g_out --BN2 bwd (reduce, finalise, apply)--> dp --pw_wgrad / pw_dgrad--> dA
     (dA, d_raw) --se_bn1_pool (one pass: SE gate gradient + BN1 backward sums per sample)--> se_bwd --> gh --bn1_coeffs--> add, c1..c3
     stride 1: dwconv_bwd_fused[BN1 data gradient on the fly; dW, dX, *swish'(bn0), BN0 sums] --> gz
-    stride 2: bn_bwd_apply --> dwconv_bwd_weight, dwconv_bwd_data --> ge --BN0 bwd reduce
+    stride 2: dwconv_bwd_fused_s2[the same fusion over 8 x 32 input-pixel tiles, taps by pixel parity] --> gz
+              (DW_S2_FUSED off, or a plain depthwise input: bn_bwd_apply --> dwconv_bwd_weight, dwconv_bwd_data --> ge --BN0 bwd reduce)
     gz --BN0 finalise + apply--> de --pw_wgrad / pw_dgrad (+skip gradient)--> g_in
 With save=False (no backward will follow) every tensor only backward would read is released as the forward goes.
 """
@@ -381,6 +382,13 @@ class GradSink:
 # forming dZ in their operand loads trades a 3-pass kernel for one more operand stream in two kernels that wait on memory anyway.
 # MUSCLE_FOLD_BN0_EARLY=0 restores the pass.  (The folds that were measured and lost are in DESIGN.md; their kernels are lab code.)
 FOLD_BN0_EARLY = os.environ.get("MUSCLE_FOLD_BN0_EARLY", "1") == "1"
+# The stride-2 blocks hand over BN0 partial sums too since their depthwise backward is fused, so B7's block 4 (1.6 M rows, 192 -> 32)
+# would qualify.  Measured with that block forced onto and off the fold, alternating on one MI355X: 93.41 against 93.44 ms per step,
+# inside either setting's own spread (profiles/dw_s2_fused_ab.txt) - no gain to tell from noise, so the stride-2 blocks keep the plain
+# apply and the fold stays what it was: stride-1 blocks only.
+# Stride-2 depthwise backward as ONE kernel (ops.dwconv_bwd_fused_s2), as stride 1 has had it since round 1.  MUSCLE_DW_S2_FUSED=0
+# (or flipping `engine.DW_S2_FUSED` at run time) restores bn_bwd_apply + dwconv_bwd_weight + dwconv_bwd_data + the BN0 reduction.
+DW_S2_FUSED = os.environ.get("MUSCLE_DW_S2_FUSED", "1") == "1"
 # Weight-gradient GEMMs on a second HIP stream (MUSCLE_WGRAD_STREAM=0 turns it off; `engine.WGRAD_SIDE_STREAM` can be
 # flipped at run time).  Nothing in the backward chain consumes them (only the optimizer and the gradient exchange do),
 # they are MFMA-bound, and the chain between two of them (BN backward, SE, depthwise) is HBM-bound.  Measured on
@@ -504,6 +512,11 @@ def _depthwise_backward(lane, tape: Tape, t: BlockTape, m, ga, c1, add, skip_res
         return ops.dwconv_bwd_fused(ga.view(N, t.Ho, t.Wo, b.cexp), t.d_raw, t.gate, add, t.bn1, c1, dw_in, dw_st,
                                     m._depthwise_conv.weight, sink.of(m._depthwise_conv.weight), b.kernel, b.pad_lo,
                                     residual=res, defer=lane.dw_reduce)
+    if DW_S2_FUSED and b.stride == 2 and dw_st is not None:
+        # stride 2 behind a BatchNorm (every stride-2 block of the model family has an expand conv): the same fusion
+        return ops.dwconv_bwd_fused_s2(ga.view(N, t.Ho, t.Wo, b.cexp), t.d_raw, t.gate, add, t.bn1, c1, dw_in, dw_st,
+                                       m._depthwise_conv.weight, sink.of(m._depthwise_conv.weight), b.kernel, b.pad_lo,
+                                       defer=lane.dw_reduce)
     # BN1 backward with g = (ga*gate + add) * swish'(bn1(d_raw)), in place over ga
     dd = ops.bn_backward_from_coeffs(ga, t.d_raw.view(N * t.Ho * t.Wo, b.cexp), t.bn1, c1, gate=t.gate, gate_add=add,
                                      rows_per_sample=t.Ho * t.Wo, out=ga).view(N, t.Ho, t.Wo, b.cexp)
@@ -523,7 +536,7 @@ def _bn0_expand_backward(lane, backbone, cfg: NetCfg, tape: Tape, t: BlockTape, 
     if part0 is not None:
         c0 = ops.bn_bwd_coeffs(part0, M, bn_mod, dw_st, sink.of(bn_mod.weight), sink.of(bn_mod.bias), training)
         wtp = tape.wtp.get(id(m._expand_conv.weight)) if b.expand else None
-        if FOLD_BN0_EARLY and wtp is not None and ops.bnbwd_fold_takes(M, b.cexp, b.cin) == "small":
+        if FOLD_BN0_EARLY and b.stride == 1 and wtp is not None and ops.bnbwd_fold_takes(M, b.cexp, b.cin) == "small":
             # the early fold: both GEMMs form dz in their operand loads, it is never written
             lane.wgrad_bnbwd(gx2, raw2, c0, t.x.view(M, b.cin), sink.of(m._expand_conv.weight).view(b.cexp, b.cin))
             g_in = ops.pw_dgrad_bnbwd_planes(gx2, raw2, c0, wtp, b.cin, residual=res)

@@ -524,6 +524,24 @@ def dwconv_bwd_fused(dA, D, gate, add, st1: BNState, c1, X, st0: Optional[BNStat
     return (gX, part, None) if bn0 is not None else (gX, part)
 
 
+def dwconv_bwd_fused_s2(dA, D, gate, add, st1: BNState, c1, X, st0: BNState, W, dW, K, pad_lo, *, defer=None):
+    """Stride-2 fused backward of BN0+SiLU -> dwconv (static same padding) -> BN1 -> SiLU -> gate; returns (gX, BN0 partial sums).
+    dA, D: [N, Ho, Wo, C]; X: [N, H, Wd, C].  defer: as in dwconv_bwd_fused."""
+    N, H, Wd, C = X.shape
+    _, Ho, Wo, _ = D.shape
+    gX = _f32(N, H, Wd, C, device=X.device)
+    P = lib().mx_dwconv_bwd_fused_s2_parts(N, H, Wd, C, K)
+    part = _f32(P, 2, C, device=X.device)
+    scratch = _f32(P, C * K * K, device=X.device)
+    cb, cs = c1.data_ptr(), 4 * c1.shape[1]
+    call("mx_dwconv_bwd_fused_s2", ptr(dA), ptr(D), ptr(gate), ptr(add), ptr(st1.scale), ptr(st1.shift), cb, cb + cs, cb + 2 * cs,
+         ptr(X), ptr(st0.scale), ptr(st0.shift), ptr(W), ptr(gX), None if defer is not None else ptr(dW), ptr(scratch), ptr(part),
+         N, H, Wd, C, K, pad_lo, Ho, Wo, stream())
+    if defer is not None:
+        defer(scratch, dW)
+    return gX, part
+
+
 def se_bn1_pool(dA2d, X2d, st: BNState, rows_per_sample):
     rows, C = X2d.shape
     N = rows // rows_per_sample

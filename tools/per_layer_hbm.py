@@ -21,15 +21,17 @@ dwf = [r for r in ph if 'dw_fwd_kernel' in r['Kernel_Name']]
 # backward: stride-1 blocks run ONE fused kernel (3 reads + 1 write: dA, d, e in, gX out = 2 d + 2 e); stride-2 blocks run
 # dw_bwd_weight (reads e and dd: e + d) and dw_bwd_data (reads dd, writes gX: d + e) behind a bn_bwd_apply pass of their own -
 # round 3 priced the stride-2 rows' dw_bwd_data alone with the fused kernel's 2 d + 2 e (rows above 8 TB/s): each kernel now
-# has its own byte model and its own column entry
-dwb = list(reversed([r for r in ph if 'dw_bwd_fused' in r['Kernel_Name']]))
+# has its own byte model and its own column entry.  With engine.DW_S2_FUSED (the default) the stride-2 blocks run ONE
+# dw_bwd_fused_s2_kernel too, priced like the stride-1 kernel: 2 d + 2 e
+dwb = list(reversed([r for r in ph if 'dw_bwd_fused_kernel' in r['Kernel_Name']]))
+dwb2 = list(reversed([r for r in ph if 'dw_bwd_fused_s2_kernel' in r['Kernel_Name']]))
 dwbw = list(reversed([r for r in ph if 'dw_bwd_weight' in r['Kernel_Name']]))
 dwbd = list(reversed([r for r in ph if 'dw_bwd_data' in r['Kernel_Name']]))
 N, h = 32, 224
 print("B7 / 448x448 / batch 32, one step; us and TB/s of algorithmic bytes (d = depthwise output, e = depthwise input, both Cexp wide)")
-print("blk  Cexp  Hin Hout k s | squeeze (1 d)  | se_bn1_pool (2 d) | dw forward (e + d) | dw backward: stride 1 fused (2 d + 2 e); stride 2 weight (e + d) + data (d + e)")
+print("blk  Cexp  Hin Hout k s | squeeze (1 d)  | se_bn1_pool (2 d) | dw forward (e + d) | dw backward: stride 1 / stride 2 fused (2 d + 2 e); stride 2 unfused: weight (e + d) + data (d + e)")
 tot, ideal = collections.Counter(), collections.Counter()
-i1 = i2 = 0
+i1 = i2 = i3 = 0
 for i, blk in enumerate(cfg.blocks):
     ho = blk.out_size(h)
     d, e = N * ho * ho * blk.cexp * 4, N * h * h * blk.cexp * 4
@@ -42,6 +44,9 @@ for i, blk in enumerate(cfg.blocks):
     if blk.stride == 1 and i1 < len(dwb):
         t = dur(dwb[i1]); i1 += 1
         cells.append("%7.1f %5.2f" % (t, (2 * d + 2 * e) / t / 1e6)); tot["dw_bwd"] += t; ideal["dw_bwd"] += (2 * d + 2 * e) / 5e6
+    elif blk.stride == 2 and i3 < len(dwb2):
+        t = dur(dwb2[i3]); i3 += 1
+        cells.append("fused_s2 %6.1f %5.2f" % (t, (2 * d + 2 * e) / t / 1e6)); tot["dw_bwd_s2"] += t; ideal["dw_bwd_s2"] += (2 * d + 2 * e) / 5e6
     elif blk.stride == 2 and i2 < len(dwbw) and i2 < len(dwbd):
         tw, td = dur(dwbw[i2]), dur(dwbd[i2]); i2 += 1
         cells.append("weight %6.1f %5.2f, data %6.1f %5.2f" % (tw, (e + d) / tw / 1e6, td, (d + e) / td / 1e6))
