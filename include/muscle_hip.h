@@ -401,6 +401,26 @@ int mx_mask_stage(const void* src, const int* jobs, const int* tabs, float* dst,
  * Bit-exact with the numpy expressions. */
 int mx_seg_input_stage(const unsigned char* src, const int* jobs, float* dst, int n, int Hd, int Wd, void* stream);
 
+/* ---- input stage of IRN training (VOC12AffinityDataset.__getitem__, src/data.py:659-705) ---------------------------------
+ * mx_irn_input_stage: one launch writes both outputs of a batch of n items, S = crop size (S % 16 == 0):
+ *   img[n,3,S,S] (fp32, fully written) = TorchvisionNormalize (src/data.py:596-609: fp64 (u8 / 255 - mean) / std, one
+ *     rounding to fp32) of the rescaled uint8 HWC image [sh,sw,3] at src + img_off, random_lr_flip applied BEFORE the
+ *     crop (the rescaled image is mirrored, not the container), random_crop's container with fill 0, CHW:
+ *       img[c, cont_top + y, cont_left + x] = norm(I[img_top + y, flip ? sw-1-(img_left + x) : img_left + x, c]),
+ *       0 <= y < ch, 0 <= x < cw; 0 elsewhere.
+ *   label[n,S/4,S/4] (uint8, fully written; NULL = the eval view, nothing written) = the ORIGINAL label [lh,lw] at
+ *     src + lab_off through pil_rescale(NEAREST) to [sh,sw], the same flip, the container with fill 255 and
+ *     pil_rescale(., 0.25, NEAREST) - which reads container pixel (4Y+2, 4X+2) - as one gather:
+ *       (y, x) = (4Y+2 - cont_top, 4X+2 - cont_left); inside the window:
+ *       label[Y, X] = L[ytab[img_top + y], xtab[flip ? sw-1-(img_left + x) : img_left + x]]; 255 elsewhere.
+ *     ytab[sh] / xtab[sw] (int32, at tabs + ytab_off / xtab_off words) are Pillow's NEAREST source indices per axis
+ *     (muscle_amd/irndata.py:nearest_table); indices are clamped to the label.  lab_off < 0: no label, all 255.
+ * src: one device buffer holding every image and label; jobs: n x 16 int32 {img_off, sh, sw, img_top, img_left, cont_top,
+ * cont_left, ch, cw, flip, lab_off, lh, lw, ytab_off, xtab_off, 0}, byte offsets into src; the tables are trusted device
+ * data.  Bit-exact with the numpy / PIL expressions.  No atomics; the call only enqueues on the stream. */
+int mx_irn_input_stage(const unsigned char* src, const int* jobs, const int* tabs, float* img, unsigned char* label, int n, int S,
+                       void* stream);
+
 /* ---- IRN random-walk propagation (src/indexing.py:77-142 as called by infer_irn.py:76).
  * mx_irn_affinity: dense[n4][ld] (zero-filled here) <- symmetric affinity 1 - max(edge along the straight path) for every
  *   pixel pair joined by one of the nd search directions, unit diagonal; edge [h,w]; pcoord = int32 (dy,dx) pairs of all

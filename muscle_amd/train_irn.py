@@ -13,7 +13,10 @@ What a caller should know:
     writes them from the CAM dicts of `infer_mcl`;
   * the loader is the host-side restatement of VOC12AffinityDataset with PIL and numpy, draws in the reference's order; it ships
     the reduced uint8 label map [crop/4, crop/4], never the three [n_dst, n_src] float label tensors - the loss kernel derives
-    the pair labels on the fly.
+    the pair labels on the fly;
+  * --loader device leaves only decoding and the draws to the workers and does the pixel work of both the training loop and
+    the displacement-mean pass on the GPU (muscle_amd.irndata: mx_resample + mx_irn_input_stage); the tensors are the host
+    loader's bit for bit, the host loader stays the default.
 """
 from __future__ import annotations
 
@@ -139,6 +142,9 @@ def parse_args(argv: Optional[List[str]] = None):
     ap.add_argument("--irn_weight_decay", default=1e-4, type=float,
                     help="handed to PolyOptimizer as the reference does: it becomes SGD's momentum (see muscle_amd.optim)")
     ap.add_argument("--num_workers", default=8, type=int)
+    ap.add_argument("--loader", default="host", choices=("host", "device"),
+                    help="host: the workers build the float32 samples; device: they decode and plan only and the GPU rescales, "
+                         "normalises, flips, crops and reduces the label (muscle_amd.irndata), the same tensors bit for bit")
     ap.add_argument("--seed", default=0, type=int)
     args = ap.parse_args(argv)
     if args.irn_crop_size % 16:
@@ -164,9 +170,16 @@ def main(argv: Optional[List[str]] = None) -> int:
     load_backbone(model, args.backbone_weights)
     model = model.to(dev)
     names = read_names(args.train_list)
-    train = VOC12AffinityDataset(names, args.voc12_root, args.ir_label_dir, args.irn_crop_size)
-    loader = DataLoader(train, batch_size=args.irn_batch_size, shuffle=True, num_workers=args.num_workers, pin_memory=True,
-                        drop_last=True)
+    if args.loader == "device":
+        # the same sampler, worker seeding and draws as below; the batches arrive as device tensors (muscle_amd.irndata)
+        from muscle_amd.irndata import IrnLoader, VOC12AffinityPlans
+        train = VOC12AffinityPlans(names, args.voc12_root, args.ir_label_dir, args.irn_crop_size)
+        loader = IrnLoader(train, args.irn_batch_size, dev, num_workers=args.num_workers, shuffle=True, drop_last=True,
+                           persistent_workers=False)
+    else:
+        train = VOC12AffinityDataset(names, args.voc12_root, args.ir_label_dir, args.irn_crop_size)
+        loader = DataLoader(train, batch_size=args.irn_batch_size, shuffle=True, num_workers=args.num_workers, pin_memory=True,
+                            drop_last=True)
     max_step = (len(train) // args.irn_batch_size) * args.irn_num_epoches
     edge_params, dp_params = model.trainable_parameters()
     optimizer = muscle_amd.PolyOptimizer([{"params": edge_params, "lr": 1 * args.irn_learning_rate},
@@ -188,8 +201,13 @@ def main(argv: Optional[List[str]] = None) -> int:
     # the mean displacement over the list becomes mean_shift.running_mean
     model.eval()
     model.mean_shift.running_mean.zero_()
-    infer = DataLoader(VOC12AffinityDataset(names, args.voc12_root, args.ir_label_dir, args.irn_crop_size, train=False),
-                       batch_size=args.irn_batch_size, shuffle=False, num_workers=args.num_workers, drop_last=False)
+    if args.loader == "device":
+        infer = IrnLoader(VOC12AffinityPlans(names, args.voc12_root, args.ir_label_dir, args.irn_crop_size, train=False),
+                          args.irn_batch_size, dev, num_workers=args.num_workers, shuffle=False, drop_last=False,
+                          persistent_workers=False)
+    else:
+        infer = DataLoader(VOC12AffinityDataset(names, args.voc12_root, args.ir_label_dir, args.irn_crop_size, train=False),
+                           batch_size=args.irn_batch_size, shuffle=False, num_workers=args.num_workers, drop_last=False)
     print("Analyzing displacements mean ... ", end="", flush=True)
     total, count = torch.zeros(2, dtype=torch.float64, device=dev), 0
     for pack in infer:
