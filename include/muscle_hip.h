@@ -362,11 +362,16 @@ int mx_seg_infer_batch(const long* rows, int nrow, int B, int lds, int K, int H,
                        float* prob, const unsigned char* gt, long long* counts, void* stream);
 
 /* ---- input stage (src/data.py:215-332, src/imutils.py:143-181,376-388) ------------------------------
- * dst[n,3,Hd,Wd] (fp32, fully written) = RandomCrop container of color_norm(uint8 HWC crop n) at (top,left), CHW, zeros
- * elsewhere; src = packed crops, jobs = n x 8 int32 {src_off, sh, sw, top, left, ey | ex<<16, eh | ew<<16, source row
- * stride in pixels or 0 = sw}, both on the
- * device; the e* box (0 = none) is RandomErasing(value=0) of train_mcl.py:114 in output coordinates.
- * Bit-exact with the numpy expressions (fp64 (x/255 - mean)/std, one rounding to fp32). */
+ * mx_input_stage: dst[n,3,Hd,Wd] (fp32, fully written) = color_norm + crop container + flip + RandomErasing + CHW of n
+ * uint8 HWC sources inside src (RandomCrop src/imutils.py:143-181, RandomCropWithMask :110-112, the flip of :288-289).
+ * jobs: n x 12 int32 {src_off, row_stride, col_step, top, left, h, w, ey | ex<<16, eh | ew<<16, 0, 0, 0}, on the device.
+ *   inside the window top <= y < top+h, left <= x < left+w (output coordinates):
+ *     dst[c, y, x] = norm(src[src_off + ((y-top) * row_stride + (x-left) * col_step) * 3 + c]);  0 outside it;
+ *   then 0 inside the box ey <= y < ey+eh, ex <= x < ex+ew (RandomErasing(value=0) of train_mcl.py:114; 0 = none).
+ * src_off is the byte offset of the pixel that lands on (top, left), row_stride is in pixels, col_step is +1 or -1: a
+ * crop [ch,cw] at (ct,cl) of a container that is then flipped is the window left = Wd-cl-cw with src_off at the crop's
+ * last column and col_step -1.  The jobs are trusted device data (as the tables of mx_irn_input_stage are).
+ * norm = (float)(((double)u8 / 255 - mean[c]) / std[c]): bit-exact with the numpy expressions. */
 int mx_input_stage(const unsigned char* src, const int* jobs, float* dst, int n, int Hd, int Wd, void* stream);
 
 /* transforms.ColorJitter (train_mcl.py:108, src/data.py:223; torchvision 0.9.0 PIL backend = Pillow's ImagingBlend, rgb2l,
@@ -394,12 +399,9 @@ int mx_resample(const unsigned char* src, const int* jobs, const int* tabs, unsi
  * container), flip, ky, kx (taps per row / column), ty_off, tx_off (int32 words into tabs), 0, 0, 0}; tabs at t*_off:
  * start[ch | cw] (first source row / column, relative to the shipped rows) then [ch | cw][k] float32 weights.
  * span_cap >= the longest run of source columns 64 neighbouring window columns read (start[x+63] + kx - start[x]); it
- * sizes the LDS tile.  fp32 accumulation in a fixed order, no atomics. */
+ * sizes the LDS tile.  fp32 accumulation in a fixed order, no atomics.  The image of the same item goes through
+ * mx_input_stage. */
 int mx_mask_stage(const void* src, const int* jobs, const int* tabs, float* dst, int n, int C, int S, int span_cap, void* stream);
-/* mx_input_stage (color_norm src/imutils.py:383-388, crop container src/imutils.py:110-112, CHW, fp32) plus the flip of
- * src/imutils.py:288-289; jobs: n x 8 int32 {src_off, sh, sw, top, left, source row stride in pixels or 0 = sw, flip, 0}.
- * Bit-exact with the numpy expressions. */
-int mx_seg_input_stage(const unsigned char* src, const int* jobs, float* dst, int n, int Hd, int Wd, void* stream);
 
 /* ---- input stage of IRN training (VOC12AffinityDataset.__getitem__, src/data.py:659-705) ---------------------------------
  * mx_irn_input_stage: one launch writes both outputs of a batch of n items, S = crop size (S % 16 == 0):

@@ -7,9 +7,13 @@
 // the same order, one rounding to fp32.
 #include "common.h"
 
-struct InputJob { int src_off, sh, sw, top, left, erase_yx, erase_hw, sstride; };   // uint8 HWC crop [sh, sw, 3] placed at (top, left);
-// erase_yx = y | x << 16, erase_hw = h | w << 16 of RandomErasing's box in the OUTPUT tensor (0 = none);
-// sstride = row stride of the source in pixels (0 = sw: a packed crop; > sw: a crop inside a larger, jittered image)
+// One job = one output image.  The window [top, top + h) x [left, left + w) of the output (RandomCrop's container, output
+// coordinates) reads the uint8 HWC source: output (y, x) inside it takes the pixel at byte
+//   src_off + ((y - top) * row_stride + (x - left) * col_step) * 3,        row_stride in pixels, col_step +1 or -1;
+// outside it the output is 0.  src_off is the pixel that lands on (top, left): a window of a flipped container
+// (RandomHorizontalFlipWithMask) starts at its crop's LAST column and steps -1.  Then RandomErasing's box, in output
+// coordinates: erase_yx = y | x << 16, erase_hw = h | w << 16 (0 = none).  The jobs are trusted device data.
+struct InputJob { int src_off, row_stride, col_step, top, left, h, w, erase_yx, erase_hw, pad0, pad1, pad2; };
 
 __global__ __launch_bounds__(256) void input_stage_kernel(const unsigned char* __restrict__ src, const InputJob* __restrict__ jobs,
                                                           float* __restrict__ dst, int Hd, int Wd) {
@@ -21,9 +25,9 @@ __global__ __launch_bounds__(256) void input_stage_kernel(const unsigned char* _
   for (long p = blockIdx.x * 256L + threadIdx.x; p < plane; p += (long)gridDim.x * 256) {
     const int y = (int)(p / Wd), x = (int)(p - (long)y * Wd);
     const int sy = y - jb.top, sx = x - jb.left;
-    float v[3] = {0.f, 0.f, 0.f};                         // RandomCrop's container is zero outside the pasted crop
-    if (sy >= 0 && sy < jb.sh && sx >= 0 && sx < jb.sw) {
-      const unsigned char* px = src + jb.src_off + ((long)sy * (jb.sstride > 0 ? jb.sstride : jb.sw) + sx) * 3;
+    float v[3] = {0.f, 0.f, 0.f};                         // the container is zero outside the pasted crop
+    if (sy >= 0 && sy < jb.h && sx >= 0 && sx < jb.w) {
+      const unsigned char* px = src + jb.src_off + ((long)sy * jb.row_stride + sx * jb.col_step) * 3;
 #pragma unroll
       for (int c = 0; c < 3; ++c) v[c] = (float)(((double)px[c] / 255.0 - mean[c]) / stdv[c]);   // imutils.py:383-388
     }
@@ -196,8 +200,7 @@ __global__ __launch_bounds__(256) void resample_v_kernel(const unsigned char* __
 
 extern "C" {
 
-// dst[n, 3, Hd, Wd] (fp32, fully written) <- color_norm(src crop n) placed at (top, left), zeros elsewhere.
-// src: packed uint8 HWC crops; jobs: n x 8 int32 {src_off, sh, sw, top, left, erase y|x<<16, erase h|w<<16, source row stride or 0}; both on the device.
+// dst[n, 3, Hd, Wd] (fp32, fully written) <- color_norm of job n's window, zeros elsewhere; jobs: n x 12 int32 (InputJob).
 int mx_input_stage(const unsigned char* src, const int* jobs, float* dst, int n, int Hd, int Wd, void* stream) {
   MX_CHECK_ARG(src && jobs && dst, "input_stage: null pointer");
   MX_CHECK_ARG(n > 0 && Hd > 0 && Wd > 0, "input_stage: bad extents n=%d Hd=%d Wd=%d", n, Hd, Wd);

@@ -2,7 +2,7 @@
 // what VOC12SegDataset.__getitem__ does per item on the host - skimage.transform.resize of the [H,W,21] soft label (a Gaussian
 // anti-alias filter + a bilinear warp over the WHOLE rescaled label in float64), RandomCropWithMask's zero container,
 // RandomHorizontalFlipWithMask, HWC -> CHW - as one batched kernel that computes the resized label only inside the crop
-// window, and the image half of the same transforms (color_norm, container, flip, CHW, fp32 cast).
+// window.  (The image half of the same transforms is mx_input_stage, csrc/input.hip.)
 //
 // The resize is separable and linear: per axis the host folds `bilinear o gaussian` (both with ndimage's 'mirror' boundary)
 // into one row of K = 2 + 2 * radius weights per output coordinate (muscle_amd/segdata.py:mask_axis_table), so
@@ -79,28 +79,6 @@ __global__ __launch_bounds__(256) void mask_stage_kernel(const unsigned char* __
   }
 }
 
-// mx_input_stage's job plus the flip bit of RandomHorizontalFlipWithMask
-struct SegInputJob { int src_off, sh, sw, top, left, sstride, flip, pad; };
-
-__global__ __launch_bounds__(256) void seg_input_stage_kernel(const unsigned char* __restrict__ src, const SegInputJob* __restrict__ jobs,
-                                                              float* __restrict__ dst, int Hd, int Wd) {
-  const SegInputJob jb = jobs[blockIdx.y];
-  const long plane = (long)Hd * Wd;
-  float* out = dst + (long)blockIdx.y * 3 * plane;
-  const double mean[3] = {0.485, 0.456, 0.406}, stdv[3] = {0.229, 0.224, 0.225};
-  for (long p = blockIdx.x * 256L + threadIdx.x; p < plane; p += (long)gridDim.x * 256) {
-    const int y = (int)(p / Wd), x = (int)(p - (long)y * Wd);
-    const int sy = y - jb.top, sx = (jb.flip ? Wd - 1 - x : x) - jb.left;
-    float v[3] = {0.f, 0.f, 0.f};
-    if (sy >= 0 && sy < jb.sh && sx >= 0 && sx < jb.sw) {
-      const unsigned char* px = src + jb.src_off + ((long)sy * (jb.sstride > 0 ? jb.sstride : jb.sw) + sx) * 3;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) v[c] = (float)(((double)px[c] / 255.0 - mean[c]) / stdv[c]);   // imutils.py:383-388
-    }
-    out[p] = v[0]; out[plane + p] = v[1]; out[2 * plane + p] = v[2];
-  }
-}
-
 extern "C" {
 
 int mx_mask_stage(const void* src, const int* jobs, const int* tabs, float* dst, int n, int C, int S, int span_cap, void* stream) {
@@ -111,17 +89,6 @@ int mx_mask_stage(const void* src, const int* jobs, const int* tabs, float* dst,
                span_cap, C);
   hipLaunchKernelGGL(mask_stage_kernel, dim3(cdiv(S, 64), S, n), dim3(256), (size_t)lds, (hipStream_t)stream, (const unsigned char*)src,
                      (const MaskJob*)jobs, tabs, dst, C, S, span_cap);
-  MX_LAUNCH_CHECK();
-  return MX_OK;
-}
-
-int mx_seg_input_stage(const unsigned char* src, const int* jobs, float* dst, int n, int Hd, int Wd, void* stream) {
-  MX_CHECK_ARG(src && jobs && dst, "seg_input_stage: null pointer");
-  MX_CHECK_ARG(n > 0 && Hd > 0 && Wd > 0, "seg_input_stage: bad extents n=%d Hd=%d Wd=%d", n, Hd, Wd);
-  const long plane = (long)Hd * Wd;
-  int bx = cdiv(plane, 256);
-  if (bx > 64) bx = 64;
-  hipLaunchKernelGGL(seg_input_stage_kernel, dim3(bx, n), dim3(256), 0, (hipStream_t)stream, src, (const SegInputJob*)jobs, dst, Hd, Wd);
   MX_LAUNCH_CHECK();
   return MX_OK;
 }

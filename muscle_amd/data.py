@@ -34,7 +34,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from ._lib import call, ptr, stream
+from ._lib import call, stream
+from ._stage import StageBuffer, input_stage_job, jitter_job, resample_job
 
 
 # ---- geometry (pure host logic) ------------------------------------------------------------------------------------
@@ -77,18 +78,19 @@ def resize_long_target(w: int, h: int, min_long=448, max_long=768):
     return (target_long, int(round(h * target_long / w)))
 
 
-def random_crop_box(h: int, w: int, cropsize: int):
-    """RandomCrop's draws (src/imutils.py:143-172; w first, then h) -> (cont_top, cont_left, img_top, img_left, ch, cw)."""
+def random_crop_box(h: int, w: int, cropsize: int, rng=random):
+    """RandomCrop's draws (src/imutils.py:143-172, :183-206; w first, then h) from `rng` -> (cont_top, cont_left, img_top,
+    img_left, ch, cw)."""
     ch, cw = min(cropsize, h), min(cropsize, w)
     w_space, h_space = w - cropsize, h - cropsize
     if w_space > 0:
-        cont_left, img_left = 0, random.randrange(w_space + 1)
+        cont_left, img_left = 0, rng.randrange(w_space + 1)
     else:
-        cont_left, img_left = random.randrange(-w_space + 1), 0
+        cont_left, img_left = rng.randrange(-w_space + 1), 0
     if h_space > 0:
-        cont_top, img_top = 0, random.randrange(h_space + 1)
+        cont_top, img_top = 0, rng.randrange(h_space + 1)
     else:
-        cont_top, img_top = random.randrange(-h_space + 1), 0
+        cont_top, img_top = rng.randrange(-h_space + 1), 0
     return cont_top, cont_left, img_top, img_left, ch, cw
 
 
@@ -273,132 +275,74 @@ def plan_item(pil_img, crop_size: int = 448, view_size=(224, 224), resize_long=(
 
 # ---- device stage -----------------------------------------------------------------------------------------------------
 class InputStager:
-    """Packs the uint8 images of a batch into one pinned buffer, copies it once and runs the device half:
+    """Packs jobs, tables and the uint8 images of a batch into one pinned buffer (`_stage.StageBuffer`: two alternate, they
+    grow), copies it once and runs the device half:
     [mx_resample: RandomResizeLong] -> [mx_color_jitter: ColorJitter of image and views] -> mx_input_stage x 3 (color_norm,
     RandomCrop container, RandomErasing box, CHW, fp32).  Which of the bracketed steps run is decided by what the plans
-    carry (`plan_item(device_resize=..., device_jitter=...)`).  Two pinned buffer sets alternate so that packing batch t+1
-    does not wait for the copy of batch t."""
+    carry (`plan_item(device_resize=..., device_jitter=...)`)."""
 
-    def __init__(self, device, batch: int, crop_size: int = 448, view_size=(224, 224), max_long: int = 768, max_src: int = 1024):
+    def __init__(self, device, batch: int, crop_size: int = 448, view_size=(224, 224)):
         self.dev, self.n, self.crop, self.view = device, batch, crop_size, view_size
-        side = max(crop_size, max_long)
-        cap = batch * (max(side, max_src) ** 2 + 2 * view_size[0] * view_size[1]) * 3     # whole source / resized images + views
-        pin = (lambda t: t.pin_memory()) if torch.cuda.is_available() else (lambda t: t)
-        words = 3 * batch * 8
-        tab_words = batch * (2 + 2 * side * (2 + 13))       # per image: two axes, <= `side` outputs, bounds + <= 13 taps
-        self._pin = [pin(torch.empty(cap, dtype=torch.uint8)) for _ in range(2)]
-        self._jobs_pin = [pin(torch.empty(words, dtype=torch.int32)) for _ in range(2)]
-        self._jit_pin = [pin(torch.empty(words, dtype=torch.int32)) for _ in range(2)]
-        self._rs_pin = [pin(torch.empty(batch * 8, dtype=torch.int32)) for _ in range(2)]
-        self._tab_pin = [pin(torch.empty(tab_words, dtype=torch.int32)) for _ in range(2)]
-        self._dev_u8 = torch.empty(cap, dtype=torch.uint8, device=device)
-        self._dev_jobs = torch.empty(words, dtype=torch.int32, device=device)
-        self._dev_jit = torch.empty(words, dtype=torch.int32, device=device)
-        self._dev_sums = torch.empty(3 * batch, dtype=torch.int64, device=device)
-        self._dev_rs_jobs = torch.empty(batch * 8, dtype=torch.int32, device=device)
-        self._dev_tab = torch.empty(tab_words, dtype=torch.int32, device=device)
-        self._dev_rs = self._dev_tmp = None                 # resized images / horizontal-pass images: allocated on first use
-        self._side, self._max_src = side, max_src
-        self._flip = 0
-        self._evt = [None, None]
+        self.buf = StageBuffer(device)
 
-    @staticmethod
-    def _jitter_words(params):
-        order, fb, fc, fs, fh = params
-        code = 0
-        for pos in range(4):
-            fn = order[pos]
-            code |= (fn if (fb, fc, fs, fh)[fn] is not None else 15) << (4 * pos)
-        return code, (fb or 0.0, fc or 0.0, fs or 0.0), ((int(fh * 255) & 0xFF) if fh is not None else 0)
+    @property
+    def last_bytes(self) -> int:
+        return self.buf.last_bytes
 
     def __call__(self, plans: Sequence[ItemPlan], labels: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
-        n = len(plans)
-        assert n <= self.n
-        k = self._flip
-        self._flip ^= 1
-        if self._evt[k] is not None:
-            self._evt[k].synchronize()                      # the copies out of this pinned set two batches ago are done
-        buf, jobs = self._pin[k].numpy(), self._jobs_pin[k].numpy().reshape(3 * self.n, 8)
-        jit = self._jit_pin[k].numpy().reshape(3 * self.n, 8)
-        jit_f = jit.view(np.float32)
-        rsj, tab = self._rs_pin[k].numpy().reshape(self.n, 8), self._tab_pin[k].numpy()
-        resize = getattr(plans[0], "resize_to", None) is not None
-        assert all((getattr(p, "resize_to", None) is not None) == resize for p in plans), "one resize mode per batch"
-        jobs[:] = 0
-        jit[:] = 0
-        jit[:, 3] = 0xFFFF                                  # order nibbles: nothing to do
-        off = tab_off = tmp_off = rs_off = 0
-        jit_px = [1, 1]                                      # largest image among the jitter jobs of (image, views)
+        n, sb = len(plans), self.buf
+        assert 0 < n <= self.n
+        resize = plans[0].resize_to is not None
+        assert all((p.resize_to is not None) == resize for p in plans), "one resize mode per batch"
+        srcs = ([p.img_u8 for p in plans], [p.view1_u8 for p in plans], [p.view2_u8 for p in plans])
+        # ---- layout: [stage jobs x3 | jitter jobs x3 | resample jobs | tables | images | views]; behind it, on the device
+        # only: [resized images | horizontal-pass temporaries | the jitter's sums]
+        sb.plan()
+        o_jobs, o_jit, o_rs = sb.reserve(3 * n * 48, 64), sb.reserve(3 * n * 32, 64), sb.reserve(n * 32, 64)
+        tab_at = [sb.reserve(p.tables.nbytes) for p in plans] if resize else []
+        at = [[sb.reserve(a.size) for a in arrs] for arrs in srcs]
+        rs_at = [sb.scratch(p.resize_to[0] * p.resize_to[1] * 3) for p in plans] if resize else []
+        tmp_at = [sb.scratch(p.img_u8.shape[0] * p.resize_to[0] * 3) for p in plans] if resize else []
+        o_sums = sb.scratch(3 * n * 8)
+        buf = sb.begin()
+        jobs = buf[o_jobs:o_jobs + 3 * n * 48].view(np.int32).reshape(3 * n, 12)
+        jit = buf[o_jit:o_jit + 3 * n * 32].view(np.int32).reshape(3 * n, 8)
+        rsj = buf[o_rs:o_rs + n * 32].view(np.int32).reshape(n, 8)
+        rs_px, jit_px = 1, [1, 1]                               # largest image among the resample / jitter jobs of (image, views)
         any_jit = False
-        for kind, (get, place) in enumerate(((lambda p: p.img_u8, lambda p: p.img_place),
-                                             (lambda p: p.view1_u8, lambda p: (0, 0)),
-                                             (lambda p: p.view2_u8, lambda p: (0, 0)))):
-            for i, p in enumerate(plans):
-                a = get(p)
-                sz = a.size
-                buf[off:off + sz] = a.reshape(-1)
-                top, left = place(p)
-                row = kind * self.n + i
-                h, w, base = a.shape[0], a.shape[1], off    # the image the jitter / the stage will see, and where it starts
-                if kind == 0 and resize:                     # RandomResizeLong on the device: source -> tmp -> resized
+        for kind, arrs in enumerate(srcs):
+            for i, (p, a) in enumerate(zip(plans, arrs)):
+                off = at[kind][i]
+                buf[off:off + a.size] = a.reshape(-1)
+                h, w = a.shape[:2]                              # the image the jitter / the stage will see, and where it starts
+                if kind == 0 and resize:                        # RandomResizeLong on the device: source -> tmp -> resized
                     tw, th = p.resize_to
-                    if max(th, tw) > self._side or max(h, w) > self._max_src:
-                        raise ValueError(f"image {w}x{h} -> {tw}x{th} exceeds the stager's max_src / max_long")
-                    t = p.tables
-                    if tab_off + t.size > tab.size:
-                        raise ValueError("resample tables exceed the stager's table buffer (a very strong downscale): raise max_src / max_long")
-                    tab[tab_off:tab_off + t.size] = t
-                    rsj[i] = (off, h, w, tmp_off, rs_off, tw, th, tab_off)
-                    tab_off += t.size
-                    tmp_off += h * tw * 3
-                    h, w, base = th, tw, rs_off
-                    rs_off += th * tw * 3
-                jobs[row, :5] = (base, h, w, top, left)
-                pj = getattr(p, "jitter", None)
-                if pj is not None:                                   # ColorJitter still to be applied: on the device
-                    code, facs, hue = self._jitter_words(pj[kind])
-                    jit[row, :4] = (base, h, w, code)
-                    jit_f[row, 4:7] = facs
-                    jit[row, 7] = hue
+                    buf[tab_at[i]:tab_at[i] + p.tables.nbytes] = p.tables.view(np.uint8)
+                    rsj[i] = resample_job(off, h, w, tmp_at[i], rs_at[i], tw, th, tab_at[i])
+                    rs_px = max(rs_px, h * tw, th * tw)
+                    h, w, off = th, tw, rs_at[i]
+                pj = p.jitter[kind] if p.jitter is not None else None   # ColorJitter still to be applied: on the device
+                jit[kind * n + i] = jitter_job(off, h, w, pj)
+                if pj is not None:
                     any_jit = True
                     jit_px[min(kind, 1)] = max(jit_px[min(kind, 1)], h * w)
-                if kind == 0 and getattr(p, "img_crop", None) is not None:   # the stage reads the crop window inside the whole image
-                    it, il, ch, cw = p.img_crop
-                    jobs[row, :3] = (base + (it * w + il) * 3, ch, cw)
-                    jobs[row, 7] = w
-                er = getattr(p, "erase", None) if kind == 0 else None
-                if er is not None:                                   # RandomErasing box of the image, output coordinates
-                    jobs[row, 5] = er[0] | (er[1] << 16)
-                    jobs[row, 6] = er[2] | (er[3] << 16)
-                off += sz
-        self._dev_u8[:off].copy_(self._pin[k][:off], non_blocking=True)
-        self._dev_jobs.copy_(self._jobs_pin[k], non_blocking=True)
-        if any_jit:
-            self._dev_jit.copy_(self._jit_pin[k], non_blocking=True)
+                top, left, win, erase = 0, 0, (0, 0, h, w), None
+                if kind == 0:
+                    (top, left), erase = p.img_place, p.erase
+                    if p.img_crop is not None:                  # the stage reads the crop window inside the whole image
+                        win = p.img_crop
+                jobs[kind * n + i] = input_stage_job(off + (win[0] * w + win[1]) * 3, w, top, left, win[2], win[3], erase=erase)
+        base, st = sb.upload(), stream()
         if resize:
-            self._dev_rs_jobs.copy_(self._rs_pin[k], non_blocking=True)
-            self._dev_tab[:tab_off].copy_(self._tab_pin[k][:tab_off], non_blocking=True)
-        evt = torch.cuda.Event()
-        evt.record()
-        self._evt[k] = evt
-        img_src = self._dev_u8
-        if resize:
-            if self._dev_rs is None:
-                self._dev_rs = torch.empty(self.n * self._side * self._side * 3, dtype=torch.uint8, device=self.dev)
-                self._dev_tmp = torch.empty(self.n * self._max_src * self._side * 3, dtype=torch.uint8, device=self.dev)
-            call("mx_resample", ptr(self._dev_u8), ptr(self._dev_rs_jobs), ptr(self._dev_tab), ptr(self._dev_tmp), ptr(self._dev_rs), n,
-                 self._max_src * self._side, stream())
-            img_src = self._dev_rs
-        if any_jit:
-            call("mx_color_jitter", ptr(img_src), ptr(self._dev_jit), ptr(self._dev_sums), n, int(jit_px[0]), stream())
-            call("mx_color_jitter", ptr(self._dev_u8), self._dev_jit.data_ptr() + 4 * 8 * self.n, self._dev_sums.data_ptr() + 8 * self.n,
-                 2 * self.n, int(jit_px[1]), stream())
+            call("mx_resample", base, base + o_rs, base, base, base, n, int(rs_px), st)
+        if any_jit:                                             # image and views apart: their sizes differ by up to 10x
+            call("mx_color_jitter", base, base + o_jit, base + o_sums, n, int(jit_px[0]), st)
+            call("mx_color_jitter", base, base + o_jit + 32 * n, base + o_sums + 8 * n, 2 * n, int(jit_px[1]), st)
         img = torch.empty(n, 3, self.crop, self.crop, dtype=torch.float32, device=self.dev)
         v1 = torch.empty(n, 3, self.view[0], self.view[1], dtype=torch.float32, device=self.dev)
         v2 = torch.empty_like(v1)
         for kind, dst in enumerate((img, v1, v2)):
-            call("mx_input_stage", ptr(img_src if kind == 0 else self._dev_u8), self._dev_jobs.data_ptr() + 4 * 8 * kind * self.n, ptr(dst), n,
-                 dst.shape[2], dst.shape[3], stream())
+            call("mx_input_stage", base, base + o_jobs + 48 * kind * n, dst.data_ptr(), n, dst.shape[2], dst.shape[3], st)
         out = {"img": img, "view1": v1, "view2": v2,
                "coord1": torch.tensor([p.coord1 for p in plans], dtype=torch.int64, device=self.dev),
                "coord2": torch.tensor([p.coord2 for p in plans], dtype=torch.int64, device=self.dev),
@@ -484,36 +428,49 @@ class StagedLoader:
 
 class MSFStager:
     """The multi-scale + flip list of `VOC12ClsDatasetMSF.__getitem__` (src/data.py:336-365) as `infer_mcl.py:123-125` feeds
-    it to the model (`img.cuda().float()`), built on the device: the decoded image crosses PCIe once as uint8; per scale
-    `mx_resample` (= `img.resize(target, PIL.Image.CUBIC)`, bit-exact) and `mx_input_stage` (color_norm, HWC -> CHW, the
-    float64 -> float32 rounding of `.float()`); the flipped copy is `np.flip(x, -1)`.  On the host the four bicubic resizes
+    it to the model (`img.cuda().float()`), built on the device: the decoded image crosses PCIe once as uint8, in one pinned
+    copy with the jobs and tables of every scale; one `mx_resample` over all scales (= `img.resize(target, PIL.Image.CUBIC)`,
+    bit-exact) and per scale `mx_input_stage` (color_norm, HWC -> CHW, the float64 -> float32 rounding of `.float()`); the
+    flipped copy is `np.flip(x, -1)`.  On the host the four bicubic resizes
     of a 500 x 375 image cost ~40 ms of a core per image; here ~0.5 ms of coefficient tables."""
 
     def __init__(self, device, max_side: int = 2048):
         self.dev, self.side = device, max_side
-        cap = max_side * max_side * 3
-        self._src = torch.empty(cap, dtype=torch.uint8, device=device)
-        self._tmp = torch.empty(cap, dtype=torch.uint8, device=device)
-        self._dst = torch.empty(cap, dtype=torch.uint8, device=device)
+        self.buf = StageBuffer(device)
 
     def __call__(self, pil_img, scales=(0.5, 1.0, 1.5, 2.0), unit: int = 1) -> List[torch.Tensor]:
-        a = np.array(pil_img.convert("RGB"))                    # (a writable copy: torch.from_numpy wants one)
+        a = np.asarray(pil_img.convert("RGB"))
         h, w = a.shape[:2]
         rounded = (int(round(w / unit) * unit), int(round(h / unit) * unit))                  # data.py:347
         if max(h, w) > self.side:
             raise ValueError(f"image {w}x{h} exceeds MSFStager(max_side={self.side})")
-        self._src[:a.size].copy_(torch.from_numpy(a).reshape(-1), non_blocking=False)
-        out: List[torch.Tensor] = []
-        for s in scales:
-            tw, th = round(rounded[0] * s), round(rounded[1] * s)                               # data.py:351-352
+        sizes = [(round(rounded[0] * s), round(rounded[1] * s)) for s in scales]              # data.py:351-352
+        for s, (tw, th) in zip(scales, sizes):
             if max(tw, th) > self.side:
                 raise ValueError(f"scale {s}: {tw}x{th} exceeds MSFStager(max_side={self.side})")
-            tab = torch.from_numpy(resample_tables(w, h, tw, th, "bicubic")).to(self.dev)
-            rs = torch.tensor([0, h, w, 0, 0, tw, th, 0], dtype=torch.int32, device=self.dev)
-            call("mx_resample", ptr(self._src), ptr(rs), ptr(tab), ptr(self._tmp), ptr(self._dst), 1, max(h * tw, th * tw), stream())
-            job = torch.tensor([0, th, tw, 0, 0, 0, 0, 0], dtype=torch.int32, device=self.dev)
+        tabs = [resample_tables(w, h, tw, th, "bicubic") for tw, th in sizes]
+        # ---- layout: [source image | resample jobs | tables | stage jobs]; on the device only: [resized | temporaries]
+        sb, k = self.buf, len(sizes)
+        sb.plan()
+        o_src, o_rs = sb.reserve(a.size), sb.reserve(k * 32, 64)
+        tab_at = [sb.reserve(t.nbytes) for t in tabs]
+        o_jobs = sb.reserve(k * 48, 64)
+        rs_at = [sb.scratch(th * tw * 3) for tw, th in sizes]
+        tmp_at = [sb.scratch(h * tw * 3) for tw, th in sizes]
+        buf = sb.begin()
+        buf[o_src:o_src + a.size] = a.reshape(-1)
+        rsj = buf[o_rs:o_rs + k * 32].view(np.int32).reshape(k, 8)
+        jobs = buf[o_jobs:o_jobs + k * 48].view(np.int32).reshape(k, 12)
+        for i, (tw, th) in enumerate(sizes):
+            buf[tab_at[i]:tab_at[i] + tabs[i].nbytes] = tabs[i].view(np.uint8)
+            rsj[i] = resample_job(o_src, h, w, tmp_at[i], rs_at[i], tw, th, tab_at[i])
+            jobs[i] = input_stage_job(rs_at[i], tw, 0, 0, th, tw)
+        base, st = sb.upload(), stream()
+        call("mx_resample", base, base + o_rs, base, base, base, k, max(max(h * tw, th * tw) for tw, th in sizes), st)
+        out: List[torch.Tensor] = []
+        for i, (tw, th) in enumerate(sizes):
             x = torch.empty(1, 3, th, tw, dtype=torch.float32, device=self.dev)
-            call("mx_input_stage", ptr(self._dst), ptr(job), ptr(x), 1, th, tw, stream())
+            call("mx_input_stage", base, base + o_jobs + 48 * i, x.data_ptr(), 1, th, tw, st)
             out.append(x)
             out.append(torch.flip(x, dims=[-1]))                                               # data.py:363
         return out

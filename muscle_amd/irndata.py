@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from ._lib import call, stream
+from ._stage import StageBuffer, resample_job
 from .data import _keep, resample_tables
 from .train_irn import random_crop_box
 
@@ -100,111 +101,69 @@ def plan_irn_eval_item(img_u8: np.ndarray, crop_size: int) -> IrnItemPlan:
     return p
 
 
-def _al(n: int, a: int = 16) -> int:
-    return (n + a - 1) // a * a
-
-
 class IrnStager:
-    """Packs the jobs, tables and uint8 sources of a batch of `IrnItemPlan`s into one pinned buffer, copies it once and runs
-    the device half: mx_resample (the bicubic rescale, only for the items whose size changes) -> mx_irn_input_stage.  Two
-    pinned buffers alternate so that packing batch t+1 does not wait for the copy of batch t; buffers grow to the largest
-    batch seen.  Returns {"img" [n,3,S,S] fp32, "label" [n,S/4,S/4] uint8} on the device - the batch `irn_step` takes - or
+    """Packs the jobs, tables and uint8 sources of a batch of `IrnItemPlan`s into one pinned buffer (`_stage.StageBuffer`: two
+    alternate, they grow to the largest batch seen), copies it once and runs the device half: mx_resample (the bicubic
+    rescale, only for the items whose size changes) -> mx_irn_input_stage.
+    Returns {"img" [n,3,S,S] fp32, "label" [n,S/4,S/4] uint8} on the device - the batch `irn_step` takes - or
     {"img"} when the plans carry no label (the eval view)."""
 
     def __init__(self, device, batch: int, crop_size: int = 512):
         if crop_size % 16:
             raise ValueError("crop_size must be a multiple of 16")
         self.dev, self.n, self.crop = device, batch, crop_size
-        self._pin = [None, None]
-        self._evt = [None, None]
-        self._dev_buf = None
-        self._k = 0
-        self.last_bytes = 0                                 # bytes of the last batch's one host-to-device copy
-        self.last_launch = None                             # (o_rs, o_tab, resample jobs, rs_px) of the last batch, for tools/bench_irn_input.py
+        self.buf = StageBuffer(device)
+        self.last_launch = None                             # (o_jobs, o_rs, resample jobs, rs_px) of the last batch, for tools/bench_irn_input.py
 
-    def _pinned(self, k: int, nbytes: int) -> np.ndarray:
-        if self._pin[k] is None or self._pin[k].numel() < nbytes:
-            t = torch.empty(_al(nbytes * 5 // 4, 4096), dtype=torch.uint8)
-            self._pin[k] = t.pin_memory() if torch.cuda.is_available() else t
-        return self._pin[k].numpy()
+    @property
+    def last_bytes(self) -> int:
+        return self.buf.last_bytes
 
     def __call__(self, plans: Sequence[IrnItemPlan], out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
         """out: tensors to write into instead of new ones ({"img"} and, for training items, {"label"}: contiguous, on the
         stager's device, of the shapes and types returned)."""
-        n, S = len(plans), self.crop
+        n, S, sb = len(plans), self.crop, self.buf
         assert 0 < n <= self.n
         with_label = plans[0].label_u8 is not None
         if any((p.label_u8 is not None) != with_label for p in plans):
             raise ValueError("a batch is either all training items or all eval views")
-        # ---- layout of the one buffer: [stage jobs | resample jobs | tables | images | labels]; behind it, on the device
-        # only: [rescaled images | horizontal-pass temporaries]
-        o_rs = 64 * n
-        o_tab = off = 96 * n
-        tab_at, ntab_at = [], []
-        for p in plans:
-            tab_at.append(off)
-            off += 0 if p.tables is None else 4 * p.tables.size
-        for p in plans:
-            ntab_at.append(off)
-            off += 4 * (p.size[0] + p.size[1]) if with_label else 0
-        off = _al(off)
-        img_at, lab_at = [], []
-        for p in plans:
-            img_at.append(off)
-            off = _al(off + p.img_u8.size)
-        for p in plans:
-            lab_at.append(off)
-            off = _al(off + p.label_u8.size) if with_label else off
-        total = off
-        rs_at, tmp_at = [], []
-        for p in plans:
-            rs_at.append(off)
-            off = _al(off + (0 if p.tables is None else p.size[0] * p.size[1] * 3))
-        for p in plans:
-            tmp_at.append(off)
-            off = _al(off + (0 if p.tables is None else p.img_u8.shape[0] * p.size[1] * 3))
-        if off >= 2 ** 31:
-            raise ValueError("batch sources exceed 2 GiB")
-        k = self._k
-        self._k ^= 1
-        if self._evt[k] is not None:
-            self._evt[k].synchronize()                      # the copy out of this pinned buffer two batches ago is done
-        buf = self._pinned(k, total)
-        jobs = buf[:o_rs].view(np.int32).reshape(n, 16)
-        rsj = buf[o_rs:o_tab].view(np.int32).reshape(n, 8)
-        jobs[:] = 0
-        rsj[:] = 0
+        rescaled = [p.tables is not None for p in plans]
+        # ---- layout: [stage jobs | resample jobs | tables | images | labels]; behind it, on the device only:
+        # [rescaled images | horizontal-pass temporaries]
+        sb.plan()
+        o_jobs, o_rs = sb.reserve(n * 64, 64), sb.reserve(n * 32, 64)
+        tab_at = [sb.reserve(p.tables.nbytes) if r else 0 for p, r in zip(plans, rescaled)]
+        ntab_at = [sb.reserve(4 * (p.size[0] + p.size[1])) if with_label else 0 for p in plans]
+        img_at = [sb.reserve(p.img_u8.size) for p in plans]
+        lab_at = [sb.reserve(p.label_u8.size) if with_label else -1 for p in plans]
+        rs_at = [sb.scratch(p.size[0] * p.size[1] * 3) if r else 0 for p, r in zip(plans, rescaled)]
+        tmp_at = [sb.scratch(p.img_u8.shape[0] * p.size[1] * 3) if r else 0 for p, r in zip(plans, rescaled)]
+        buf = sb.begin()
+        jobs = buf[o_jobs:o_jobs + n * 64].view(np.int32).reshape(n, 16)
+        rsj = buf[o_rs:o_rs + n * 32].view(np.int32).reshape(n, 8)
         m, rs_px = 0, 1                                     # resample jobs are packed: only the items that are rescaled
         for i, p in enumerate(plans):
             h, w = p.img_u8.shape[:2]
             sh, sw = p.size
             buf[img_at[i]:img_at[i] + p.img_u8.size] = p.img_u8.reshape(-1)
             src = img_at[i]
-            if p.tables is not None:
-                buf[tab_at[i]:tab_at[i] + 4 * p.tables.size] = p.tables.view(np.uint8)
-                rsj[m] = (img_at[i], h, w, tmp_at[i], rs_at[i], sw, sh, (tab_at[i] - o_tab) // 4)
+            if rescaled[i]:
+                buf[tab_at[i]:tab_at[i] + p.tables.nbytes] = p.tables.view(np.uint8)
+                rsj[m] = resample_job(img_at[i], h, w, tmp_at[i], rs_at[i], sw, sh, tab_at[i])
                 m, rs_px, src = m + 1, max(rs_px, h * sw, sh * sw), rs_at[i]
-            lab_off, yo, xo = -1, 0, 0
+            yo = xo = 0
             if with_label:
                 buf[lab_at[i]:lab_at[i] + p.label_u8.size] = p.label_u8.reshape(-1)
                 o = ntab_at[i]
                 buf[o:o + 4 * sh] = p.ytab.view(np.uint8)
                 buf[o + 4 * sh:o + 4 * (sh + sw)] = p.xtab.view(np.uint8)
-                lab_off, yo, xo = lab_at[i], (o - o_tab) // 4, (o - o_tab) // 4 + sh
+                yo, xo = o // 4, o // 4 + sh
             jobs[i] = (src, sh, sw, p.window[0], p.window[1], p.place[0], p.place[1], p.window[2], p.window[3], int(p.flip),
-                       lab_off, h, w, yo, xo, 0)
-        if self._dev_buf is None or self._dev_buf.numel() < off:
-            self._dev_buf = torch.empty(_al(off * 5 // 4, 4096), dtype=torch.uint8, device=self.dev)
-        self._dev_buf[:total].copy_(self._pin[k][:total], non_blocking=True)
-        self.last_bytes = total
-        evt = torch.cuda.Event()
-        evt.record()
-        self._evt[k] = evt
-        self.last_launch = (o_rs, o_tab, m, int(rs_px))
-        base = self._dev_buf.data_ptr()
-        st = stream()
+                       lab_at[i], h, w, yo, xo, 0)
+        base, st = sb.upload(), stream()
+        self.last_launch = (o_jobs, o_rs, m, int(rs_px))
         if m:
-            call("mx_resample", base, base + o_rs, base + o_tab, base, base, m, int(rs_px), st)
+            call("mx_resample", base, base + o_rs, base, base, base, m, int(rs_px), st)
         want = {"img": ((n, 3, S, S), torch.float32)}
         if with_label:
             want["label"] = ((n, S // 4, S // 4), torch.uint8)
@@ -215,7 +174,7 @@ class IrnStager:
             if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != out["img"].device:
                 raise ValueError(f"out[{k!r}] must be a contiguous {dt} tensor of shape {shape}")
         out = {k: out[k] for k in want}
-        call("mx_irn_input_stage", base, base, base + o_tab, out["img"].data_ptr(),
+        call("mx_irn_input_stage", base, base + o_jobs, base, out["img"].data_ptr(),
              out["label"].data_ptr() if with_label else None, n, S, st)
         return out
 

@@ -15,7 +15,7 @@ The skimage resize alone filters and warps 21 channels of the WHOLE rescaled lab
 Here `plan_seg_item` makes the same draws from the same generators in the same order and computes geometry and weight tables
 only; `SegStager` ships the decoded uint8 image and the source rows of the label the crop window reads (float16 as
 `muscle_amd.infer_irn --soft_output 1` writes them) in ONE pinned copy per batch, and the device does the pixel work:
-`mx_color_jitter` -> `mx_resample` (Pillow's bilinear, bit-exact) -> `mx_seg_input_stage` for the image, `mx_mask_stage` for
+`mx_color_jitter` -> `mx_resample` (Pillow's bilinear, bit-exact) -> `mx_input_stage` for the image, `mx_mask_stage` for
 the label.
 
 skimage.transform.resize (0.16.2, defaults order=1, mode='reflect', anti_aliasing=True, clip=True) is restated from its
@@ -35,6 +35,7 @@ import numpy as np
 import torch
 
 from ._lib import call, stream
+from ._stage import StageBuffer, input_stage_job, jitter_job, resample_job
 from .data import _keep, color_jitter_params, random_crop_box, resample_tables
 
 JITTER = (0.1, 0.1, 0.1, 0.05)          # src/data.py:81
@@ -130,131 +131,73 @@ def plan_seg_item(pil_img, soft_mask: np.ndarray, min_scale: float = 0.5, max_sc
     return p
 
 
-def _al(n: int, a: int = 16) -> int:
-    return (n + a - 1) // a * a
-
-
 class SegStager:
-    """Packs the sources, jobs and tables of a batch of `SegItemPlan`s into one pinned buffer, copies it once and runs the
-    device half: mx_color_jitter (ColorJitter on the original image) -> mx_resample (the bilinear rescale) ->
-    mx_seg_input_stage (color_norm, crop container, flip, CHW, fp32), and mx_mask_stage for the label.  Two pinned buffers
-    alternate so that packing batch t+1 does not wait for the copy of batch t; buffers grow to the largest batch seen.
+    """Packs the sources, jobs and tables of a batch of `SegItemPlan`s into one pinned buffer (`_stage.StageBuffer`: two
+    alternate, they grow to the largest batch seen), copies it once and runs the device half: mx_color_jitter (ColorJitter on
+    the original image) -> mx_resample (the bilinear rescale) -> mx_input_stage (color_norm, crop container, flip, CHW,
+    fp32), and mx_mask_stage for the label.
     Returns {"img" [n,3,S,S], "mask" [n,C,S,S]} (+ "label" [n,20]) on the device: the batch `muscle_step` takes."""
 
     def __init__(self, device, batch: int, crop_size: int = 448):
         self.dev, self.n, self.crop = device, batch, crop_size
-        self._pin = [None, None]
-        self._evt = [None, None]
-        self._dev_buf = None
-        self._dev_tmp = self._dev_rs = None
-        self._dev_sums = None                               # ColorJitter's per-image luminance sums (device scratch)
-        self._k = 0
-        self.last_bytes = 0                                 # bytes of the last batch's one host-to-device copy
+        self.buf = StageBuffer(device)
 
-    def _pinned(self, k: int, nbytes: int) -> np.ndarray:
-        if self._pin[k] is None or self._pin[k].numel() < nbytes:
-            t = torch.empty(_al(nbytes * 5 // 4, 4096), dtype=torch.uint8)
-            self._pin[k] = t.pin_memory() if torch.cuda.is_available() else t
-        return self._pin[k].numpy()
-
-    @staticmethod
-    def _grow(t, nbytes: int, device):
-        if t is None or t.numel() < nbytes:
-            return torch.empty(_al(nbytes * 5 // 4, 4096), dtype=torch.uint8, device=device)
-        return t
+    @property
+    def last_bytes(self) -> int:
+        return self.buf.last_bytes
 
     def __call__(self, plans: Sequence[SegItemPlan], labels: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
-        from .data import InputStager
-        n, S = len(plans), self.crop
+        n, S, sb = len(plans), self.crop, self.buf
         assert 0 < n <= self.n
         C = plans[0].mask_src.shape[2]
         if any(p.mask_src.shape[2] != C for p in plans):
             raise ValueError("every soft mask of a batch must have the same number of channels")
-        # ---- layout of the one buffer: [image jobs | jitter jobs | resample jobs | mask jobs | tables | images | masks]
-        o_jobs, o_jit, o_rs, o_mj = 0, 32 * n, 64 * n, 96 * n
-        o_tab = off = 160 * n
-        tab_at, mtab_at = [], []
-        for p in plans:
-            tab_at.append(off)
-            off += 4 * p.tables.size
-        for p in plans:
-            mtab_at.append(off)
-            off += 4 * sum(s.size + w.size for s, w in (p.mask_y, p.mask_x))
-        off = _al(off)
-        img_at, msk_at = [], []
-        for p in plans:
-            img_at.append(off)
-            off = _al(off + p.img_u8.size)
-        for p in plans:
-            msk_at.append(off)
-            off = _al(off + p.mask_src.nbytes)
-        total = off
-        if total >= 2 ** 31:
-            raise ValueError("batch sources exceed 2 GiB")
-        k = self._k
-        self._k ^= 1
-        if self._evt[k] is not None:
-            self._evt[k].synchronize()                      # the copy out of this pinned buffer two batches ago is done
-        buf = self._pinned(k, total)
-        words = buf[:o_tab].view(np.int32).reshape(-1, 8)
-        words[:] = 0
-        jobs, jit, rsj = words[:n], words[n:2 * n], words[2 * n:3 * n]
-        mj = words[3 * n:5 * n].reshape(n, 16)
-        jit_f = jit.view(np.float32)
-        jit[:, 3] = 0xFFFF                                  # order nibbles: nothing to do
-        tmp_off = rs_off = 0
+        # ---- layout: [image jobs | jitter jobs | resample jobs | mask jobs | tables | images | masks]; behind it, on the
+        # device only: [rescaled images | horizontal-pass temporaries | the jitter's sums]
+        sb.plan()
+        o_jobs, o_jit, o_rs, o_mj = sb.reserve(n * 48, 64), sb.reserve(n * 32, 64), sb.reserve(n * 32, 64), sb.reserve(n * 64, 64)
+        tab_at = [sb.reserve(p.tables.nbytes) for p in plans]
+        mtab_at = [[sb.reserve(s.nbytes + w.nbytes) for s, w in (p.mask_y, p.mask_x)] for p in plans]
+        img_at = [sb.reserve(p.img_u8.size) for p in plans]
+        msk_at = [sb.reserve(p.mask_src.nbytes) for p in plans]
+        rs_at = [sb.scratch(p.resize_to[0] * p.resize_to[1] * 3) for p in plans]
+        tmp_at = [sb.scratch(p.img_u8.shape[0] * p.resize_to[0] * 3) for p in plans]
+        o_sums = sb.scratch(n * 8)
+        buf = sb.begin()
+        jobs = buf[o_jobs:o_jobs + n * 48].view(np.int32).reshape(n, 12)
+        jit = buf[o_jit:o_jit + n * 32].view(np.int32).reshape(n, 8)
+        rsj = buf[o_rs:o_rs + n * 32].view(np.int32).reshape(n, 8)
+        mj = buf[o_mj:o_mj + n * 64].view(np.int32).reshape(n, 16)
         any_jit, jit_px, rs_px, span_cap = False, 1, 1, 1
         for i, p in enumerate(plans):
             h, w = p.img_u8.shape[:2]
             tw, th = p.resize_to
             it, il, ch, cw = p.img_crop
             buf[img_at[i]:img_at[i] + p.img_u8.size] = p.img_u8.reshape(-1)
-            buf[tab_at[i]:tab_at[i] + 4 * p.tables.size] = p.tables.view(np.uint8)
-            rsj[i] = (img_at[i], h, w, tmp_off, rs_off, tw, th, (tab_at[i] - o_tab) // 4)
-            jobs[i] = (rs_off + (it * tw + il) * 3, ch, cw, p.place[0], p.place[1], tw, int(p.flip), 0)
-            tmp_off += h * tw * 3
-            rs_off += th * tw * 3
+            buf[tab_at[i]:tab_at[i] + p.tables.nbytes] = p.tables.view(np.uint8)
+            rsj[i] = resample_job(img_at[i], h, w, tmp_at[i], rs_at[i], tw, th, tab_at[i])
             rs_px = max(rs_px, h * tw, th * tw)
+            jobs[i] = input_stage_job(rs_at[i] + (it * tw + il) * 3, tw, p.place[0], p.place[1], ch, cw,
+                                      flip_width=S if p.flip else None)
+            jit[i] = jitter_job(img_at[i], h, w, p.jitter)
             if p.jitter is not None:
-                code, facs, hue = InputStager._jitter_words(p.jitter)
-                jit[i, :4] = (img_at[i], h, w, code)
-                jit_f[i, 4:7] = facs
-                jit[i, 7] = hue
                 any_jit, jit_px = True, max(jit_px, h * w)
             m = p.mask_src
             buf[msk_at[i]:msk_at[i] + m.nbytes] = m.reshape(-1).view(np.uint8)
-            (sy, wy), (sx, wx) = p.mask_y, p.mask_x
-            o = mtab_at[i]
-            ty_off = (o - o_tab) // 4
-            for a in (sy, wy):
-                buf[o:o + a.nbytes] = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
-                o += a.nbytes
-            tx_off = (o - o_tab) // 4
-            for a in (sx, wx):
-                buf[o:o + a.nbytes] = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
-                o += a.nbytes
-            mj[i, :13] = (msk_at[i], m.shape[0], m.shape[1], int(m.dtype == np.float32), p.place[0], p.place[1], ch, cw,
-                          int(p.flip), wy.shape[1], wx.shape[1], ty_off, tx_off)
+            for o, (start, wgt) in zip(mtab_at[i], (p.mask_y, p.mask_x)):
+                buf[o:o + start.nbytes] = np.ascontiguousarray(start).view(np.uint8)
+                buf[o + start.nbytes:o + start.nbytes + wgt.nbytes] = np.ascontiguousarray(wgt).reshape(-1).view(np.uint8)
+            mj[i] = (msk_at[i], m.shape[0], m.shape[1], int(m.dtype == np.float32), p.place[0], p.place[1], ch, cw,
+                     int(p.flip), p.mask_y[1].shape[1], p.mask_x[1].shape[1], mtab_at[i][0] // 4, mtab_at[i][1] // 4, 0, 0, 0)
             span_cap = max(span_cap, p.span_cap)
-        self._dev_buf = self._grow(self._dev_buf, total, self.dev)
-        self._dev_tmp = self._grow(self._dev_tmp, tmp_off, self.dev)
-        self._dev_rs = self._grow(self._dev_rs, rs_off, self.dev)
-        if self._dev_sums is None:
-            self._dev_sums = torch.empty(self.n, dtype=torch.int64, device=self.dev)
-        self._dev_buf[:total].copy_(self._pin[k][:total], non_blocking=True)
-        self.last_bytes = total
-        evt = torch.cuda.Event()
-        evt.record()
-        self._evt[k] = evt
-        base = self._dev_buf.data_ptr()
-        st = stream()
+        base, st = sb.upload(), stream()
         if any_jit:
-            call("mx_color_jitter", base, base + o_jit, self._dev_sums.data_ptr(), n, int(jit_px), st)
-        call("mx_resample", base, base + o_rs, base + o_tab, self._dev_tmp.data_ptr(), self._dev_rs.data_ptr(), n, int(rs_px), st)
+            call("mx_color_jitter", base, base + o_jit, base + o_sums, n, int(jit_px), st)
+        call("mx_resample", base, base + o_rs, base, base, base, n, int(rs_px), st)
         img = torch.empty(n, 3, S, S, dtype=torch.float32, device=self.dev)
         mask = torch.empty(n, C, S, S, dtype=torch.float32, device=self.dev)
-        call("mx_seg_input_stage", self._dev_rs.data_ptr(), base + o_jobs, img.data_ptr(), n, S, S, st)
-        call("mx_mask_stage", base, base + o_mj, base + o_tab, mask.data_ptr(), n, C, S, int(span_cap), st)
+        call("mx_input_stage", base, base + o_jobs, img.data_ptr(), n, S, S, st)
+        call("mx_mask_stage", base, base + o_mj, base, mask.data_ptr(), n, C, S, int(span_cap), st)
         out = {"img": img, "mask": mask}
         if labels is not None:
             out["label"] = labels.to(self.dev, non_blocking=True)

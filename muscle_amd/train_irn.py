@@ -52,17 +52,9 @@ def normalize(img: np.ndarray) -> np.ndarray:
 
 
 def random_crop_box(h: int, w: int, crop: int, rng):
-    """src/imutils.py:183-206: the width is drawn before the height."""
-    ch, cw = min(crop, h), min(crop, w)
-    w_space, h_space = w - crop, h - crop
-    if w_space > 0:
-        cont_left, img_left = 0, rng.randrange(w_space + 1)
-    else:
-        cont_left, img_left = rng.randrange(-w_space + 1), 0
-    if h_space > 0:
-        cont_top, img_top = 0, rng.randrange(h_space + 1)
-    else:
-        cont_top, img_top = rng.randrange(-h_space + 1), 0
+    """src/imutils.py:183-206 (the width is drawn before the height): `data.random_crop_box` in the reference's 8-value form."""
+    from .data import random_crop_box as box
+    cont_top, cont_left, img_top, img_left, ch, cw = box(h, w, crop, rng)
     return cont_top, cont_top + ch, cont_left, cont_left + cw, img_top, img_top + ch, img_left, img_left + cw
 
 

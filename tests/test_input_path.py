@@ -94,6 +94,44 @@ def test_device_stage_bit_exact_with_reference():
     assert np.array_equal(b["view2"][0].cpu().numpy(), want[2].astype(np.float32))
 
 
+@pytest.mark.gpu
+def test_input_stage_kernel_equals_the_header_rule():
+    """mx_input_stage called directly against the numpy restatement of the header's rule (tests/input_stage_ref.py), bit for
+    bit: 37 x 53 (nothing divides anything) with a full window, a window with a border on every side, col_step -1, and
+    col_step -1 with an erase box and a row stride larger than the window; then 160 x 131 = 20 960 pixels, more than the
+    64 x 256 threads of the capped grid, so the grid-stride loop takes a second trip.  The output is poisoned with NaN first."""
+    from input_stage_ref import input_stage_ref
+    from muscle_amd._lib import call, stream
+    from muscle_amd._stage import input_stage_job
+    dev = torch.device("cuda:0")
+    g = np.random.default_rng(7)
+
+    def run(Hd, Wd, jobs, src):
+        d_src, d_jobs = torch.from_numpy(src).to(dev), torch.tensor(jobs, dtype=torch.int32, device=dev)
+        out = torch.full((len(jobs), 3, Hd, Wd), float("nan"), dtype=torch.float32, device=dev)
+        call("mx_input_stage", d_src.data_ptr(), d_jobs.data_ptr(), out.data_ptr(), len(jobs), Hd, Wd, stream())
+        got = out.cpu().numpy()
+        assert not np.isnan(got).any()
+        for i, job in enumerate(jobs):
+            assert np.array_equal(got[i], input_stage_ref(src, job, Hd, Wd)), (Hd, Wd, i)
+        return got
+
+    Hd, Wd = 37, 53
+    src = g.integers(0, 256, 16 + 2 * Hd * Wd * 3, dtype=np.uint8)
+    full, part = 16, 16 + Hd * Wd * 3                          # a packed [37,53,3] image, then a packed [30,40,3] crop
+    got = run(Hd, Wd, [input_stage_job(full, Wd, 0, 0, Hd, Wd),
+                       input_stage_job(part, 40, 3, 5, 30, 40),
+                       input_stage_job(part, 40, 3, 5, 30, 40, flip_width=Wd),
+                       input_stage_job(full + (5 * Wd + 7) * 3, Wd, 4, 6, 20, 25, flip_width=Wd, erase=(10, 20, 15, 40))], src)
+    assert np.array_equal(got[2], np.flip(got[1], -1)) and (got[1][:, :3] == 0).all() and (got[1][:, :, 45:] == 0).all()
+    assert (got[0] != 0).all() and (got[3][:, 10:25, 20:] == 0).all() and (got[3][:, 4:10, 22:47] != 0).all()
+    Hd, Wd = 160, 131
+    assert Hd * Wd > 64 * 256
+    src = g.integers(0, 256, Hd * Wd * 3, dtype=np.uint8)
+    run(Hd, Wd, [input_stage_job(0, Wd, 0, 0, Hd, Wd),
+                 input_stage_job((2 * Wd + 3) * 3, Wd, 1, 4, 150, 120, flip_width=Wd, erase=(100, 60, 80, 90))], src)
+
+
 # ---- ColorJitter / RandomErasing: restated from torchvision 0.9.0 (not installed here): PARITY UNPINNED ----------------
 # What can be checked without torchvision: the draws they take from torch's generator (count, order, ranges - as the
 # published source has them), the identities of the PIL adjustments, the erase box on the device, and that switching the

@@ -128,10 +128,10 @@ def main():
     torch.cuda.synchronize()
     t_wall = (time.perf_counter() - t0) / 10
     whole = events(lambda: stager(plans, out=out), args.reps)
-    o_rs, o_tab, m, rs_px = stager.last_launch
-    base, st = stager._dev_buf.data_ptr(), stream()
-    rs = events(lambda: call("mx_resample", base, base + o_rs, base + o_tab, base, base, m, rs_px, st), args.reps)
-    stg = events(lambda: call("mx_irn_input_stage", base, base, base + o_tab, out["img"].data_ptr(), out["label"].data_ptr(), N, S, st),
+    o_jobs, o_rs, m, rs_px = stager.last_launch
+    base, st = stager.buf.base, stream()
+    rs = events(lambda: call("mx_resample", base, base + o_rs, base, base, base, m, rs_px, st), args.reps)
+    stg = events(lambda: call("mx_irn_input_stage", base, base + o_jobs, base, out["img"].data_ptr(), out["label"].data_ptr(), N, S, st),
                  args.reps)
     stored = out["img"].numel() * 4 + out["label"].numel()
     fmt = lambda v: f"{v[0]:7.3f} ms ({v[1]:.3f}-{v[2]:.3f})"

@@ -1,6 +1,6 @@
 """Input path of decoder training (muscle_amd.segdata) next to the step it feeds: per batch of 16 at 448x448 from 375x500
 sources over the scale range 0.5 .. 1.75 - device time of the stage (one pinned copy + mx_color_jitter + mx_resample +
-mx_seg_input_stage + mx_mask_stage, HIP events), bytes copied, host time of plan_seg_item and of the stager's packing on one
+mx_input_stage + mx_mask_stage, HIP events), bytes copied, host time of plan_seg_item and of the stager's packing on one
 core, the muscle_step time of tools/bench_dec.py's configuration on the staged batch, and the per-item time of the scipy
 restatement of the reference's label resize (tests/segdata_ref.py) on one core.  Not the contract bench.
   python tools/bench_segdata.py [--reps 30] [--no-step]"""
