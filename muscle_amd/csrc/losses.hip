@@ -697,7 +697,18 @@ int mx_adam(float* p, const float* g, float* m, float* v, long n, float lr, floa
 // Exact zeros (masked channels: ~88 % of all elements) are never histogrammed: they cannot change the sum, and
 // 64 lanes hitting LDS bin 0 serialised the pass.
 // ---------------------------------------------------------------------------
+// BIT INVARIANT of the low-res family: the forward parks / histograms fabsf(a - b) * m of a pixel and class, and the backward
+// kernels recompute it and compare its BITS with the threshold the select found.  lr_coord and lr_pixel are inlined into
+// four kernels (runtime K and the 21-class template); under hipcc's default contraction (fast-honor-pragmas; the build
+// passes no -ffp-contract flag) the compiler fused multiplies into different neighbours in each of them (e.g. a[k] * ia
+// into the caller's a[k] - b[k]), the band kernel's value differed from the histogrammed one in the last bit, and the
+// threshold element silently got weight 0 instead of krem / cnt_eq.  So both functions are compiled without contraction and
+// name their fused steps themselves (fmaf): one IEEE operation sequence, whatever the caller.  The pragma is honoured only
+// by that default: a literal -ffp-contract=fast fuses globally, ignores it and undoes this.
+// The full-resolution pair (er_diff_kernel / er_bwd_kernel through softmaxnorm_px) has the same hazard and no pragma: the
+// two agree today by the compiler's choice, and tests/test_gpu_er.py (tie and constant-region cases) is what watches it.
 __device__ __forceinline__ void lr_coord(int d, int in, int out, int& i0, int& i1, float& w1) {
+#pragma clang fp contract(off)
   float scale = (out > 1) ? (float)(in - 1) / (float)(out - 1) : 0.f;
   float s = scale * d;
   i0 = (int)s;
@@ -706,9 +717,16 @@ __device__ __forceinline__ void lr_coord(int d, int in, int out, int& i0, int& i
   w1 = s - i0;
 }
 
+// v0 * (u00 * p00 + u01 * p01) + v1 * (u00 * p10 + u01 * p11) with its three fused steps spelled out
+__device__ __forceinline__ float lr_lerp(float v0, float v1, float u00, float u01, float p00, float p01, float p10, float p11) {
+#pragma clang fp contract(off)
+  return fmaf(v1, fmaf(u01, p11, u00 * p10), v0 * fmaf(u01, p01, u00 * p00));
+}
+
 // fills a[K], b[K] with the softmaxnorm'ed upsampled cam / sgc at (n, Y, X); returns argmax of b's foreground
 __device__ __forceinline__ int lr_pixel(const float* cam, const float* sgc, int n, int Y, int X, int h, int w, int L, int K, int H,
                                         int W, float* a, float* b, float& wy, float& wx, int& y0, int& y1, int& x0, int& x1) {
+#pragma clang fp contract(off)
   lr_coord(Y, h, H, y0, y1, wy);
   lr_coord(X, w, W, x0, x1, wx);
   const long base = (long)n * h * w * L;
@@ -717,20 +735,15 @@ __device__ __forceinline__ int lr_pixel(const float* cam, const float* sgc, int 
   const float* s00 = sgc + base + ((long)y0 * w + x0) * L; const float* s01 = sgc + base + ((long)y0 * w + x1) * L;
   const float* s10 = sgc + base + ((long)y1 * w + x0) * L; const float* s11 = sgc + base + ((long)y1 * w + x1) * L;
   float ma = -INFINITY, mb = -INFINITY;
-  // cells are L floats apart with L % 4 == 0 (checked by the callers): 16-byte loads, four classes per step; the
-  // interpolation of each class is the same expression as before (bit-identical)
+  // cells are L floats apart with L % 4 == 0 (checked by the callers): 16-byte loads, four classes per step
   const float u00 = (1.f - wx), u01 = wx, v0 = (1.f - wy), v1 = wy;
   for (int k4 = 0; k4 < K; k4 += 4) {
     const float4 p00 = ld4(c00 + k4), p01 = ld4(c01 + k4), p10 = ld4(c10 + k4), p11 = ld4(c11 + k4);
     const float4 q00 = ld4(s00 + k4), q01 = ld4(s01 + k4), q10 = ld4(s10 + k4), q11 = ld4(s11 + k4);
-    const float av[4] = {v0 * (u00 * p00.x + u01 * p01.x) + v1 * (u00 * p10.x + u01 * p11.x),
-                         v0 * (u00 * p00.y + u01 * p01.y) + v1 * (u00 * p10.y + u01 * p11.y),
-                         v0 * (u00 * p00.z + u01 * p01.z) + v1 * (u00 * p10.z + u01 * p11.z),
-                         v0 * (u00 * p00.w + u01 * p01.w) + v1 * (u00 * p10.w + u01 * p11.w)};
-    const float bv[4] = {v0 * (u00 * q00.x + u01 * q01.x) + v1 * (u00 * q10.x + u01 * q11.x),
-                         v0 * (u00 * q00.y + u01 * q01.y) + v1 * (u00 * q10.y + u01 * q11.y),
-                         v0 * (u00 * q00.z + u01 * q01.z) + v1 * (u00 * q10.z + u01 * q11.z),
-                         v0 * (u00 * q00.w + u01 * q01.w) + v1 * (u00 * q10.w + u01 * q11.w)};
+    const float av[4] = {lr_lerp(v0, v1, u00, u01, p00.x, p01.x, p10.x, p11.x), lr_lerp(v0, v1, u00, u01, p00.y, p01.y, p10.y, p11.y),
+                         lr_lerp(v0, v1, u00, u01, p00.z, p01.z, p10.z, p11.z), lr_lerp(v0, v1, u00, u01, p00.w, p01.w, p10.w, p11.w)};
+    const float bv[4] = {lr_lerp(v0, v1, u00, u01, q00.x, q01.x, q10.x, q11.x), lr_lerp(v0, v1, u00, u01, q00.y, q01.y, q10.y, q11.y),
+                         lr_lerp(v0, v1, u00, u01, q00.z, q01.z, q10.z, q11.z), lr_lerp(v0, v1, u00, u01, q00.w, q01.w, q10.w, q11.w)};
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int k = k4 + j;
