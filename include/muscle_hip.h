@@ -437,6 +437,16 @@ int mx_irn_transition(float* dense, int n4, int ld, float beta, float* colsum, v
  * values themselves as the script's --soft_output writes them.  max_scratch: one uint32. */
 int mx_irn_finish(const float* rw, int C, int h, int w, int H, int W, float bg_thres, unsigned* max_scratch, unsigned char* label,
                   void* soft_half, void* stream);
+/* The compact soft pseudo-label (muscle_amd/softlabel.py) back to rows of the dense array: what infer_irn.py:79-88 saves
+ * (np.concatenate([bg_thres plane, rw_up / max]).astype(float16), HWC) and src/data.py:102 np.load's, re-created from the
+ * stored walk maps with the arithmetic of mx_irn_finish (csrc/irn_soft.h is included by both kernels), bit for bit.
+ * Batched: jobs = n x 16 int32 {rw_off, keys_off, K, h, w, H, W, r0, rows, dst_off, channels, vmax, bg, 0, 0, 0}; *_off are
+ * byte offsets from base: rw fp32 [K,h,w] (4-byte aligned), keys uint8 [K] ascending (the map i is channel keys[i] + 1 of
+ * the label), dst 16-byte aligned; vmax / bg are float bits: the maximum mx_irn_finish divided by and the threshold.
+ * Every item's float16 [rows, W, channels] at dst_off is fully written: rows r0 .. r0 + rows - 1 of the [H,W,channels]
+ * label - channel 0 half(bg), channel keys[i] + 1 half(up4(rw_i, r0 + y, x) / vmax), every other channel +0.
+ * H <= 4h, W <= 4w, r0 + rows <= H, channels <= 256.  The job table is trusted device data.  No atomics. */
+int mx_soft_expand(void* base, const int* jobs, int n, void* stream);
 /* The same walk without the matrix (csrc/irn_walk.hip): x . T^steps as `steps` stencil applications, O(nd * n) memory.
  * mx_irn_walk_weights (indexing.py:77-93 + :116-118; same path table as mx_irn_affinity, n = h*w):
  *   W[nd][n] fp32, direction-major: W[d][p] = (1 - max of the edge along the straight path p -> p+d)^beta, 0 where p+d lies

@@ -4,6 +4,7 @@
 // a sparse COO tensor assembled on the CPU and .to_dense().cuda()) and turns it into the column-stochastic matrix.
 #include "common.h"
 #include <hip/hip_fp16.h>
+#include "irn_soft.h"
 
 // padded edge map of propagate_to_edge (:124): radius columns left/right and radius rows at the bottom, value 1.0
 __device__ __forceinline__ float irn_edge_padded(const float* edge, int h, int w, int radius, int y, int x) {
@@ -79,7 +80,10 @@ __global__ __launch_bounds__(256) void irn_col_scale_kernel(float* dense, int n4
 
 // infer_irn.py:78-94: rw_up = interpolate(rw, x4, bilinear, align_corners=False)[:, :H, :W]; rw_up /= max(rw_up);
 // label = argmax over [bg_thres, rw_up_1 .. rw_up_C] (first maximum wins).
-__device__ __forceinline__ float irn_up4(const float* m, int h, int w, int Y, int X) {
+// irn_up4 and the value / rounding step of the label live in irn_soft.h, shared with mx_soft_expand (softlabel.hip).
+// The maximum keeps the plain expression: hipcc contracts it one way in the unrolled loop of irn_up_max_kernel and another
+// way in its remainder loop, and the value every label is divided by must keep its bits.
+__device__ __forceinline__ float irn_up4_max(const float* m, int h, int w, int Y, int X) {
   float sy = ((float)Y + 0.5f) * 0.25f - 0.5f, sx = ((float)X + 0.5f) * 0.25f - 0.5f;
   if (sy < 0.f) sy = 0.f;
   if (sx < 0.f) sx = 0.f;
@@ -96,7 +100,7 @@ __global__ __launch_bounds__(256) void irn_up_max_kernel(const float* rw, int C,
   const long total = (long)C * H * W;
   for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const int X = (int)(i % W), Y = (int)((i / W) % H), c = (int)(i / ((long)W * H));
-    m = fmaxf(m, irn_up4(rw + (long)c * h * w, h, w, Y, X));
+    m = fmaxf(m, irn_up4_max(rw + (long)c * h * w, h, w, Y, X));
   }
   m = wave_max(m);
   if ((threadIdx.x & 63) == 0) atomicMax(mx_bits, __float_as_uint(m));      // values are >= 0: bit order == value order
@@ -110,10 +114,10 @@ __global__ __launch_bounds__(256) void irn_label_kernel(const float* rw, int C, 
     const int X = (int)(p % W), Y = (int)(p / W);
     float best = bg_thres;
     int bk = 0;
-    if (soft) soft[p * (C + 1)] = __float2half_rn(bg_thres);
+    if (soft) soft[p * (C + 1)] = irn_soft_half(bg_thres);
     for (int c = 0; c < C; ++c) {
-      const float v = irn_up4(rw + (long)c * h * w, h, w, Y, X) / mx;
-      if (soft) soft[p * (C + 1) + c + 1] = __float2half_rn(v);
+      const float v = irn_soft_value(rw + (long)c * h * w, h, w, Y, X, mx);
+      if (soft) soft[p * (C + 1) + c + 1] = irn_soft_half(v);
       if (v > best) { best = v; bk = c + 1; }
     }
     label[p] = (unsigned char)bk;

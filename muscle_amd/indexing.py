@@ -101,15 +101,27 @@ def propagate_to_edge(x: torch.Tensor, edge: torch.Tensor, radius: int = 5, beta
     return rw[:C, :n].reshape(C, 1, h, w)
 
 
-def finish_semseg(rw: torch.Tensor, H: int, W: int, bg_thres: float, soft_output: bool = False):
+def finish_semseg(rw: torch.Tensor, H: int, W: int, bg_thres: float, soft_output=False):
     """infer_irn.py:78-94: rw [C,1,h,w] -> uint8 label map [H,W] (argmax over [bg_thres, upsampled rw / max]); with
-    soft_output also the fp16 [H,W,C+1] array the script saves."""
+    soft_output also the fp16 [H,W,C+1] array the script saves.  soft_output="compact": (label, softlabel.CompactSoft) - the
+    maps of the channels that hold a non-zero word, the maximum mx_irn_finish divided by (its max_scratch word) and the
+    threshold, which `softlabel.expand` turns back into that array bit for bit.  An all-zero rw gives vmax = 0 (the dense
+    array would be NaN): such a CompactSoft cannot be saved or expanded."""
     C, _, h, w = rw.shape
     r = rw.reshape(C, h, w).contiguous().float()
+    compact = isinstance(soft_output, str)
+    if compact and soft_output != "compact":
+        raise ValueError(f"finish_semseg: soft_output must be False, True or 'compact' (got {soft_output!r})")
     label = torch.empty(H, W, dtype=torch.uint8, device=rw.device)
-    soft = torch.empty(H, W, C + 1, dtype=torch.float16, device=rw.device) if soft_output else None
+    soft = torch.empty(H, W, C + 1, dtype=torch.float16, device=rw.device) if soft_output and not compact else None
     scratch = torch.empty(1, dtype=torch.int32, device=rw.device)
     call("mx_irn_finish", ptr(r), C, h, w, H, W, float(bg_thres), ptr(scratch), ptr(label), ptr(soft), stream())
+    if compact:
+        from .softlabel import CompactSoft
+        present = (r.view(torch.int32) != 0).reshape(C, -1).any(dim=1)          # by the bits: a map of -0 is not "absent"
+        keys = torch.nonzero(present).reshape(-1)
+        vmax = scratch.view(torch.float32).cpu().numpy()[0]
+        return label, CompactSoft(keys.cpu().numpy(), r[keys].cpu().numpy(), (H, W), vmax, np.float32(bg_thres), C + 1)
     return (label, soft) if soft_output else label
 
 

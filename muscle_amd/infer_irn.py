@@ -1,6 +1,9 @@
 """`python -m muscle_amd.infer_irn`: the reference's infer_irn.py (IRN boundary map + random walk -> pseudo labels) on the
 HIP path.  Same arguments, same output files: `<sem_seg_out_dir>_png/<name>.png`, the label map as a palette PNG with the VOC
 colour map, and with --soft_output 1 instead `<sem_seg_out_dir>/<name>.npy`, float16 [H,W,21].
+--soft_output 2 (not in the reference) writes the compact form of that array, `<sem_seg_out_dir>/<name>.npz`
+(muscle_amd/softlabel.py: the walk maps of the present classes, 47 KB per class at 375x500 instead of 7.9 MB), which
+`train_muscle --mask_root` reads and `python -m muscle_amd.softlabel unpack` turns into the .npy bit for bit.
 
 Differences a caller can see:
   * --irn_network is accepted and ignored: the one network the reference ships (src.backbones.resnet50_irn) is built in;
@@ -29,7 +32,8 @@ def parse_args(argv: Optional[List[str]] = None):
     ap.add_argument("--sem_seg_out_dir", default="./irn_rw", type=str)
     ap.add_argument("--voc12_root", default="data/VOC2012", type=str)
     ap.add_argument("--infer_list", default="data/train.txt", type=str)
-    ap.add_argument("--soft_output", default=0, type=int, help="write float16 soft pseudo labels instead of the PNG")
+    ap.add_argument("--soft_output", default=0, type=int,
+                    help="1: write float16 soft pseudo labels <name>.npy instead of the PNG; 2: their compact form <name>.npz")
     ap.add_argument("--walk", default="dense", choices=("dense", "stencil"),
                     help="the random walk: dense = exp_times squarings of the n x n transition matrix (the reference's way), "
                          "stencil = 2^exp_times matrix-free steps on an fp64 state (O(n) memory)")
@@ -48,6 +52,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     from muscle_amd.infer import load_cam_dict
     from muscle_amd.infer_seg import read_names
     from muscle_amd.irn import EdgeDisplacement, infer_irn, save_palette_png
+    from muscle_amd.softlabel import save_compact
 
     dev = torch.device("cuda:0")
     model = EdgeDisplacement()
@@ -62,8 +67,13 @@ def main(argv: Optional[List[str]] = None) -> int:
         pair = torch.cat(stager(img, (1.0,)), dim=0)                                                 # image + flip, color_norm'ed
         cam = load_cam_dict(os.path.join(args.cam_dir, name + ".npy"))
         res = infer_irn(model, pair, cam, beta=args.beta, exp_times=args.exp_times, bg_thres=args.sem_seg_bg_thres,
-                        soft_output=bool(args.soft_output), method=args.walk)
-        if args.soft_output:
+                        soft_output="compact" if args.soft_output == 2 else bool(args.soft_output), method=args.walk)
+        if args.soft_output == 2:
+            if res[1].vmax > 0:
+                save_compact(os.path.join(args.sem_seg_out_dir, name + ".npz"), res[1])
+            else:                                                # all-zero walk result: the dense array would be 0 / 0
+                print(f"[muscle_amd] {name}: the walk result is all zero, no soft label written", file=sys.stderr)
+        elif args.soft_output:
             np.save(os.path.join(args.sem_seg_out_dir, name + ".npy"), res[1].cpu().numpy())
         else:
             save_palette_png(os.path.join(args.sem_seg_out_dir + "_png", name + ".png"), res)

@@ -454,11 +454,12 @@ def cam_stack(cam_dict, H: int, W: int, device) -> torch.Tensor:
 
 
 def infer_irn(model: EdgeDisplacement, img_pair: torch.Tensor, cam_dict, *, beta=8, exp_times=6, bg_thres=0.35,
-              soft_output: bool = False, method: str = "dense"):
+              soft_output=False, method: str = "dense"):
     """infer_irn.py:64-92 for one image: the network, the CAM down-scaling (:76), the random walk (:77) and the label step
     (:79-92).  img_pair: [2,3,H,W] on the device; cam_dict: {class index: float32 [H,W]}.  Returns the uint8 label map [H,W]
-    (and the fp16 [H,W,21] array with soft_output) on the device.  method: the walk of indexing.propagate_to_edge, "dense"
-    (matrix squarings) or "stencil" (matrix-free)."""
+    (and the fp16 [H,W,21] array with soft_output) on the device; soft_output="compact" gives the `softlabel.CompactSoft` (host
+    arrays) in the array's place.  method: the walk of indexing.propagate_to_edge, "dense" (matrix squarings) or "stencil"
+    (matrix-free)."""
     H, W = img_pair.shape[2:]
     edge, _dp = model(img_pair)
     with torch.no_grad():

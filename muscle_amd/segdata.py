@@ -16,7 +16,9 @@ Here `plan_seg_item` makes the same draws from the same generators in the same o
 only; `SegStager` ships the decoded uint8 image and the source rows of the label the crop window reads (float16 as
 `muscle_amd.infer_irn --soft_output 1` writes them) in ONE pinned copy per batch, and the device does the pixel work:
 `mx_color_jitter` -> `mx_resample` (Pillow's bilinear, bit-exact) -> `mx_input_stage` for the image, `mx_mask_stage` for
-the label.
+the label.  A label may also come in its compact form (`muscle_amd.softlabel.CompactSoft`, `<name>.npz`): then the
+low-resolution walk maps are shipped (47 KB per present class at 375x500 instead of up to 7.9 MB of rows) and
+`mx_soft_expand` re-creates the float16 rows the window reads, bit for bit, in device scratch just before `mx_mask_stage`.
 
 skimage.transform.resize (0.16.2, defaults order=1, mode='reflect', anti_aliasing=True, clip=True) is restated from its
 published source: `scipy.ndimage.gaussian_filter(mask, sigma, mode='mirror')` with sigma = max(0, (in/out - 1)/2) per spatial
@@ -37,6 +39,7 @@ import torch
 from ._lib import call, stream
 from ._stage import StageBuffer, input_stage_job, jitter_job, resample_job
 from .data import _keep, color_jitter_params, random_crop_box, resample_tables
+from .softlabel import CompactSoft, expand_job, load_compact, pack_compact
 
 JITTER = (0.1, 0.1, 0.1, 0.05)          # src/data.py:81
 
@@ -88,22 +91,29 @@ def mask_axis_table(n_in: int, n_out: int, lo: int = 0, cnt: Optional[int] = Non
 class SegItemPlan:
     """Sources + geometry of one decoder-training item, ready for `SegStager`."""
     __slots__ = ("img_u8", "jitter", "scale", "resize_to", "tables", "img_crop", "place", "flip",
-                 "mask_src", "mask_y", "mask_x", "span_cap")
+                 "mask_src", "mask_y", "mask_x", "span_cap", "compact", "mask_rows")
     # img_u8: the ORIGINAL decoded image [h,w,3]; jitter: ColorJitter parameters or None; resize_to: (W, H) of the rescale;
     # tables: Pillow's bilinear coefficient tables for it; img_crop = (top, left, ch, cw): RandomCropWithMask's window inside
     # the rescaled image / label; place = (top, left) of the window inside the [crop, crop] container; flip: fliplr of the
     # containers; mask_src: the source rows [r0:r1] of the label the window reads (float16 / float32, [rows, W, C]);
     # mask_y / mask_x = (start, weights float32) of mask_axis_table for the window, start_y relative to r0;
-    # span_cap: the longest run of source columns 64 neighbouring window columns read.
+    # span_cap: the longest run of source columns 64 neighbouring window columns read;
+    # mask_rows = (r0, r1); compact: the CompactSoft the rows are expanded from on the device (mask_src is None then), or None.
+
+    @property
+    def channels(self) -> int:
+        return self.compact.channels if self.compact is not None else self.mask_src.shape[2]
 
 
-def plan_seg_item(pil_img, soft_mask: np.ndarray, min_scale: float = 0.5, max_scale: float = 1.5, crop_size: int = 448,
+def plan_seg_item(pil_img, soft_mask, min_scale: float = 0.5, max_scale: float = 1.5, crop_size: int = 448,
                   augment: bool = True) -> SegItemPlan:
     """Host side of VOC12SegDataset.__getitem__ (src/data.py:104-112) for one decoded RGB image and its soft label [H,W,C]:
     the draws in the reference's order - ColorJitter parameters (torch), scale (random.uniform), crop box (random.randrange,
     width then height), flip (random.getrandbits) - and the tables of both resizes.  No pixel is touched.
-    augment=False leaves the ColorJitter (and its draws) out; scale, crop and flip stay."""
-    if soft_mask.ndim != 3:
+    augment=False leaves the ColorJitter (and its draws) out; scale, crop and flip stay.
+    soft_mask may be a `softlabel.CompactSoft`: the same draws and tables from its `size`; no rows are cut on the host."""
+    compact = soft_mask if isinstance(soft_mask, CompactSoft) else None
+    if compact is None and soft_mask.ndim != 3:
         raise ValueError(f"soft mask must be [H,W,C] (got {soft_mask.shape})")
     p = SegItemPlan()
     w, h = pil_img.size
@@ -118,14 +128,18 @@ def plan_seg_item(pil_img, soft_mask: np.ndarray, min_scale: float = 0.5, max_sc
     p.img_crop, p.place = (it, il, ch, cw), (ct, cl)
     p.img_u8 = np.ascontiguousarray(np.asarray(pil_img))
     p.tables = resample_tables(w, h, tw, th, "bilinear")
-    hm, wm = soft_mask.shape[:2]
+    hm, wm = compact.size if compact is not None else soft_mask.shape[:2]
     sy, wy = mask_axis_table(hm, th, it, ch)
     sx, wx = mask_axis_table(wm, tw, il, cw)
     r0, r1 = int(sy.min()), int(sy.max()) + wy.shape[1]
-    src = soft_mask[r0:r1]
-    if src.dtype not in (np.float16, np.float32):           # float64 files: rounded to fp32 (6e-8 relative)
-        src = src.astype(np.float32)
-    p.mask_src = np.ascontiguousarray(src)
+    p.compact, p.mask_rows = compact, (r0, r1)
+    if compact is not None:
+        p.mask_src = None
+    else:
+        src = soft_mask[r0:r1]
+        if src.dtype not in (np.float16, np.float32):       # float64 files: rounded to fp32 (6e-8 relative)
+            src = src.astype(np.float32)
+        p.mask_src = np.ascontiguousarray(src)
     p.mask_y, p.mask_x = (sy - r0, wy.astype(np.float32)), (sx, wx.astype(np.float32))
     p.span_cap = int((sx[np.minimum(np.arange(cw) + 63, cw - 1)] + wx.shape[1] - sx).max())
     return p
@@ -135,7 +149,9 @@ class SegStager:
     """Packs the sources, jobs and tables of a batch of `SegItemPlan`s into one pinned buffer (`_stage.StageBuffer`: two
     alternate, they grow to the largest batch seen), copies it once and runs the device half: mx_color_jitter (ColorJitter on
     the original image) -> mx_resample (the bilinear rescale) -> mx_input_stage (color_norm, crop container, flip, CHW,
-    fp32), and mx_mask_stage for the label.
+    fp32), and mx_mask_stage for the label; in front of it ONE mx_soft_expand for the items whose label is compact: their
+    walk maps travel in the copy, the float16 rows of their windows are written into device scratch and the item's mask job
+    points there.  Dense and compact items may share a batch.
     Returns {"img" [n,3,S,S], "mask" [n,C,S,S]} (+ "label" [n,20]) on the device: the batch `muscle_step` takes."""
 
     def __init__(self, device, batch: int, crop_size: int = 448):
@@ -146,29 +162,43 @@ class SegStager:
     def last_bytes(self) -> int:
         return self.buf.last_bytes
 
+    def layout(self, plans: Sequence[SegItemPlan]) -> dict:
+        """Plans the staging buffer of a batch (no packing, no GPU): byte offsets of every region.
+        [image jobs | jitter jobs | resample jobs | mask jobs | expand jobs | tables | images | labels]; behind it, on the
+        device only: [rescaled images | horizontal-pass temporaries | the jitter's sums | expanded label rows].
+        "msk": per item the shipped label bytes - the source rows of a dense label, rw then keys (K*h*w*4 + K bytes) of a
+        compact one; "exp": per compact item the scratch region of its (r1-r0) x W x channels float16 rows, else None."""
+        n, sb = len(plans), self.buf
+        nc = sum(p.compact is not None for p in plans)
+        sb.plan()
+        L = {"jobs": sb.reserve(n * 48, 64), "jit": sb.reserve(n * 32, 64), "rs": sb.reserve(n * 32, 64), "mj": sb.reserve(n * 64, 64)}
+        L["sj"] = sb.reserve(nc * 64, 64) if nc else None
+        L["tab"] = [sb.reserve(p.tables.nbytes) for p in plans]
+        L["mtab"] = [[sb.reserve(s.nbytes + w.nbytes) for s, w in (p.mask_y, p.mask_x)] for p in plans]
+        L["img"] = [sb.reserve(p.img_u8.size) for p in plans]
+        L["msk"] = [sb.reserve(p.compact.nbytes if p.compact is not None else p.mask_src.nbytes) for p in plans]
+        L["rsz"] = [sb.scratch(p.resize_to[0] * p.resize_to[1] * 3) for p in plans]
+        L["tmp"] = [sb.scratch(p.img_u8.shape[0] * p.resize_to[0] * 3) for p in plans]
+        L["sums"] = sb.scratch(n * 8)
+        L["exp"] = [None if p.compact is None else
+                    sb.scratch((p.mask_rows[1] - p.mask_rows[0]) * p.compact.size[1] * p.compact.channels * 2) for p in plans]
+        return L
+
     def __call__(self, plans: Sequence[SegItemPlan], labels: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         n, S, sb = len(plans), self.crop, self.buf
         assert 0 < n <= self.n
-        C = plans[0].mask_src.shape[2]
-        if any(p.mask_src.shape[2] != C for p in plans):
+        C = plans[0].channels
+        if any(p.channels != C for p in plans):
             raise ValueError("every soft mask of a batch must have the same number of channels")
-        # ---- layout: [image jobs | jitter jobs | resample jobs | mask jobs | tables | images | masks]; behind it, on the
-        # device only: [rescaled images | horizontal-pass temporaries | the jitter's sums]
-        sb.plan()
-        o_jobs, o_jit, o_rs, o_mj = sb.reserve(n * 48, 64), sb.reserve(n * 32, 64), sb.reserve(n * 32, 64), sb.reserve(n * 64, 64)
-        tab_at = [sb.reserve(p.tables.nbytes) for p in plans]
-        mtab_at = [[sb.reserve(s.nbytes + w.nbytes) for s, w in (p.mask_y, p.mask_x)] for p in plans]
-        img_at = [sb.reserve(p.img_u8.size) for p in plans]
-        msk_at = [sb.reserve(p.mask_src.nbytes) for p in plans]
-        rs_at = [sb.scratch(p.resize_to[0] * p.resize_to[1] * 3) for p in plans]
-        tmp_at = [sb.scratch(p.img_u8.shape[0] * p.resize_to[0] * 3) for p in plans]
-        o_sums = sb.scratch(n * 8)
+        L = self.layout(plans)
+        o_jobs, o_jit, o_rs, o_mj, o_sj, o_sums = L["jobs"], L["jit"], L["rs"], L["mj"], L["sj"], L["sums"]
+        tab_at, mtab_at, img_at, msk_at, rs_at, tmp_at, exp_at = L["tab"], L["mtab"], L["img"], L["msk"], L["rsz"], L["tmp"], L["exp"]
         buf = sb.begin()
         jobs = buf[o_jobs:o_jobs + n * 48].view(np.int32).reshape(n, 12)
         jit = buf[o_jit:o_jit + n * 32].view(np.int32).reshape(n, 8)
         rsj = buf[o_rs:o_rs + n * 32].view(np.int32).reshape(n, 8)
         mj = buf[o_mj:o_mj + n * 64].view(np.int32).reshape(n, 16)
-        any_jit, jit_px, rs_px, span_cap = False, 1, 1, 1
+        any_jit, jit_px, rs_px, span_cap, nc = False, 1, 1, 1, 0
         for i, p in enumerate(plans):
             h, w = p.img_u8.shape[:2]
             tw, th = p.resize_to
@@ -182,12 +212,19 @@ class SegStager:
             jit[i] = jitter_job(img_at[i], h, w, p.jitter)
             if p.jitter is not None:
                 any_jit, jit_px = True, max(jit_px, h * w)
-            m = p.mask_src
-            buf[msk_at[i]:msk_at[i] + m.nbytes] = m.reshape(-1).view(np.uint8)
+            if p.compact is not None:                       # the rows come out of mx_soft_expand: float16, in scratch
+                pack_compact(buf, msk_at[i], p.compact)
+                buf[o_sj + nc * 64:o_sj + nc * 64 + 64].view(np.int32)[:] = expand_job(p.compact, msk_at[i], exp_at[i], p.mask_rows)
+                nc += 1
+                m_off, m_rows, m_cols, m_f32 = exp_at[i], p.mask_rows[1] - p.mask_rows[0], p.compact.size[1], 0
+            else:
+                m = p.mask_src
+                buf[msk_at[i]:msk_at[i] + m.nbytes] = m.reshape(-1).view(np.uint8)
+                m_off, m_rows, m_cols, m_f32 = msk_at[i], m.shape[0], m.shape[1], int(m.dtype == np.float32)
             for o, (start, wgt) in zip(mtab_at[i], (p.mask_y, p.mask_x)):
                 buf[o:o + start.nbytes] = np.ascontiguousarray(start).view(np.uint8)
                 buf[o + start.nbytes:o + start.nbytes + wgt.nbytes] = np.ascontiguousarray(wgt).reshape(-1).view(np.uint8)
-            mj[i] = (msk_at[i], m.shape[0], m.shape[1], int(m.dtype == np.float32), p.place[0], p.place[1], ch, cw,
+            mj[i] = (m_off, m_rows, m_cols, m_f32, p.place[0], p.place[1], ch, cw,
                      int(p.flip), p.mask_y[1].shape[1], p.mask_x[1].shape[1], mtab_at[i][0] // 4, mtab_at[i][1] // 4, 0, 0, 0)
             span_cap = max(span_cap, p.span_cap)
         base, st = sb.upload(), stream()
@@ -197,6 +234,8 @@ class SegStager:
         img = torch.empty(n, 3, S, S, dtype=torch.float32, device=self.dev)
         mask = torch.empty(n, C, S, S, dtype=torch.float32, device=self.dev)
         call("mx_input_stage", base, base + o_jobs, img.data_ptr(), n, S, S, st)
+        if nc:
+            call("mx_soft_expand", base, base + o_sj, nc, st)
         call("mx_mask_stage", base, base + o_mj, base, mask.data_ptr(), n, C, S, int(span_cap), st)
         out = {"img": img, "mask": mask}
         if labels is not None:
@@ -204,22 +243,29 @@ class SegStager:
         return out
 
 
+MASK_FORMATS = ("auto", "dense", "compact")
+
+
 class VOC12SegDataset:
     """The reference dataset's role (src/data.py:69-123, `inference=False`): `plan(idx)` is the host half of `__getitem__`
     (JPEG decode, np.load of the soft label, the draws, the tables); a batch of plans goes through a `SegStager`.
     Reads `<mask_root>/<name>.npy` as `muscle_amd.infer_irn --soft_output 1` writes it (float16 [H,W,21]); float32 files
-    are shipped as they are and float64 files rounded to float32.  mask_type='hard' (PNG labels; train_muscle.py does not use
+    are shipped as they are and float64 files rounded to float32.  mask_format: "dense" reads that file, "compact" reads
+    `<mask_root>/<name>.npz` as `infer_irn --soft_output 2` writes it (muscle_amd/softlabel.py), "auto" takes the .npy when it
+    exists - a tree of dense files behaves as it always did - and the .npz otherwise.  mask_type='hard' (PNG labels; train_muscle.py does not use
     it) is refused."""
 
     def __init__(self, img_name_list_path: str, voc12_root: str, mask_root: str, min_scale: float = 0.5, max_scale: float = 1.5,
                  crop_size: int = 448, mask_type: str = "soft", labels: Optional[Dict[str, np.ndarray]] = None,
-                 augment: bool = True):
+                 augment: bool = True, mask_format: str = "auto"):
+        if mask_format not in MASK_FORMATS:
+            raise ValueError(f"mask_format must be one of {MASK_FORMATS} (got {mask_format!r})")
         if mask_type != "soft":
             raise NotImplementedError(f"mask_type={mask_type!r}: only the soft pseudo-labels train_muscle.py trains on "
                                       "(mask_type='soft', <name>.npy) are built on the HIP path")
         self.names = [ln.split(" ")[0].split("/")[-1].split(".")[0] for ln in open(img_name_list_path).read().splitlines()]
         self.root, self.mask_root, self.crop = voc12_root, mask_root, crop_size
-        self.min_scale, self.max_scale, self.augment = min_scale, max_scale, augment
+        self.min_scale, self.max_scale, self.augment, self.mask_format = min_scale, max_scale, augment, mask_format
         if labels is None and os.path.exists("data/cls_labels.npy"):
             labels = np.load("data/cls_labels.npy", allow_pickle=True).item()          # src/data.py:53-56
         self.labels = labels
@@ -227,11 +273,18 @@ class VOC12SegDataset:
     def __len__(self):
         return len(self.names)
 
+    def load_mask(self, name: str):
+        """The soft label of `name`: the dense array or a CompactSoft, as mask_format says.  A missing file raises."""
+        dense = os.path.join(self.mask_root, name + ".npy")
+        if self.mask_format == "dense" or (self.mask_format == "auto" and os.path.exists(dense)):
+            return np.load(dense, allow_pickle=True)
+        return load_compact(os.path.join(self.mask_root, name + ".npz"))
+
     def plan(self, idx: int) -> Tuple[str, SegItemPlan, Optional[np.ndarray]]:
         import PIL.Image
         name = self.names[idx]
         img = PIL.Image.open(os.path.join(self.root, "JPEGImages", name + ".jpg")).convert("RGB")
-        mask = np.load(os.path.join(self.mask_root, name + ".npy"), allow_pickle=True)
+        mask = self.load_mask(name)
         lab = None if self.labels is None else np.asarray(self.labels[name], dtype=np.float32)
         return name, plan_seg_item(img, mask, self.min_scale, self.max_scale, self.crop, self.augment), lab
 

@@ -3,7 +3,9 @@ path.  Same arguments, same files: `<session_name>/_<epoch>.pth` after every epo
 
 Differences a caller can see:
   * the input path runs on the device (`muscle_amd.segdata`): DataLoader workers decode and plan, the GPU resizes, crops and
-    flips image and label; --mask_root holds what `python -m muscle_amd.infer_irn --soft_output 1` writes;
+    flips image and label; --mask_root holds what `python -m muscle_amd.infer_irn --soft_output 1` writes (<name>.npy) or
+    its compact form (--soft_output 2, <name>.npz), chosen by --mask_format (new; auto: the .npy where it exists, else the
+    .npz); the compact form is expanded on the device to the same float16 rows, bit for bit;
   * --val_list (new, default data/val.txt: the list the reference hard-codes) names the images of the per-epoch validation;
   * --crf 1 runs the dense CRF of the validation on the GPU with t=1 (the exact windowed CRF of muscle_amd/crf.py, not
     pydensecrf's lattice filter);
@@ -37,6 +39,9 @@ def parse_args(argv: Optional[List[str]] = None):
     ap.add_argument("--weights", default=None, type=str)
     ap.add_argument("--voc12_root", default="data/VOC2012", type=str)
     ap.add_argument("--mask_root", required=True, type=str, help="directory of soft pseudo-labels <name>.npy, [H,W,21]")
+    ap.add_argument("--mask_format", default="auto", choices=("auto", "dense", "compact"),
+                    help="dense: <name>.npy; compact: <name>.npz (infer_irn --soft_output 2); auto: the .npy where it exists, "
+                         "else the .npz")
     ap.add_argument("--k", default=128, type=int)
     ap.add_argument("--step", default=7, type=int)
     ap.add_argument("--lamb", default=5e-2, type=float)
@@ -76,7 +81,8 @@ def main(argv: Optional[List[str]] = None) -> int:
     os.makedirs(args.tblog_dir, exist_ok=True)
     os.makedirs(args.session_name, exist_ok=True)
     train_dataset = VOC12SegDataset(args.train_list, args.voc12_root, args.mask_root, min_scale=0.5, max_scale=1.75,
-                                    crop_size=args.crop_size, mask_type="soft")             # :119-125
+                                    crop_size=args.crop_size, mask_type="soft",
+                                    mask_format=args.mask_format)                           # :119-125
     if train_dataset.labels is None:
         raise FileNotFoundError("data/cls_labels.npy (the image-level labels, src/data.py:53-56) not found")
     loader = SegLoader(train_dataset, args.batch_size, dev, num_workers=args.num_workers, shuffle=True, drop_last=True,

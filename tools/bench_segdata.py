@@ -3,7 +3,11 @@ sources over the scale range 0.5 .. 1.75 - device time of the stage (one pinned 
 mx_input_stage + mx_mask_stage, HIP events), bytes copied, host time of plan_seg_item and of the stager's packing on one
 core, the muscle_step time of tools/bench_dec.py's configuration on the staged batch, and the per-item time of the scipy
 restatement of the reference's label resize (tests/segdata_ref.py) on one core.  Not the contract bench.
-  python tools/bench_segdata.py [--reps 30] [--no-step]"""
+  python tools/bench_segdata.py [--reps 30] [--no-step]
+  python tools/bench_segdata.py --compact [--reps 30]
+--compact: the same 16 items (labels of three present classes from mx_irn_finish) staged from the dense float16 arrays and
+from their compact form (muscle_amd/softlabel.py), alternating in one run: per form the bytes of the one copy and the
+HIP-event time of the stage; the result is appended to profiles/segdata_bench.txt.  Nothing else is measured then."""
 import os, sys, time, random
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -22,8 +26,52 @@ ims = [R.synth_image(H, W, i) for i in range(N)]
 masks = [R.synth_label(H, W, 100 + i) for i in range(N)]
 scales = [0.5 + 1.25 * i / (N - 1) for i in range(N)]
 
-def plan_all():
+def plan_all(masks=masks):
     return [D.plan_seg_item(ims[i], masks[i], scales[i], scales[i], S) for i in range(N)]
+
+
+def compact_run():
+    from muscle_amd import indexing
+    h, w = (H + 3) // 4, (W + 3) // 4
+    dense, compact = [], []
+    for i in range(N):
+        rw = torch.from_numpy(synth.uniform(200 + i, "rw", (20, 1, h, w)).astype(np.float32)) ** 2
+        for c in range(20):
+            if c not in ((i + 1) % 20, (i + 8) % 20, (i + 15) % 20):
+                rw[c] *= 0.0
+        dense.append(indexing.finish_semseg(rw.to(dev), H, W, 0.35, soft_output=True)[1].cpu().numpy())
+        compact.append(indexing.finish_semseg(rw.to(dev), H, W, 0.35, soft_output="compact")[1])
+    forms = {}
+    for name, src in (("dense", dense), ("compact", compact)):
+        random.seed(0); torch.manual_seed(0)
+        forms[name] = (plan_all(src), D.SegStager(dev, N, S))
+    out = {}
+    for name, (plans, stager) in forms.items():
+        for _ in range(3): out[name] = stager(plans)
+    torch.cuda.synchronize()
+    same = all(torch.equal(out["dense"][k], out["compact"][k]) for k in ("img", "mask"))
+    ms = {name: 0.0 for name in forms}
+    rounds, per = 6, max(1, reps // 6)
+    for _ in range(rounds):                                   # alternating: both forms see the same clocks and the same neighbours
+        for name, (plans, stager) in forms.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(per): stager(plans)
+            e1.record(); torch.cuda.synchronize()
+            ms[name] += e0.elapsed_time(e1) / (rounds * per)
+    lines = [f"tools/bench_segdata.py --compact: batch {N} at {S}x{S} from {H}x{W} labels of 3 present classes, scales {scales[0]:.2f} .. "
+             f"{scales[-1]:.2f}, {rounds} x {per} reps per form, alternating; staged batches of the two forms bit-equal: {same}"]
+    for name, (plans, stager) in forms.items():
+        lines.append(f"  {name:7s}: {stager.last_bytes/1e6:8.2f} MB in the one copy, {ms[name]:.3f} ms/batch between HIP events "
+                     f"(copy, mx_color_jitter, mx_resample, mx_input_stage" + (", mx_soft_expand" if name == "compact" else "") + ", mx_mask_stage)")
+    print("\n".join(lines))
+    with open(os.path.join(ROOT, "profiles", "segdata_bench.txt"), "a") as f:
+        f.write("\n" + "\n".join(lines) + "\n")
+
+
+if "--compact" in sys.argv:
+    compact_run()
+    sys.exit(0)
 
 plans = plan_all()
 t0 = time.perf_counter()
