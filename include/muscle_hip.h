@@ -679,6 +679,56 @@ int mx_ir_label(const unsigned char* rgb, const float* cams, const int* keys, in
 int mx_crf_label(const unsigned char* rgb, const int* labels, int L, int H, int W, int t, float gt_prob, float sxy_g, float w_g,
                  float sxy_b, float srgb, float w_b, float trunc, void* ws, unsigned char* pred, float* q_out, void* stream);
 
+/* ---- the permutohedral-lattice backend of both CRFs (csrc/lattice.hip): the filter pydensecrf evaluates the models of
+ * src/imutils.py:439-456 and src/imutils.py:477-491 on (Adams, Baek & Davis 2010).  A DIFFERENT model from the windowed sums above
+ * (its messages differ from the exact ones by up to a quarter of their size on sparse lattices), selectable, never the default; its
+ * cost per pass does not grow with the kernel width.  What is pinned is the algorithm below against its numpy restatement
+ * (tests/lattice_ref.py); parity with pydensecrf itself is not pinned.
+ *
+ * Features, fp32 with fp32 divisions: D = 2: f = (x / sxy, y / sxy);  D = 5: f = (x / sxy, y / sxy, r / srgb, g / srgb, b / srgb).
+ * Construction per pixel, fp32, every operation rounded on its own (no fused multiply-add), in this order:
+ *   sf[i] = (D+1) sqrt(2/3) / sqrt((i+1)(i+2))   (double, rounded to fp32 once)
+ *   sm = 0;  for j = D..1: cf = f[j-1] * sf[j-1]; el[j] = sm - j * cf; sm += cf;    el[0] = sm
+ *   rd[i] = floor(el[i] * fp32(1 / (D+1)) + 0.5);  rem0[i] = rd[i] * (D+1);  sum = sum_i rd[i]
+ *   for i < j: if el[i] - rem0[i] < el[j] - rem0[j] then rank[i]++ else rank[j]++
+ *   sum > 0: rank >= D+1-sum -> rem0 -= D+1, rank += sum - (D+1); the others rank += sum
+ *   sum < 0: rank < -sum     -> rem0 += D+1, rank += D+1 + sum;   the others rank += sum
+ *   b[0..D+1] = 0;  for i = 0..D: v = (el[i] - rem0[i]) / (D+1); b[D-rank[i]] += v; b[D+1-rank[i]] -= v;    b[0] += 1 + b[D+1]
+ *   vertex r = 0..D: key[i] = rem0[i] + canon[r][rank[i]] for i < D, canon[r][k] = r for k <= D-r, else r - (D+1); weight b[r]
+ * Distinct keys get one vertex id each (ids may differ from run to run; no value depends on them).  Blur neighbours of a vertex
+ * in direction j = 0..D: n1 = the vertex with key - 1 in every coordinate but key[j] + D in coordinate j (j < D), n2 = key + 1 but
+ * key[j] - D; -1 when absent.
+ * Filter of C channels: splat val[vertex] += b[r] * in[pixel] (64-bit fixed point, integer atomics: the same bits in every run);
+ * blur for j = 0, 1, .., D in this order val' = val + 0.5 (val[n1_j] + val[n2_j]), absent = 0; slice out[pixel] =
+ * alpha sum_r b[r] val[vertex_r], alpha = 1 / (1 + 2^-D).  H * W <= 2^24 / 6, 1 <= C <= 32.  Nothing synchronises with the host. */
+/* src/imutils.py:439-456: bytes of a lattice workspace for D in {2, 5}: the worst case of H*W*(D+1) vertices and C channels */
+long mx_lattice_ws(int D, int H, int W, int C);                         /* < 0: bad arguments */
+/* src/imutils.py:439-456: build the lattice of the uint8 image rgb [H,W,3] in ws (16-byte aligned).  srgb <= 0: the spatial
+ * kernel, D = 2 (rgb is not read); else the bilateral one, D = 5.  An image whose key range does not fit the packed 64-bit hash
+ * key at these widths is refused before any launch. */
+int mx_lattice_build(const unsigned char* rgb, int H, int W, float sxy, float srgb, void* ws, void* stream);
+/* src/imutils.py:439-456: out [C,H,W] = the filter of in [C,H,W] on the lattice that mx_lattice_build left in ws, which must have
+ * been sized for at least C channels */
+int mx_lattice_filter(void* ws, const float* in, float* out, int C, void* stream);
+/* src/imutils.py:439-456: copies of the structure for tests, M = H*W*(D+1) rows each: vid [H*W][D+1] vertex ids, weight
+ * [H*W][D+1], keys [M][D] (the first count rows are vertices), nbr [2(D+1)][M] (row 2j: n1_j, row 2j+1: n2_j), count [1] */
+int mx_lattice_export(void* ws, int* vid, float* weight, int* keys, int* nbr, int* count, void* stream);
+/* The CRFs with both kernels on lattices, as pydensecrf runs them: n_m = 1 / sqrt(filter_m(1) + 1e-20), message
+ * w_m n_m filter_m(n_m Q), and the unary, softmax, argmax and conf rules of the windowed entries above, whose argument lists these
+ * keep (without trunc / fused).  ws: mx_crf_lattice_ws(L, H, W) bytes, 16-byte aligned. */
+/* src/imutils.py:439-456: workspace bytes of the three entries below for L labels, 1 <= L <= 24 */
+long mx_crf_lattice_ws(int L, int H, int W);                            /* < 0: bad arguments */
+/* src/imutils.py:439-456: mx_crf_inference on lattices */
+int mx_crf_inference_lattice(const unsigned char* rgb, const float* prob, int L, int H, int W, int t, float confidence, float sxy_g,
+                             float w_g, float sxy_b, float srgb, float w_b, void* ws, float* q_out, unsigned char* pred, void* stream);
+/* src/imutils.py:477-491: mx_crf_label on lattices */
+int mx_crf_label_lattice(const unsigned char* rgb, const int* labels, int L, int H, int W, int t, float gt_prob, float sxy_g, float w_g,
+                         float sxy_b, float srgb, float w_b, void* ws, unsigned char* pred, float* q_out, void* stream);
+/* src/imutils.py:477-491 twice + the combination: mx_ir_label on lattices (both problems as columns of one filter where 2L <= 32) */
+int mx_ir_label_lattice(const unsigned char* rgb, const float* cams, const int* keys, int C, int H, int W, float fg_thres, float bg_thres,
+                        int t, float gt_prob, float sxy_g, float w_g, float sxy_b, float srgb, float w_b, void* ws, unsigned char* conf,
+                        unsigned char* pred2, float* q_out, void* stream);
+
 /* ---- the IRN edge / displacement network of infer_irn.py:66 (src/backbones/resnet50_irn.py:215-232 on src/backbones/resnet50.py),
  * inference only.  Its 1x1 convolutions are mx_pw_fwd calls; these are the pieces the EfficientNet path has no use for.
  * fp32, fixed summation order, no atomics. */

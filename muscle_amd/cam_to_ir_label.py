@@ -6,7 +6,9 @@ For every name of --infer_list: <voc12_root>/JPEGImages/<name>.jpg and <cam_dir>
 
 What a caller should know:
   * the CRF is the windowed model of `infer_seg --crf 2` with the label unary (--crf_trunc: R_m = ceil(trunc * sxy_m)); the window
-    is part of the model, so the maps are not bit-identical with pydensecrf's;
+    is part of the model, so the maps are not bit-identical with pydensecrf's.  --crf_pairwise lattice runs the CRFs on
+    permutohedral lattices instead (pydensecrf's own approximation, cost independent of the bilateral width; a different model,
+    pinned against a numpy restatement, not against pydensecrf itself); the default is window;
   * JPEG decode and np.load run on --num_workers host threads ahead of the device, the PNGs are written by one writer thread
     behind a bounded queue (drained, and a write error re-raised, before the script exits); one workspace is kept per image size
     and only the label map is read back per image;
@@ -32,6 +34,8 @@ def parse_args(argv: Optional[List[str]] = None):
     ap.add_argument("--conf_fg_thres", default=0.30, type=float)
     ap.add_argument("--conf_bg_thres", default=0.05, type=float)
     ap.add_argument("--crf_trunc", default=4.0, type=float, help="window half-width R_m = ceil(trunc * sxy_m); <= 0: all pairs")
+    ap.add_argument("--crf_pairwise", default="window", choices=("window", "lattice"),
+                    help="exact windowed sums, or the permutohedral lattice (--crf_trunc is ignored)")
     ap.add_argument("--num_workers", default=4, type=int, help="host threads that decode JPEGs and load dicts ahead of the device")
     return ap.parse_args(argv)
 
@@ -86,7 +90,7 @@ def main(argv: Optional[List[str]] = None) -> int:
                 if it + ahead < len(names):
                     pending.append(pool.submit(load_item, args.voc12_root, args.cam_dir, names[it + ahead]))
                 conf = cam_to_ir_label(img, cam_dict, conf_fg_thres=args.conf_fg_thres, conf_bg_thres=args.conf_bg_thres,
-                                       trunc=args.crf_trunc)
+                                       trunc=args.crf_trunc, pairwise=args.crf_pairwise)
                 writer.put(os.path.join(args.ir_label_out_dir, name + ".png"), conf.cpu().numpy())
                 print(name, it, flush=True)
     finally:

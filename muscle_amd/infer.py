@@ -150,14 +150,18 @@ def load_cam_dict(path: str) -> Dict[int, np.ndarray]:
 
 
 def infer_seg(model, img_list: List[torch.Tensor], H: int, W: int, cls_label=None, return_prob: bool = False, crf_img=None,
-              crf_t: int = 4, crf_trunc: float = 4.0) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+              crf_t: int = 4, crf_trunc: float = 4.0, crf_pairwise: str = "window") -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """infer_seg.py:88-133.  model: MuSCLe(mode='dec'); img_list: [1,3,Hs,Ws] device tensors in the order
     of VOC12ClsDatasetMSF (scale-major, plain then flipped; data.MSFStager builds it); cls_label: optional [K] class scores
     (entry 0, the background, is not used: :125).  Returns (pred uint8 [H,W], the fp32 mean probability map [K,H,W] if
     return_prob else None), both on the device.
     crf_img: the original uint8 image [H,W,3] (numpy or tensor).  With it the dense CRF of :128-129 runs on the mean map
     (crf.crf_inference with crf_t iterations, scale_factor 1.5, window crf_trunc): pred is argmax Q and the returned map
-    is Q.  Without it nothing of the CRF runs and the result is what it was before the CRF existed, bit for bit."""
+    is Q.  Without it nothing of the CRF runs and the result is what it was before the CRF existed, bit for bit.
+    crf_pairwise: "window" (the exact windowed sums, the default) or "lattice" (the permutohedral lattice of muscle_amd.lattice:
+    pydensecrf's own approximation, a different model; crf_trunc is ignored)."""
+    from .lattice import check_pairwise
+    check_pairwise(crf_pairwise)
     if not img_list:
         raise ValueError("infer_seg needs at least one pass")
     model.eval()
@@ -193,7 +197,8 @@ def infer_seg(model, img_list: List[torch.Tensor], H: int, W: int, cls_label=Non
         call("mx_seg_infer", ptr(tab), len(rows), lds, K, H, W, ptr(cls), ptr(pred), ptr(prob), stream())
         if crf_img is not None:
             from .crf import crf_run
-            prob, pred = crf_run(crf_img, prob, crf_t, 1.5, K, 0.5, crf_trunc, want_q=return_prob, want_pred=True)
+            prob, pred = crf_run(crf_img, prob, crf_t, 1.5, K, 0.5, crf_trunc, want_q=return_prob, want_pred=True,
+                                 pairwise=crf_pairwise)
     return pred, prob
 
 

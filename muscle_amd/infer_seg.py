@@ -5,7 +5,9 @@ Differences a caller can see:
   * the dense CRF: --crf 2 [--crf_trunc 4.0] runs the reference's CRF model (imutils.crf_inference, t=4) on the GPU with
     its pairwise sums evaluated exactly over a square window (muscle_amd/crf.py).  --crf 1 in the reference means
     pydensecrf's lattice filter on the CPU, whose label maps are not reproduced bit for bit: it stays refused, with a
-    message that points to --crf 2, and --crf defaults to 0 (the reference defaults to 1);
+    message that points to --crf 2, and --crf defaults to 0 (the reference defaults to 1).  --crf 2 --crf_pairwise lattice
+    runs the same model on permutohedral lattices instead (muscle_amd/lattice.py): pydensecrf's own approximation on the GPU,
+    pinned against a numpy restatement of the algorithm, not against pydensecrf itself; the default is window;
   * --gt_dir (new, optional): the SegmentationClass directory; prints do_python_eval's IoU table for the written maps;
   * --num_workers and --tblog are accepted and unused (the multi-scale list is built on the device, nothing is logged).
 """
@@ -33,6 +35,8 @@ def parse_args(argv: Optional[List[str]] = None):
     ap.add_argument("--out_seg", default=None, type=str)
     ap.add_argument("--crf", default=0, type=int, help="0: none; 2: the dense CRF on the GPU, exact windowed kernels (1 = pydensecrf: refused)")
     ap.add_argument("--crf_trunc", default=4.0, type=float, help="--crf 2: window half-width in units of sxy (<= 0: all pairs)")
+    ap.add_argument("--crf_pairwise", default="window", choices=("window", "lattice"),
+                    help="--crf 2: exact windowed sums, or the permutohedral lattice (pydensecrf's approximation; --crf_trunc is ignored)")
     ap.add_argument("--bifpn", default=3, type=int)
     ap.add_argument("--pretrained", default="b7", type=str)
     ap.add_argument("--gt_dir", default=None, type=str, help="SegmentationClass directory: print the IoU table")
@@ -85,7 +89,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         if args.cls_dir:
             cls = np.load(os.path.join(args.cls_dir, name + ".npy"), allow_pickle=True).squeeze()
         crf_img = np.asarray(img, dtype=np.uint8) if args.crf == 2 else None                # infer_seg.py:128-129, t=4
-        pred, _ = infer_seg(model, stager(img, scales), H, W, cls_label=cls, crf_img=crf_img, crf_t=4, crf_trunc=args.crf_trunc)
+        pred, _ = infer_seg(model, stager(img, scales), H, W, cls_label=cls, crf_img=crf_img, crf_t=4, crf_trunc=args.crf_trunc,
+                            crf_pairwise=args.crf_pairwise)
         if args.out_seg is not None:
             save_seg_png(os.path.join(args.out_seg, name + ".png"), pred)
         if ev is not None:
