@@ -804,6 +804,50 @@ long mx_gn_bwd_ws(int N, int HW, int C, int G);
 int mx_gn_bwd(const float* dY, const float* X, const float* stat, const float* gamma, int N, int HW, int C, int G, void* ws, long ws_bytes,
               float* dX, float* dgamma, float* dbeta, void* stream);
 
+/* ---- instance pseudo-labels from the displacement field (IRN's published make_ins_seg_labels step, as DESIGN.md "Instance
+ * pseudo-labels" specifies it in six steps; csrc/irn_ins.hip).  Everything after the network is O(H*W) memory on the device.
+ * Only integer atomics (min / max / add): every result is independent of the execution order. */
+
+/* Step 1, centroids.  dp [2,h,w] (plane 0 = dy, plane 1 = dx, finite); cent int32 [2,h,w] (y plane, x plane).  One thread per pixel
+ * starts at its own coordinate and moves `iterations` times by the bilinear sample of dp at (ceil, floor) taps, each product and sum one
+ * fp32 operation in the written order (no fused multiply-add), clipped to the image; then rounds half to even.  The field is staged in
+ * LDS when 8*h*w bytes fit 160 KiB, read through L2 otherwise.  iterations >= 0. */
+int mx_irn_centroids(const float* dp, int h, int w, int iterations, int* cent, void* stream);
+/* Step 2, first line: weak[h,w] int32 = sqrt(dp[1]^2 + dp[0]^2) < thres ? 1 : 0, fp32, that operation order. */
+int mx_irn_weak(const float* dp, int h, int w, float thres, int* weak, void* stream);
+/* Steps 2 and 6, connected components: pixels with equal non-zero int32 labels that touch along an edge (4-connectivity) form a
+ * component; root[h,w] int32 = the smallest linear index y*w + x of the pixel's component, -1 where label is 0.  Union-find: 16x16
+ * tiles in LDS, tile borders merged with atomicMin on the parent array in ws, then every pixel follows its chain to the root.  Three
+ * launches whatever the input; nothing is read back.  ws: mx_ccl_ws(h, w) bytes, contents need not survive.  h*w < 2^31. */
+long mx_ccl_ws(int h, int w);                                            /* < 0: bad arguments */
+int mx_ccl(const int* label, int h, int w, int* root, void* ws, void* stream);
+/* Steps 2 and 6, compressing the ids that occur to 0..count-1 in ascending order.  The id of pixel p is root[q], q = p without cent,
+ * q = cent[p] * w + cent[n + p] with cent (step 2: the component at the pixel's centroid); ids lie in -1..n-1, n = h*w < 2^30.
+ * mx_id_mark: marks int32 [n+1] (zero-filled here), marks[id+1] = 1 for every id that occurs (marks[0]: the background, -1).
+ * mx_id_rank: rank[n+1] = exclusive prefix sum of marks (one workgroup), count[0] = the number of distinct ids, count[1] = marks[0].
+ * mx_id_apply: out[p] = rank[id(p) + 1] (step 2's cluster map: background first if it occurs). */
+int mx_id_mark(const int* root, const int* cent, int h, int w, int* marks, void* stream);
+int mx_id_rank(const int* marks, int n1, int* rank, int* count, void* stream);
+int mx_id_apply(const int* root, const int* cent, int h, int w, const int* rank, int* out, void* stream);
+/* Step 3: x[(k*I + i)*n + p] = cluster[p] == i ? cam[k*n + p] : 0; cam [K,n], cluster int32 [n] in 0..I-1, x [K*I, n] fully written. */
+int mx_irn_ins_split(const float* cam, const int* cluster, int K, int I, int n, float* x, void* stream);
+/* Step 5.  mx_irn_up_max: max_scratch[0] = the bits of the maximum mx_irn_finish divides by (the same kernel, so the same bits),
+ * for any C > 0.  mx_irn_ins_finish: with that maximum and the arithmetic of csrc/irn_soft.h, label[H,W] int32 = argmax over
+ * [bg_thres, rw_up_1 / max .. rw_up_C / max] (first maximum wins, 0 = background) and win[H,W] fp32 = the winning value; no [C,H,W]
+ * array is written.  A maximum of 0 gives label 0 and win = bg_thres everywhere.  H <= 4h, W <= 4w. */
+int mx_irn_up_max(const float* rw, int C, int h, int w, int H, int W, unsigned* max_scratch, void* stream);
+int mx_irn_ins_finish(const float* rw, int C, int h, int w, int H, int W, float bg_thres, const unsigned* max_scratch, int* label,
+                      float* win, void* stream);
+/* Step 6 after mx_ccl + mx_id_mark/rank on the label map (n = H*W pixels): segment s = rank[root+1] - marks[0] numbers the components in
+ * the order of their first pixel.  area[s] = pixel count (integer add), score_bits[s] = the bits of max win over the segment (integer
+ * max on the bit patterns; win >= 0), seg_label[s] / seg_first[s] = label and index of the first pixel.  area and score_bits hold nseg
+ * entries and are zero-filled here.  mx_seg_map: seg_map[p] = order[s] + 1 (order int32 [nseg]: the segment's final number), 0 where
+ * root[p] < 0. */
+int mx_seg_stats(const int* label, const int* root, const float* win, const int* rank, const int* marks, int n, int nseg, int* area,
+                 unsigned* score_bits, int* seg_label, int* seg_first, void* stream);
+int mx_seg_map(const int* root, const int* rank, const int* marks, const int* order, int n, int nseg, int* seg_map,
+               void* stream);
+
 #ifdef __cplusplus
 }
 #endif

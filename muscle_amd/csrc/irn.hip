@@ -152,16 +152,28 @@ int mx_irn_transition(float* dense, int n4, int ld, float beta, float* colsum, v
   return MX_OK;
 }
 
+// The maximum every value is divided by, alone: mx_irn_finish's first launch, also used by mx_irn_ins_finish (irn_ins.hip), so both
+// divide by the same bits.
+int mx_irn_up_max(const float* rw, int C, int h, int w, int H, int W, unsigned* max_scratch, void* stream) {
+  MX_CHECK_ARG(rw && max_scratch && C > 0 && h > 0 && w > 0 && H > 0 && W > 0 && H <= 4 * h && W <= 4 * w, "irn_up_max: bad args");
+  hipStream_t st = (hipStream_t)stream;
+  hipMemsetAsync(max_scratch, 0, sizeof(unsigned), st);
+  long b1 = ((long)C * H * W + 255) / 256;
+  if (b1 > 4096) b1 = 4096;
+  hipLaunchKernelGGL(irn_up_max_kernel, dim3((unsigned)b1), dim3(256), 0, st, rw, C, h, w, H, W, max_scratch);
+  MX_LAUNCH_CHECK();
+  return MX_OK;
+}
+
 int mx_irn_finish(const float* rw, int C, int h, int w, int H, int W, float bg_thres, unsigned* max_scratch, unsigned char* label,
                   void* soft_half, void* stream) {
   MX_CHECK_ARG(rw && max_scratch && label && C > 0 && C < 255 && h > 0 && w > 0 && H > 0 && W > 0 && H <= 4 * h && W <= 4 * w,
                "irn_finish: bad args (the label map is the top-left HxW crop of the 4x upsampled maps)");
+  const int rc = mx_irn_up_max(rw, C, h, w, H, W, max_scratch, stream);
+  if (rc != MX_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
-  hipMemsetAsync(max_scratch, 0, sizeof(unsigned), st);
-  long b1 = ((long)C * H * W + 255) / 256, b2 = ((long)H * W + 255) / 256;
-  if (b1 > 4096) b1 = 4096;
+  long b2 = ((long)H * W + 255) / 256;
   if (b2 > 4096) b2 = 4096;
-  hipLaunchKernelGGL(irn_up_max_kernel, dim3((unsigned)b1), dim3(256), 0, st, rw, C, h, w, H, W, max_scratch);
   hipLaunchKernelGGL(irn_label_kernel, dim3((unsigned)b2), dim3(256), 0, st, rw, C, h, w, H, W, max_scratch, bg_thres, label,
                      (__half*)soft_half);
   MX_LAUNCH_CHECK();

@@ -9,7 +9,10 @@ Differences a caller can see:
   * --irn_network is accepted and ignored: the one network the reference ships (src.backbones.resnet50_irn) is built in;
   * nothing is downloaded: --irn_weights_name must name a checkpoint (the reference fetches ImageNet weights first and then
     overwrites them with the checkpoint);
-  * --walk stencil (not in the reference) runs the random walk matrix-free; the default, dense, is the reference's way.
+  * --walk stencil (not in the reference) runs the random walk matrix-free; the default, dense, is the reference's way;
+  * --ins_seg_out_dir DIR (not in the reference: IRN's published make_ins_seg_labels step) also writes the instance
+    pseudo-label `DIR/<name>.npy`, the dict {'score' [n], 'mask' bool [n,H,W], 'class' [n]} of muscle_amd/ins_seg.py, from
+    the same network forward; --walk applies to both walks.  Without the flag nothing changes.
 """
 from __future__ import annotations
 
@@ -37,6 +40,11 @@ def parse_args(argv: Optional[List[str]] = None):
     ap.add_argument("--walk", default="dense", choices=("dense", "stencil"),
                     help="the random walk: dense = exp_times squarings of the n x n transition matrix (the reference's way), "
                          "stencil = 2^exp_times matrix-free steps on an fp64 state (O(n) memory)")
+    ap.add_argument("--ins_seg_out_dir", default=None, type=str,
+                    help="also write instance pseudo-labels <name>.npy here (muscle_amd/ins_seg.py); off by default")
+    ap.add_argument("--ins_seg_bg_thres", default=0.25, type=float)
+    ap.add_argument("--ins_refine_iters", default=300, type=int, help="centroid refinement iterations of the instance path")
+    ap.add_argument("--ins_dp_thres", default=2.5, type=float, help="displacement magnitude below which a pixel seeds an instance")
     args = ap.parse_args(argv)
     if args.irn_network != ap.get_default("irn_network"):
         print(f"[muscle_amd] note: --irn_network {args.irn_network} ignored; the ResNet-50 IRN is the one network built here",
@@ -62,12 +70,22 @@ def main(argv: Optional[List[str]] = None) -> int:
     if args.soft_output:
         os.makedirs(args.sem_seg_out_dir, exist_ok=True)
     os.makedirs(args.sem_seg_out_dir + "_png", exist_ok=True)
+    ins_kw = None
+    if args.ins_seg_out_dir:
+        from muscle_amd.ins_seg import save_instances, warn_all_zero
+        os.makedirs(args.ins_seg_out_dir, exist_ok=True)
+        ins_kw = dict(bg_thres=args.ins_seg_bg_thres, iterations=args.ins_refine_iters, dp_thres=args.ins_dp_thres)
     for it, name in enumerate(read_names(args.infer_list)):
         img = PIL.Image.open(os.path.join(args.voc12_root, "JPEGImages", name + ".jpg")).convert("RGB")
         pair = torch.cat(stager(img, (1.0,)), dim=0)                                                 # image + flip, color_norm'ed
         cam = load_cam_dict(os.path.join(args.cam_dir, name + ".npy"))
         res = infer_irn(model, pair, cam, beta=args.beta, exp_times=args.exp_times, bg_thres=args.sem_seg_bg_thres,
-                        soft_output="compact" if args.soft_output == 2 else bool(args.soft_output), method=args.walk)
+                        soft_output="compact" if args.soft_output == 2 else bool(args.soft_output), method=args.walk, ins_seg=ins_kw)
+        if ins_kw is not None:
+            res, ins = res
+            if ins.vmax == 0:
+                warn_all_zero(name)
+            save_instances(os.path.join(args.ins_seg_out_dir, name + ".npy"), ins)
         if args.soft_output == 2:
             if res[1].vmax > 0:
                 save_compact(os.path.join(args.sem_seg_out_dir, name + ".npz"), res[1])

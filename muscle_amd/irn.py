@@ -454,19 +454,27 @@ def cam_stack(cam_dict, H: int, W: int, device) -> torch.Tensor:
 
 
 def infer_irn(model: EdgeDisplacement, img_pair: torch.Tensor, cam_dict, *, beta=8, exp_times=6, bg_thres=0.35,
-              soft_output=False, method: str = "dense"):
+              soft_output=False, method: str = "dense", ins_seg=None):
     """infer_irn.py:64-92 for one image: the network, the CAM down-scaling (:76), the random walk (:77) and the label step
     (:79-92).  img_pair: [2,3,H,W] on the device; cam_dict: {class index: float32 [H,W]}.  Returns the uint8 label map [H,W]
     (and the fp16 [H,W,21] array with soft_output) on the device; soft_output="compact" gives the `softlabel.CompactSoft` (host
     arrays) in the array's place.  method: the walk of indexing.propagate_to_edge, "dense" (matrix squarings) or "stencil"
-    (matrix-free)."""
+    (matrix-free).  ins_seg: None, or the keyword arguments {bg_thres, iterations, dp_thres} of
+    `ins_seg.instances_from_field`: the same forward then also feeds the instance path (with this call's beta, exp_times and
+    method) and (the result above, ins_seg.InstanceLabels) is returned."""
     H, W = img_pair.shape[2:]
-    edge, _dp = model(img_pair)
+    edge, dp = model(img_pair)
     with torch.no_grad():
         cams = cam_stack(cam_dict, H, W, img_pair.device)
         down = ops.resize_planar_halfpixel(cams, edge.shape[1], edge.shape[2])
         rw = indexing.propagate_to_edge(down, edge, beta=beta, exp_times=exp_times, radius=5, method=method)
-        return indexing.finish_semseg(rw, H, W, bg_thres, soft_output=soft_output)
+        res = indexing.finish_semseg(rw, H, W, bg_thres, soft_output=soft_output)
+    if ins_seg is None:
+        return res
+    from .ins_seg import instances_from_field
+    keys = sorted(int(k) for k in cam_dict)                    # the planes of `down` the instance path needs: no second upload or resize
+    return res, instances_from_field(edge, dp, cam_dict, H, W, beta=beta, exp_times=exp_times, method=method,
+                                     down=down[keys].contiguous() if keys else None, **ins_seg)
 
 
 def voc_color_map(n: int = 256) -> np.ndarray:
