@@ -60,19 +60,33 @@ static ColGeom col_geom(long rows, int C, int rps, long rows_limit /*rows that o
 }
 
 // F::eval(r, c, v0, v1): contributes two float4 partials for element block (row r, cols c..c+3)
-// sum of P partial float4s, `stride` floats apart, in index order (four loads in flight, one fixed association)
-__device__ __forceinline__ float4 ordered_sum4(const float* p, int P, long stride) {
-  float4 t = ld4(p);
+// sum of P partial float4s, `stride` floats apart, in index order (four loads in flight, one fixed association), accumulated in T
+template <typename T>
+__device__ __forceinline__ float4 ordered_sum4_as(const float* p, int P, long stride) {
+  const float4 f = ld4(p);
+  T tx = f.x, ty = f.y, tz = f.z, tw = f.w;
   int i = 1;
   for (; i + 3 < P; i += 4) {
     const float4 a = ld4(p + i * stride), b = ld4(p + (i + 1) * stride), c = ld4(p + (i + 2) * stride), d = ld4(p + (i + 3) * stride);
-    t.x += a.x; t.y += a.y; t.z += a.z; t.w += a.w;
-    t.x += b.x; t.y += b.y; t.z += b.z; t.w += b.w;
-    t.x += c.x; t.y += c.y; t.z += c.z; t.w += c.w;
-    t.x += d.x; t.y += d.y; t.z += d.z; t.w += d.w;
+    tx += (T)a.x; ty += (T)a.y; tz += (T)a.z; tw += (T)a.w;
+    tx += (T)b.x; ty += (T)b.y; tz += (T)b.z; tw += (T)b.w;
+    tx += (T)c.x; ty += (T)c.y; tz += (T)c.z; tw += (T)c.w;
+    tx += (T)d.x; ty += (T)d.y; tz += (T)d.z; tw += (T)d.w;
   }
-  for (; i < P; ++i) { const float4 a = ld4(p + i * stride); t.x += a.x; t.y += a.y; t.z += a.z; t.w += a.w; }
-  return t;
+  for (; i < P; ++i) {
+    const float4 a = ld4(p + i * stride);
+    tx += (T)a.x; ty += (T)a.y; tz += (T)a.z; tw += (T)a.w;
+  }
+  return make_float4((float)tx, (float)ty, (float)tz, (float)tw);
+}
+// The join of a sample's row blocks.  Up to 64 partials (every per-sample sum of a training batch: at most 32 row blocks at 32
+// samples) it is an fp32 chain.  Longer joins - the whole-tensor sums with one sample and up to 1000 row blocks - run in fp64 and
+// round once, like the join of the BatchNorm statistics: an fp32 chain over 1000 partials of one sign was off by 12-18 x 2^-24 of
+// the sum, several times the error of the streaming part before it (tests/test_gpu_bn_kernels.py).  fp64 for every join cost
+// 0.4 ms per B7 step (96.5 against 96.1, twice) - the last workgroup of every (sample, column chunk) runs this alone.
+constexpr int JOIN_FP32_MAX = 64;
+__device__ __forceinline__ float4 ordered_sum4(const float* p, int P, long stride) {
+  return P <= JOIN_FP32_MAX ? ordered_sum4_as<float>(p, P, stride) : ordered_sum4_as<double>(p, P, stride);
 }
 
 // PER_SAMPLE: out0[sample][C] = the per-sample column sums.  A sample's rows are cut into gridDim.x row blocks; each
@@ -189,7 +203,8 @@ static int colreduce_parts(long rows, int C) {
 }
 
 // geometry of the per-sample reductions (mx_pool_sum, mx_se_bn1_pool): falls back to one row block per sample when the
-// launch would need more arrival counters than the scratch header holds
+// launch would need more arrival counters than the scratch header holds (a guard only: N * colchunks > 1024 already leaves
+// col_geom one workgroup per sample and chunk, so no shape reaches the fallback with several row blocks)
 static ColGeom pool_geom(long rows, int C, int rps, dim3* grid, int planes = 1) {
   const int N = (int)(rows / rps);
   ColGeom g = col_geom(rows, C, rps, rps, N, planes);
