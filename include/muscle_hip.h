@@ -651,7 +651,7 @@ int mx_crf_inference(const unsigned char* rgb, const float* prob, int L, int H, 
                      float sxy_b, float srgb, float w_b, float trunc, void* workspace, float* q_out, unsigned char* pred, void* stream);
 
 /* ---- IR labels from CAMs: the label CRF (src/imutils.py:477-491, crf_inference_label) and IRN's cam_to_ir_label around it;
- * csrc/ir_label.hip -------------------------------------------------------------------------------------------------------- */
+ * csrc/crf.hip, the message kernel of the section above with the label unary ---------------------------------------------- */
 
 /* The model of the section above (same k_m, n_m, window R_m = ceil(trunc * sxy_m) and update; the window is part of the model, so
  * label maps are not bit-identical with pydensecrf's lattice filter) with the unary of unary_from_labels(zero_unsure=False) for L

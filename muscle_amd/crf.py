@@ -29,34 +29,18 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 import torch
 
-from ._lib import MuscleHipError, call, lib, ptr, stream
-from .lattice import check_pairwise, crf_lattice_workspace
+from ._lib import call, lib, ptr, stream
+from .lattice import cached_workspace, check_pairwise, crf_lattice_workspace, device_image
 
 # imutils.py:452-453: addPairwiseGaussian(sxy=3/scale_factor, compat=1), addPairwiseBilateral(sxy=32/scale_factor, srgb=10, compat=10)
 GAUSS_SXY, GAUSS_W = 3.0, 1.0
 BILATERAL_SXY, BILATERAL_SRGB, BILATERAL_W = 32.0, 10.0, 10.0
 
-_ws: Dict[Tuple[int, int, int], torch.Tensor] = {}
+_ws: Dict[tuple, torch.Tensor] = {}
 
 
 def _workspace(dev: torch.device, H: int, W: int) -> torch.Tensor:
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), H, W)
-    ws = _ws.get(key)
-    if ws is None:
-        nbytes = lib().mx_crf_workspace_bytes(1, H, W)
-        if nbytes < 0:
-            raise MuscleHipError(f"mx_crf_workspace_bytes failed: {lib().mx_last_error().decode()}")
-        if len(_ws) >= 4:                                      # a few image sizes at most stay resident
-            _ws.pop(next(iter(_ws)))
-        ws = _ws[key] = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
-    return ws
-
-
-def _device_image(img, dev: torch.device) -> torch.Tensor:
-    t = img if torch.is_tensor(img) else torch.from_numpy(np.array(img))       # a copy: PIL-backed arrays are read-only
-    if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:
-        raise ValueError(f"img must be uint8 [H,W,3] (got {t.dtype} {tuple(t.shape)})")
-    return t.to(dev).contiguous()
+    return cached_workspace(_ws, lib().mx_crf_workspace_bytes, dev, (1, H, W), 4)
 
 
 def crf_run(img, probs, t: int, scale_factor: float, labels: int, confidence: float, trunc: float, want_q: bool = True,
@@ -74,7 +58,7 @@ def crf_run(img, probs, t: int, scale_factor: float, labels: int, confidence: fl
         raise ValueError(f"probs must be [labels={labels},H,W] (got {tuple(p.shape)})")
     p = p.to(dev, torch.float32).contiguous()
     L, H, W = p.shape
-    im = _device_image(img, dev)
+    im = device_image(img, dev)
     if tuple(im.shape[:2]) != (H, W):
         raise ValueError(f"img is {tuple(im.shape[:2])}, probs {(H, W)}")
     if not scale_factor > 0:
@@ -106,21 +90,12 @@ LABEL_GAUSS_SXY, LABEL_GAUSS_W = 3.0, 3.0
 LABEL_BILATERAL_SXY, LABEL_BILATERAL_SRGB, LABEL_BILATERAL_W = 50.0, 5.0, 10.0
 LABEL_MODEL = (LABEL_GAUSS_SXY, LABEL_GAUSS_W, LABEL_BILATERAL_SXY, LABEL_BILATERAL_SRGB, LABEL_BILATERAL_W)
 
-_label_ws: Dict[Tuple[int, int, int], torch.Tensor] = {}
+_label_ws: Dict[tuple, torch.Tensor] = {}
 
 
 def label_workspace(dev: torch.device, H: int, W: int) -> torch.Tensor:
     """The workspace of mx_ir_label / mx_crf_label for an image size (it does not depend on L); one is kept per size."""
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), H, W)
-    ws = _label_ws.get(key)
-    if ws is None:
-        nbytes = lib().mx_ir_label_ws(2, H, W)
-        if nbytes < 0:
-            raise MuscleHipError(f"mx_ir_label_ws failed: {lib().mx_last_error().decode()}")
-        if len(_label_ws) >= 4:                                # a few image sizes at most stay resident
-            _label_ws.pop(next(iter(_label_ws)))
-        ws = _label_ws[key] = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
-    return ws
+    return cached_workspace(_label_ws, lib().mx_ir_label_ws, dev, (2, H, W), 4)
 
 
 def crf_label_run(img, labels, t: int, n_labels: int, gt_prob: float, trunc: float, want_q: bool = False,
@@ -134,7 +109,7 @@ def crf_label_run(img, labels, t: int, n_labels: int, gt_prob: float, trunc: flo
     dev = lab.device if lab.is_cuda else torch.device("cuda", torch.cuda.current_device())
     lab = lab.to(dev, torch.int32).contiguous()
     H, W = lab.shape
-    im = _device_image(img, dev)
+    im = device_image(img, dev)
     if tuple(im.shape[:2]) != (H, W):
         raise ValueError(f"img is {tuple(im.shape[:2])}, labels {(H, W)}")
     L = int(n_labels)

@@ -1,6 +1,6 @@
 // Permutohedral-lattice filter (Adams, Baek & Davis 2010) and the two dense CRFs on it: the approximation pydensecrf evaluates the
 // CRFs of src/imutils.py:439-456 (crf_inference) and src/imutils.py:477-491 (crf_inference_label) with.  A selectable backend
-// beside the exact windowed kernels of crf.hip / ir_label.hip: a DIFFERENT model (include/muscle_hip.h states it), whose cost per
+// beside the exact windowed kernels of crf.hip: a DIFFERENT model (include/muscle_hip.h states it), whose cost per
 // pass is O(N * D) whatever the kernel width.
 //
 // Build, once per image and kernel (D = 2: (x, y) / sxy;  D = 5: (x / sxy, y / sxy, r / srgb, g / srgb, b / srgb)):
@@ -30,6 +30,7 @@
 // All of it gather- and bandwidth-bound; every kernel's grid covers the worst case N (D+1) vertices and exits above the
 // vertex count, which stays on the device: nothing synchronises with the host.
 #include "common.h"
+#include "crf_model.h"
 #include <math.h>
 #include <string.h>
 
@@ -501,35 +502,25 @@ bool lat_find(void* ws, LatDesc& d) {
 // ---- the CRFs on two lattices -------------------------------------------------------------------------------------------------
 // Maps are pixel-major [N][C], C = G * L columns: problem g in columns g*L .. g*L+L-1.
 
-// U = -log(clip(confidence * p + (1 - confidence) / L, 1e-5, 1)), Q_0 = softmax(-U)   (crf_unary_kernel of crf.hip)
+// U = -log(clip(confidence * p + (1 - confidence) / L, 1e-5, 1)), Q_0 = softmax(-U)
 __global__ void lat_unary_prob_kernel(const float* prob, int L, int N, float confidence, float* U, float* q0) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
   const float base = (1.0f - confidence) / (float)L;
-  float m = -INFINITY;
   for (int l = 0; l < L; ++l) {
-    const float c = fminf(fmaxf(confidence * prob[(long)l * N + i] + base, 1e-5f), 1.0f);
-    const float u = -logf(c);
+    const float u = crf_prob_unary(confidence, prob[(long)l * N + i], base);
     U[(long)i * L + l] = u;
-    m = fmaxf(m, -u);
+    q0[(long)i * L + l] = -u;
   }
-  float s = 0.f;
-  for (int l = 0; l < L; ++l) { const float e = expf(-U[(long)i * L + l] - m); q0[(long)i * L + l] = e; s += e; }
-  const float inv = 1.0f / s;
-  for (int l = 0; l < L; ++l) q0[(long)i * L + l] *= inv;
+  crf_softmax_row(q0 + (long)i * L, L);
 }
 
-// the two thresholded argmax maps (first maximum wins: a CAM value equal to the threshold is background)
+// the two thresholded argmax maps
 __global__ void lat_cam_labels_kernel(const float* cams, int Cc, int N, float fg_thres, float bg_thres, unsigned char* lab) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
-  float bf = fg_thres, bb = bg_thres;
-  int lf = 0, lb = 0;
-  for (int c = 0; c < Cc; ++c) {
-    const float v = cams[(long)c * N + i];
-    if (v > bf) { bf = v; lf = c + 1; }
-    if (v > bb) { bb = v; lb = c + 1; }
-  }
+  int lf, lb;
+  crf_cam_labels(cams, Cc, N, i, fg_thres, bg_thres, lf, lb);
   lab[i] = (unsigned char)lf;
   lab[(long)N + i] = (unsigned char)lb;
 }
@@ -537,25 +528,21 @@ __global__ void lat_cam_labels_kernel(const float* cams, int Cc, int N, float fg
 __global__ void lat_in_labels_kernel(const int* labels, int L, int N, unsigned char* lab) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
-  const int v = labels[i];
-  lab[i] = (unsigned char)((v >= 0 && v < L) ? v : 255);
+  lab[i] = (unsigned char)crf_in_label(labels[i], L);
 }
 
-// unary_from_labels(zero_unsure=False) of problems g0 .. g0+G-1 and Q_0 = softmax(-U)   (irl_label_kernel of ir_label.hip)
+// unary_from_labels(zero_unsure=False) of problems g0 .. g0+G-1 and Q_0 = softmax(-U)
 __global__ void lat_unary_lab_kernel(const unsigned char* lab, int g0, int G, int L, int N, float u_own, float u_oth, float* U, float* q0) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= N * G) return;
   const int i = idx / G, g = idx % G;
   const int own = lab[(long)(g0 + g) * N + i];
-  const float m = fmaxf(-u_own, -u_oth);
-  const float e_own = expf(-u_own - m), e_oth = expf(-u_oth - m);
-  float s = 0.f;
-  for (int l = 0; l < L; ++l) s += (l == own) ? e_own : e_oth;
-  const float inv = 1.0f / s;
+  const CrfLabelE e = crf_label_exp(u_own, u_oth);
+  const float inv = crf_label_inv(e, own, L);
   const long o = (long)i * (G * L) + g * L;
   for (int l = 0; l < L; ++l) {
     U[o + l] = (l == own) ? u_own : u_oth;
-    q0[o + l] = ((l == own) ? e_own : e_oth) * inv;
+    q0[o + l] = ((l == own) ? e.own : e.oth) * inv;
   }
 }
 
@@ -566,37 +553,20 @@ __global__ void lat_final_kernel(const float* U, const float* Mg, const float* M
   if (idx >= N * G) return;
   const int i = idx / G, g = idx % G;
   const long o = (long)i * (G * L) + g * L;
-  float m = -INFINITY;
-  for (int l = 0; l < L; ++l) {
-    const float x = Mg ? (Mg[o + l] - U[o + l]) + Mb[o + l] : -U[o + l];
-    q_next[o + l] = x;
-    m = fmaxf(m, x);
-  }
-  float s = 0.f;
-  for (int l = 0; l < L; ++l) { const float e = expf(q_next[o + l] - m); q_next[o + l] = e; s += e; }
-  const float inv = 1.0f / s;
-  int best = 0; float bv = -1.f;
-  for (int l = 0; l < L; ++l) {
-    const float q = q_next[o + l] * inv;
-    q_next[o + l] = q;
-    if (q > bv) { bv = q; best = l; }
-    if (last && q_out) q_out[((long)(g0 + g) * L + l) * N + i] = q;
-  }
-  if (last) {
-    if (pred) pred[(long)(g0 + g) * N + i] = (unsigned char)best;
-    if (pred2) pred2[(long)(g0 + g) * N + i] = (unsigned char)best;
-  }
+  for (int l = 0; l < L; ++l) q_next[o + l] = Mg ? (Mg[o + l] - U[o + l]) + Mb[o + l] : -U[o + l];
+  const int best = crf_softmax_row(q_next + o, L);
+  if (!last) return;
+  if (q_out)
+    for (int l = 0; l < L; ++l) q_out[((long)(g0 + g) * L + l) * N + i] = q_next[o + l];
+  if (pred) pred[(long)(g0 + g) * N + i] = (unsigned char)best;
+  if (pred2) pred2[(long)(g0 + g) * N + i] = (unsigned char)best;
 }
 
-// the three-line combination of cam_to_ir_label
+// the IR label out of the two argmax maps
 __global__ void lat_conf_kernel(const unsigned char* pred, const int* keys, int N, unsigned char* conf) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
-  const int fg = keys[pred[i]], bg = keys[pred[(long)N + i]];
-  int c = fg;
-  if (fg == 0) c = 255;
-  if (bg + fg == 0) c = 0;
-  conf[i] = (unsigned char)c;
+  conf[i] = crf_combine(keys[pred[i]], keys[pred[(long)N + i]]);
 }
 
 int lat_crf_columns(int L) { return 2 * L <= LAT_MAXC ? 2 * L : L; }
@@ -785,7 +755,7 @@ int mx_ir_label_lattice(const unsigned char* rgb, const float* cams, const int* 
   const int N = H * W, L = C + 1;
   lat_crf_carve(w, ws, lat_crf_columns(L));
   const LatModel m = {t, sxy_g, w_g, sxy_b, srgb, w_b};
-  const float u_own = -logf(gt_prob), u_oth = -logf((1.0f - gt_prob) / (float)(L - 1));
+  const CrfLabelU u = crf_label_unary(gt_prob, L);
   if (t > 0) {
     const int rc = lat_crf_setup(w, rgb, st);
     if (rc != MX_OK) return rc;
@@ -794,7 +764,7 @@ int mx_ir_label_lattice(const unsigned char* rgb, const float* cams, const int* 
   MX_LAUNCH_CHECK();
   const int G = 2 * L <= LAT_MAXC ? 2 : 1;
   for (int g0 = 0; g0 < 2; g0 += G) {
-    hipLaunchKernelGGL(lat_unary_lab_kernel, dim3(cdiv((long)N * G, 128)), dim3(128), 0, st, w.lab, g0, G, L, N, u_own, u_oth, w.U, w.Q[0]);
+    hipLaunchKernelGGL(lat_unary_lab_kernel, dim3(cdiv((long)N * G, 128)), dim3(128), 0, st, w.lab, g0, G, L, N, u.own, u.oth, w.U, w.Q[0]);
     MX_LAUNCH_CHECK();
     const int rc = lat_crf_iterate(w, m, g0, G, L, q_out, w.pred, pred2, st);
     if (rc != MX_OK) return rc;
@@ -815,14 +785,14 @@ int mx_crf_label_lattice(const unsigned char* rgb, const int* labels, int L, int
   const int N = H * W;
   lat_crf_carve(w, ws, lat_crf_columns(L));
   const LatModel m = {t, sxy_g, w_g, sxy_b, srgb, w_b};
-  const float u_own = -logf(gt_prob), u_oth = -logf((1.0f - gt_prob) / (float)(L - 1));
+  const CrfLabelU u = crf_label_unary(gt_prob, L);
   if (t > 0) {
     const int rc = lat_crf_setup(w, rgb, st);
     if (rc != MX_OK) return rc;
   }
   hipLaunchKernelGGL(lat_in_labels_kernel, dim3(cdiv(N, 128)), dim3(128), 0, st, labels, L, N, w.lab);
   MX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(lat_unary_lab_kernel, dim3(cdiv(N, 128)), dim3(128), 0, st, w.lab, 0, 1, L, N, u_own, u_oth, w.U, w.Q[0]);
+  hipLaunchKernelGGL(lat_unary_lab_kernel, dim3(cdiv(N, 128)), dim3(128), 0, st, w.lab, 0, 1, L, N, u.own, u.oth, w.U, w.Q[0]);
   MX_LAUNCH_CHECK();
   return lat_crf_iterate(w, m, 0, 1, L, q_out, pred, (unsigned char*)nullptr, st);
 }

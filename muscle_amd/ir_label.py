@@ -22,8 +22,8 @@ import numpy as np
 import torch
 
 from ._lib import call, ptr, stream
-from .crf import LABEL_MODEL, _device_image, label_workspace
-from .lattice import check_pairwise, crf_lattice_workspace
+from .crf import LABEL_MODEL, label_workspace
+from .lattice import check_pairwise, crf_lattice_workspace, device_image
 
 CONF_FG_THRES, CONF_BG_THRES = 0.30, 0.05
 CRF_T, CRF_GT_PROB = 10, 0.7                                   # src/imutils.py:477
@@ -54,7 +54,7 @@ def ir_label_run(img, cams, keys: Sequence[int], *, fg_thres: float = CONF_FG_TH
     C, H, W = c.shape
     if len(keys) != C + 1:
         raise ValueError(f"keys must have C+1 = {C + 1} entries (got {len(keys)})")
-    im = _device_image(img, dev)
+    im = device_image(img, dev)
     if tuple(im.shape[:2]) != (H, W):
         raise ValueError(f"img is {tuple(im.shape[:2])}, cams {(H, W)}")
     with torch.cuda.device(dev):

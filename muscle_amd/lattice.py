@@ -8,7 +8,7 @@ restates it in numpy), selectable there with pairwise="lattice".  Parity with py
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import Callable, Dict, Optional
 
 import numpy as np
 import torch
@@ -25,18 +25,42 @@ def check_pairwise(pairwise: str) -> bool:
     return pairwise == "lattice"
 
 
+def device_image(img, dev: Optional[torch.device] = None) -> torch.Tensor:
+    """img (numpy array, PIL-backed array or tensor) checked as uint8 [H,W,3], contiguous on dev (None: the tensor's own device
+    if it is on one, else the current one)."""
+    t = img if torch.is_tensor(img) else torch.from_numpy(np.array(img))       # a copy: PIL-backed arrays are read-only
+    if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:
+        raise ValueError(f"img must be uint8 [H,W,3] (got {t.dtype} {tuple(t.shape)})")
+    if dev is None:
+        dev = t.device if t.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    return t.to(dev).contiguous()
+
+
+def cached_workspace(cache: Dict[tuple, torch.Tensor], size_fn: Callable[..., int], dev: torch.device, args: tuple,
+                     keep: int) -> torch.Tensor:
+    """The workspace of size_fn(*args) bytes on dev out of cache, which holds at most `keep` of them (the oldest one goes): a few
+    image sizes at most stay resident."""
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(),) + args
+    ws = cache.get(key)
+    if ws is None:
+        nbytes = size_fn(*args)
+        if nbytes < 0:
+            raise MuscleHipError(f"{size_fn.__name__} failed: {lib().mx_last_error().decode()}")
+        if len(cache) >= keep:
+            cache.pop(next(iter(cache)))
+        ws = cache[key] = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
+    return ws
+
+
 class PermutohedralLattice:
     """The lattice of one uint8 image [H,W,3] (numpy array or tensor) and one kernel: srgb None (or <= 0) is the spatial kernel
     (D = 2), else the bilateral one (D = 5).  Built once; `filter` may be called any number of times with up to max_channels
     channels."""
 
     def __init__(self, img, sxy: float, srgb: Optional[float] = None, *, max_channels: int = 32):
-        t = img if torch.is_tensor(img) else torch.from_numpy(np.array(img))
-        if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:
-            raise ValueError(f"img must be uint8 [H,W,3] (got {t.dtype} {tuple(t.shape)})")
-        dev = t.device if t.is_cuda else torch.device("cuda", torch.cuda.current_device())
-        self.img = t.to(dev).contiguous()
-        self.H, self.W = int(t.shape[0]), int(t.shape[1])
+        self.img = device_image(img)
+        dev = self.img.device
+        self.H, self.W = int(self.img.shape[0]), int(self.img.shape[1])
         self.D = 5 if (srgb is not None and srgb > 0) else 2
         self.sxy, self.srgb = float(sxy), float(srgb) if self.D == 5 else 0.0
         self.max_channels = int(max_channels)
@@ -74,18 +98,9 @@ class PermutohedralLattice:
         return vid, w, keys[:M], nbr, M
 
 
-_crf_ws = {}
+_crf_ws: Dict[tuple, torch.Tensor] = {}
 
 
 def crf_lattice_workspace(dev: torch.device, L: int, H: int, W: int) -> torch.Tensor:
     """The workspace of the mx_*_lattice CRF entries for L labels and an image size; a few are kept."""
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), L, H, W)
-    ws = _crf_ws.get(key)
-    if ws is None:
-        nbytes = lib().mx_crf_lattice_ws(L, H, W)
-        if nbytes < 0:
-            raise MuscleHipError(f"mx_crf_lattice_ws failed: {lib().mx_last_error().decode()}")
-        if len(_crf_ws) >= 2:
-            _crf_ws.pop(next(iter(_crf_ws)))
-        ws = _crf_ws[key] = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
-    return ws
+    return cached_workspace(_crf_ws, lib().mx_crf_lattice_ws, dev, (L, H, W), 2)
