@@ -848,6 +848,26 @@ int mx_seg_stats(const int* label, const int* root, const float* win, const int*
 int mx_seg_map(const int* root, const int* rank, const int* marks, const int* order, int n, int nseg, int* seg_map,
                void* stream);
 
+/* ---- instance-segmentation evaluation (DESIGN.md "Instance evaluation"; csrc/ins_eval.hip): the integer joint-count table of one
+ * image's prediction against its ground-truth instance map b (uint8 [n_pix], values 0..B, 0 = no object).  Every mask IoU, at every
+ * threshold, follows from the table on the host.  Integer counts and integer atomic adds only, no floating point: the result does not
+ * depend on the execution order.  Both entries OVERWRITE table and bad (no zeroing by the caller) and only enqueue on `stream`.
+ * A value outside its range (a < 0, a > A, b > B) never indexes the table: the pixel is counted in bad[0] and skipped, so bad[0] is
+ * the number of such pixels (each counted once) and the caller decides what a non-zero count means.
+ * Limits: 0 < n_pix < 2^31, A >= 0, n >= 0, 0 <= B <= 255, a table of at most 2^26 cells; anything else is an argument error (negative
+ * return before any launch).  No alignment is asked of a, b or masks: 16-byte packed loads are used where a group of 16 pixels lies
+ * inside the array, byte loads on an unaligned start and a ragged end.
+ *
+ * mx_label_pair_counts: table[a[i]*(B+1) + b[i]] += 1 for every pixel i; a int32 [n_pix] is a non-overlapping label map with values
+ * 0..A (InstanceLabels.seg_map: 0 = none, s = segment s-1); table int32 [(A+1)*(B+1)].  Threads add run lengths, into an LDS tile when
+ * the table has at most 8192 cells; a larger table is added to directly, behind a 1024-slot LDS hash of cells per workgroup that
+ * takes the adds of the cells many threads share.
+ * mx_mask_pair_counts: masks uint8 [n*n_pix] (non-zero = set; masks may overlap or be empty; may be NULL when n = 0); table int32
+ * [(n+1)*(B+1)]: row p in 1..n counts the pixels of mask p-1 by their b value, row 0 counts EVERY pixel (the histogram of b: the
+ * ground-truth areas).  One row of workgroups per table row, each with an LDS histogram of B+1 bins. */
+int mx_label_pair_counts(const int* a, const unsigned char* b, long n_pix, int A, int B, int* table, int* bad, void* stream);
+int mx_mask_pair_counts(const unsigned char* masks, const unsigned char* b, long n_pix, int n, int B, int* table, int* bad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,3 +29,14 @@ from .ir_label import cam_to_ir_label, combine_conf  # noqa: F401,E402  (IR labe
 from .lattice import PermutohedralLattice  # noqa: F401,E402  (the lattice filter; pairwise="lattice" of the CRFs)
 from .ins_seg import (InstanceLabels, cluster_centroids, connected_components, find_centroids,  # noqa: F401,E402
                       infer_irn_instances)  # (instance pseudo-labels from the displacement field; infer_irn --ins_seg_out_dir)
+
+_INS_EVAL = ("InsSegEval", "voc_instances", "pair_table", "mask_iou", "label_pair_counts", "mask_pair_counts")
+
+
+def __getattr__(name):
+    # instance-segmentation evaluation (script: muscle_amd.ins_eval).  Resolved on first use, so that `python -m muscle_amd.ins_eval`
+    # does not find its own module imported by the package before it runs.
+    if name in _INS_EVAL:
+        from . import ins_eval
+        return getattr(ins_eval, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -13,6 +13,9 @@ Differences a caller can see:
   * --ins_seg_out_dir DIR (not in the reference: IRN's published make_ins_seg_labels step) also writes the instance
     pseudo-label `DIR/<name>.npy`, the dict {'score' [n], 'mask' bool [n,H,W], 'class' [n]} of muscle_amd/ins_seg.py, from
     the same network forward; --walk applies to both walks.  Without the flag nothing changes.
+  * --ins_eval 1 (needs --ins_seg_out_dir; IRN's published eval_ins_seg step) also evaluates every instance label as it is made,
+    from its seg_map on the device against SegmentationClass/ and SegmentationObject/ under --voc12_root, and prints the lines of
+    `python -m muscle_amd.ins_eval` at the end (muscle_amd/ins_eval.py).  Off by default; the files written are the same.
 """
 from __future__ import annotations
 
@@ -45,7 +48,12 @@ def parse_args(argv: Optional[List[str]] = None):
     ap.add_argument("--ins_seg_bg_thres", default=0.25, type=float)
     ap.add_argument("--ins_refine_iters", default=300, type=int, help="centroid refinement iterations of the instance path")
     ap.add_argument("--ins_dp_thres", default=2.5, type=float, help="displacement magnitude below which a pixel seeds an instance")
+    ap.add_argument("--ins_eval", default=0, type=int,
+                    help="1: also evaluate the instance labels (VOC AP^r, muscle_amd/ins_eval.py) and print the result at the end")
+    ap.add_argument("--ins_eval_iou", default=[0.25, 0.5, 0.7, 0.75], type=float, nargs="+", help="IoU thresholds of --ins_eval")
     args = ap.parse_args(argv)
+    if args.ins_eval and not args.ins_seg_out_dir:
+        ap.error("--ins_eval 1 evaluates the instance labels: it needs --ins_seg_out_dir")
     if args.irn_network != ap.get_default("irn_network"):
         print(f"[muscle_amd] note: --irn_network {args.irn_network} ignored; the ResNet-50 IRN is the one network built here",
               file=sys.stderr)
@@ -75,6 +83,11 @@ def main(argv: Optional[List[str]] = None) -> int:
         from muscle_amd.ins_seg import save_instances, warn_all_zero
         os.makedirs(args.ins_seg_out_dir, exist_ok=True)
         ins_kw = dict(bg_thres=args.ins_seg_bg_thres, iterations=args.ins_refine_iters, dp_thres=args.ins_dp_thres)
+    ins_ev = None
+    if args.ins_eval:
+        from muscle_amd.ins_eval import InsSegEval, check_gt_files, read_gt_pngs
+        check_gt_files(args.voc12_root, list(read_names(args.infer_list)))
+        ins_ev = InsSegEval(dev, iou_thresholds=args.ins_eval_iou)
     for it, name in enumerate(read_names(args.infer_list)):
         img = PIL.Image.open(os.path.join(args.voc12_root, "JPEGImages", name + ".jpg")).convert("RGB")
         pair = torch.cat(stager(img, (1.0,)), dim=0)                                                 # image + flip, color_norm'ed
@@ -86,6 +99,8 @@ def main(argv: Optional[List[str]] = None) -> int:
             if ins.vmax == 0:
                 warn_all_zero(name)
             save_instances(os.path.join(args.ins_seg_out_dir, name + ".npy"), ins)
+            if ins_ev is not None:
+                ins_ev.add(ins, *read_gt_pngs(args.voc12_root, name))
         if args.soft_output == 2:
             if res[1].vmax > 0:
                 save_compact(os.path.join(args.sem_seg_out_dir, name + ".npz"), res[1])
@@ -96,6 +111,9 @@ def main(argv: Optional[List[str]] = None) -> int:
         else:
             save_palette_png(os.path.join(args.sem_seg_out_dir + "_png", name + ".png"), res)
         print(name, it, flush=True)
+    if ins_ev is not None:
+        for line in ins_ev.lines():
+            print(line, flush=True)
     return 0
 
 
