@@ -147,6 +147,19 @@ int mx_pw_wgrad_small(const float* G, const float* X, int x_mode, const float* x
                       const float* x_gate, int rows_per_sample, float* dW, int R, int Co, int Ci, int ldg, int ldx,
                       void* ws, long ws_bytes, void* stream);
 
+/* The whole backward of the expand convolution (backward of model.py:77) where BOTH of its halves are HBM-bound - (Co, Ci) = (288, 48)
+ * and (192, 32) only: the small-output kernel above also multiplies every 16-row slab of dZ it holds into W[Co,Ci] (the parameter itself,
+ * row-major) and writes dX[R,Ci] = dZ W (+ residual), so G (and G2) cross the fabric once for both gradients and dZ is never written.
+ * dZ = c1*G + c2*G2 + c3 (coef = [3][Co]) or G itself (G2 = coef = null); exact fp32 MFMA in every GEMM mode.  dX and residual share
+ * lddx.  Scratch: [groups][Co*Ci] floats, never more than mx_pw_wgrad_small_ws(R,Co,Ci,0) where that is not 0; dW = null leaves the
+ * partial matrices there for mx_pw_parts_reduce (same kernel, same order: dW += their sum).  _ok: 1 where the engine takes it (one of
+ * the two shapes, R >= 65536); the entry point itself runs any R >= 1 and answers MX_EARG for every other shape before any launch. */
+int mx_pw_bwd_small_fused_ok(int R, int Co, int Ci);
+int mx_pw_bwd_small_fused_groups(int R, int Co, int Ci);
+int mx_pw_bwd_small_fused(const float* G, const float* G2, const float* coef, const float* X, const float* W, float* dW, float* dX,
+                          const float* residual, int R, int Co, int Ci, int ldg, int ldx, int lddx, void* ws, long ws_bytes, void* stream);
+int mx_pw_parts_reduce(const float* part, int groups, int n, float* dW, void* stream);
+
 /* The same weight gradient for LARGE outputs (Co*Ci >= 16384): dW cut into 128/64-wide tiles, the rows into groups, partial
  * tiles per group added in a fixed order - deterministic, no atomics; workgroup ids are XCD-aware so that a row slab crosses
  * the fabric once.  mx_pw_wgrad_tile_ws: bytes of scratch needed for contiguous operands (ldg = Co, ldx = Ci), 0 = shape not taken.

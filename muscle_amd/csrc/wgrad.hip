@@ -21,11 +21,25 @@ struct WgArgs {
   int SG, SX;              // LDS row strides (floats), == 16 mod 32: the 4 rows of a fragment fall on disjoint banks
   const float* G2;         // GBN instantiations: the G operand is c1*G + c2*G2 + c3 per column (BatchNorm backward apply folded
   const float* gcoef;      //   into the load; gcoef = [3][Co]); G2 shares G's leading dimension
+  const float* W;          // DKB instantiations: the conv weight [Co, Ci] (row-major, the parameter itself), and the data gradient
+  float* dX;               //   dX[R, lddx] = dZ W (+ res) leaves the kernel as a by-product of the slabs it already holds
+  const float* res;        //   optional [R, lddx], added to dX
+  int lddx;
 };
 
 // GI / XI: 16-byte chunks of a G / X row per loader lane (a row is shared by NT/16 lanes); XMODE: operand prologue of X.
-template <int TCO, int TCI, int NW, int GI, int XI, int XMODE, bool GBN = false>
-__global__ __launch_bounds__(NW * 64, NW == 4 ? 3 : 4) void wgrad_small_kernel(WgArgs a) {
+//
+// DKB > 0: the fused backward of the expand conv (Co = 32 DKB, Ci = 16 TCI, four waves).  The slab of dZ that the loader wrote is also
+// the A operand of the data gradient dX[16, Ci] = dZ[16, Co] W[Co, Ci]: Co (the K of that product) is cut into four ranges of 8 DKB, one
+// per wave, whose share of W sits in registers as B fragments for the whole kernel (2 DKB TCI of them).  K is permuted inside every
+// block of 8 so that ONE ds_read_b64 (lane (l15, q): dZ[l15][8 t + 2 q + e], e = 0, 1) feeds two consecutive MFMA steps - the fragment of
+// step e holds W[8 t + 2 q + e][.] in the same order.  With the row stride == 16 mod 32 that read is a 4-way bank conflict (8 LDS cycles
+// instead of 2; the plain (row l15, k q) ds_read_b32 would be 8-way, 16 cycles per MFMA step): 4 DKB such reads per workgroup and slab
+// against 120 + 8 DKB TCI MFMAs of 32 cycles.  The four partial 16 x Ci tiles go to one of two LDS buffers (row stride Ci + 4); after the
+// slab's barrier, i.e. during the next slab, one float4 per thread adds them in wave order, adds `res` and stores the dX row piece: one
+// barrier per slab as before.  The weight-gradient half is untouched: same MFMAs in the same order, same partial matrices.
+template <int TCO, int TCI, int NW, int GI, int XI, int XMODE, bool GBN = false, int DKB = 0>
+__global__ __launch_bounds__(NW * 64, DKB ? 2 : (NW == 4 ? 3 : 4)) void wgrad_small_kernel(WgArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int RB = 16, NT = NW * 64, LPR = NT / RB;       // loader lanes per slab row
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -65,7 +79,13 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 3 : 4) void wgrad_small_kernel(W
       if (c < gch) {
         float4 v = rg[i];
         if (GBN && rin) {               // dZ = c1*G + c2*G2 + c3 (rows past the range stay zero: they must not add c3)
-          const float4 k1 = ld4(a.gcoef + 4 * c), k2 = ld4(a.gcoef + a.Co + 4 * c), k3 = ld4(a.gcoef + 2 * a.Co + 4 * c);
+          float4 k1, k2, k3;
+          if (DKB) {                    // the fused form keeps the coefficients in LDS: no global round trip per chunk in front of the MFMAs
+            const float* cf = smem + 2 * slab + 128 * (a.Ci + 4);
+            k1 = ld4(cf + 4 * c); k2 = ld4(cf + a.Co + 4 * c); k3 = ld4(cf + 2 * a.Co + 4 * c);
+          } else {
+            k1 = ld4(a.gcoef + 4 * c); k2 = ld4(a.gcoef + a.Co + 4 * c); k3 = ld4(a.gcoef + 2 * a.Co + 4 * c);
+          }
           const float4 x = rg2[GBN ? i : 0];
           v = make_float4(k1.x * v.x + (k2.x * x.x + k3.x), k1.y * v.y + (k2.y * x.y + k3.y), k1.z * v.z + (k2.z * x.z + k3.z),
                           k1.w * v.w + (k2.w * x.w + k3.w));
@@ -90,8 +110,61 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 3 : 4) void wgrad_small_kernel(W
       }
     }
   };
+  // ---- data-gradient half (DKB > 0 only) ----
+  static_assert(DKB == 0 || (NW == 4 && XMODE == MX_PLAIN), "the fused form: four waves, plain X");
+  constexpr int DK = DKB ? DKB : 1, DN = DKB ? TCI : 1;
+  const int kw = wave * 8 * DKB;                             // this wave's range of Co
+  const int PS = a.Ci + 4;                                   // row stride of a partial tile (floats): rows 4 apart fall on other banks
+  float* const pbase = smem + 2 * slab;                      // [2 buffers][4 waves][16 rows][PS], then the [3][Co] coefficients
+  const int xq = a.Ci >> 2, drow = tid / xq, dc = tid - drow * xq;      // the float4 of the dX slab this thread finishes
+  float wf[DK][2][DN];
+  if (DKB) {
+#pragma unroll
+    for (int t = 0; t < DK; ++t)
+#pragma unroll
+      for (int e = 0; e < 2; ++e)
+#pragma unroll
+        for (int n = 0; n < DN; ++n) wf[t][e][n] = a.W[(long)(kw + 8 * t + 2 * q + e) * a.Ci + 16 * n + l15];
+  }
+  auto dgrad = [&](int cur, int s) {                         // this wave's partial of slab s -> pbase[s & 1][wave]
+    f32x4w da[DN];
+#pragma unroll
+    for (int n = 0; n < DN; ++n) da[n] = f32x4w{0.f, 0.f, 0.f, 0.f};
+    const float* dz = smem + cur * slab + l15 * a.SG + kw + 2 * q;
+#pragma unroll
+    for (int t = 0; t < DK; ++t) {
+      const float2 v = *reinterpret_cast<const float2*>(dz + 8 * t);
+#pragma unroll
+      for (int n = 0; n < DN; ++n) da[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(v.x, wf[t][0][n], da[n], 0, 0, 0);
+#pragma unroll
+      for (int n = 0; n < DN; ++n) da[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(v.y, wf[t][1][n], da[n], 0, 0, 0);
+    }
+    float* pb = pbase + (s & 1) * (64 * PS) + (wave * 16 + 4 * q) * PS + l15;      // da[n][r] = partial dX[4 q + r][16 n + l15]
+#pragma unroll
+    for (int n = 0; n < DN; ++n)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) pb[r * PS + 16 * n] = da[n][r];
+  };
+  auto dx_res = [&](int s) {                                 // the residual piece of slab s, requested early
+    const long r = r_beg + (long)s * RB + drow;
+    return (a.res && drow < RB && r < r_end) ? ld4(a.res + r * a.lddx + 4 * dc) : make_float4(0.f, 0.f, 0.f, 0.f);
+  };
+  auto dx_out = [&](int s, float4 rr) {                      // dX rows of slab s: the four partials in wave order, then the residual
+    const long r = r_beg + (long)s * RB + drow;
+    if (drow < RB && r < r_end) {
+      const float* p = pbase + (s & 1) * (64 * PS) + drow * PS + 4 * dc;
+      float4 v = ld4(p);
+#pragma unroll
+      for (int w = 1; w < 4; ++w) { const float4 u = ld4(p + w * 16 * PS); v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w; }
+      if (a.res) { v.x += rr.x; v.y += rr.y; v.z += rr.z; v.w += rr.w; }
+      st4(a.dX + r * a.lddx + 4 * dc, v);
+    }
+  };
+
   // columns beyond Co / Ci (up to the wave grid's 16-column tiles) stay zero: fragments read them without a test
   for (int i = tid; i < 2 * slab; i += NT) smem[i] = 0.f;
+  if (DKB && GBN)
+    for (int i = tid; i < 3 * a.Co; i += NT) pbase[128 * PS + i] = a.gcoef[i];
   __syncthreads();
 
   f32x4w acc[TCO][TCI];
@@ -107,9 +180,17 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 3 : 4) void wgrad_small_kernel(W
     if (ns > 1) load(r_beg + RB);
   }
   __syncthreads();
+  float4 rr = make_float4(0.f, 0.f, 0.f, 0.f);               // (DKB) the residual piece of the slab before
   for (int s = 0; s < ns; ++s) {
     const int cur = s & 1;
-    if (s + 1 < ns) {
+    if (DKB) {
+      // dX of the previous slab first (its partials: published by the last barrier; its residual piece: requested a slab ago, so the
+      // wait for it is the wait `store` needs anyway - behind the new requests it would drain them in front of the barrier)
+      if (s > 0) dx_out(s - 1, rr);
+      if (s + 1 < ns) store(smem + (cur ^ 1) * slab, r_beg + (long)(s + 1) * RB);
+      rr = dx_res(s);
+      if (s + 2 < ns) load(r_beg + (long)(s + 2) * RB);
+    } else if (s + 1 < ns) {
       store(smem + (cur ^ 1) * slab, r_beg + (long)(s + 1) * RB);
       if (s + 2 < ns) load(r_beg + (long)(s + 2) * RB);
     }
@@ -128,8 +209,10 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 3 : 4) void wgrad_small_kernel(W
 #pragma unroll
         for (int j = 0; j < TCI; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], bv[j], acc[i][j], 0, 0, 0);
     }
+    if (DKB) dgrad(cur, s);
     __syncthreads();
   }
+  if (DKB && ns > 0) dx_out(ns - 1, rr);
   // partial matrix of this workgroup: acc[i][j][r] = dW[16 t_co + 4q + r][16 t_ci + l15]
   float* out = a.part + (long)blockIdx.x * a.Co * a.Ci;
 #pragma unroll
@@ -267,6 +350,42 @@ static WgLaunch wg_dispatch(const WgPlan& p, int Co, int Ci, int x_mode, bool gb
   if (p.tco == TCO && p.tci == TCI && p.nw == NW && gi == GI && xi == XI && x_mode == MODE) return &wg_launch_one<TCO, TCI, NW, GI, XI, MODE>;
   WG_TABLE(WG_TRY)
 #undef WG_TRY
+  return nullptr;
+}
+
+// ---- the fused backward of the expand conv (wgrad_small_kernel<..., DKB>): dW and dX from one pass over (G, G2) ----
+// Exactly two shapes.  The tiling is the small-output kernel's; the workgroup holds 2 DKB TCI weight fragments more and two buffers of
+// partial dX tiles, so two workgroups share a CU instead of three, and the rows are dealt to 512 workgroups: one round.  Under 131 072
+// rows (launches too short for a second round to matter) the row groups stay those of wg_plan: there dW matches mx_pw_wgrad_small* bit
+// for bit, partial matrix by partial matrix.
+static bool wgf_shape(int Co, int Ci) { return (Co == 288 && Ci == 48) || (Co == 192 && Ci == 32); }
+
+static bool wgf_plan(int R, int Co, int Ci, WgPlan* p) {
+  if (R < 1 || !wgf_shape(Co, Ci) || !wg_plan(1 << 20, Co, Ci, p) || p->nw != 4) return false;
+  p->lds_bytes += 2L * 4 * 16 * (Ci + 4) * 4 + 3L * Co * 4;
+  int rows = cdiv(cdiv(R, 512), 16) * 16;
+  if (rows < 64) rows = 64;
+  WgPlan q;
+  if (R < 131072 && wg_plan(R, Co, Ci, &q)) rows = q.rows_per_wg;
+  p->rows_per_wg = rows;
+  p->groups = cdiv(R, rows);
+  return true;
+}
+
+template <int TCO, int TCI, int GI, int XI, bool GBN, int DKB>
+static int wgf_launch_one(const WgArgs& a, const WgPlan& p, hipStream_t st) {
+  const void* fn = reinterpret_cast<const void*>(&wgrad_small_kernel<TCO, TCI, 4, GI, XI, MX_PLAIN, GBN, DKB>);
+  if (p.lds_bytes > 64 * 1024) {
+    const int rc = mx_dyn_lds_optin(fn, 80 * 1024);
+    if (rc != MX_OK) return rc;
+  }
+  hipLaunchKernelGGL((wgrad_small_kernel<TCO, TCI, 4, GI, XI, MX_PLAIN, GBN, DKB>), dim3(p.groups), dim3(256), p.lds_bytes, st, a);
+  return MX_OK;
+}
+
+static WgLaunch wgf_dispatch(const WgPlan& p, int Co, int Ci, bool gbn) {
+  if (Co == 288 && Ci == 48 && p.tco == 5 && p.tci == 3) return gbn ? &wgf_launch_one<5, 3, 5, 1, true, 9> : &wgf_launch_one<5, 3, 5, 1, false, 9>;
+  if (Co == 192 && Ci == 32 && p.tco == 3 && p.tci == 2) return gbn ? &wgf_launch_one<3, 2, 3, 1, true, 6> : &wgf_launch_one<3, 2, 3, 1, false, 6>;
   return nullptr;
 }
 
@@ -1336,6 +1455,58 @@ int mx_pw_wgrad_small_bnbwd(const float* G, const float* G2, const float* coef, 
   MX_CHECK_ARG(G2 && coef, "wgrad_small_bnbwd: null pointer");
   MX_CHECK_ARG((((uintptr_t)G2 | (uintptr_t)coef) & 15) == 0, "wgrad_small_bnbwd: pointers must be 16-byte aligned");
   return wgrad_small_impl(G, G2, coef, MxOperand{X, nullptr, nullptr, nullptr, MX_PLAIN, 1}, dW, R, Co, Ci, ldg, ldx, ws, ws_bytes, stream);
+}
+
+// 1 where the engine should take mx_pw_bwd_small_fused: one of its two shapes, and a reduction as long as the small-output kernel asks
+int mx_pw_bwd_small_fused_ok(int R, int Co, int Ci) { return R >= 65536 && wgf_shape(Co, Ci) ? 1 : 0; }
+
+// partial matrices mx_pw_bwd_small_fused leaves in `ws` ([groups][Co*Ci] floats; never more than mx_pw_wgrad_small_ws holds), 0 = shape not taken
+int mx_pw_bwd_small_fused_groups(int R, int Co, int Ci) {
+  WgPlan p;
+  return wgf_plan(R, Co, Ci, &p) ? p.groups : 0;
+}
+
+// The whole backward of a small expand conv in one pass: dW[Co,Ci] += dZ^T X and dX[R,Ci] = dZ W (+ residual), dZ = c1*G + c2*G2 + c3
+// (coef = [3][Co]) or G itself (G2 = coef = null).  (Co, Ci) = (288, 48) or (192, 32) only, any R >= 1.  W: [Co, Ci] row-major; dX and
+// residual share lddx.  dW = null leaves the partial matrices in ws for a later mx_pw_parts_reduce.
+int mx_pw_bwd_small_fused(const float* G, const float* G2, const float* coef, const float* X, const float* W, float* dW, float* dX,
+                          const float* residual, int R, int Co, int Ci, int ldg, int ldx, int lddx, void* ws, long ws_bytes, void* stream) {
+  MX_CHECK_ARG(wgf_shape(Co, Ci) && R >= 1, "pw_bwd_small_fused: shape R=%d Co=%d Ci=%d not taken (288 x 48 and 192 x 32 only)", R, Co, Ci);
+  MX_CHECK_ARG(G && X && W && dX && ws, "pw_bwd_small_fused: null pointer");
+  MX_CHECK_ARG((G2 == nullptr) == (coef == nullptr), "pw_bwd_small_fused: G2 and coef come together");
+  MX_CHECK_ARG((((uintptr_t)G | (uintptr_t)G2 | (uintptr_t)coef | (uintptr_t)X | (uintptr_t)W | (uintptr_t)dW | (uintptr_t)dX | (uintptr_t)residual |
+                 (uintptr_t)ws) & 15) == 0, "pw_bwd_small_fused: pointers must be 16-byte aligned");
+  MX_CHECK_ARG(ldg % 4 == 0 && ldx % 4 == 0 && lddx % 4 == 0 && ldg >= Co && ldx >= Ci && lddx >= Ci,
+               "pw_bwd_small_fused: leading dimensions (%d, %d, %d) must be multiples of 4 and cover the rows", ldg, ldx, lddx);
+  WgPlan p;
+  MX_CHECK_ARG(wgf_plan(R, Co, Ci, &p), "pw_bwd_small_fused: no plan for R=%d Co=%d Ci=%d", R, Co, Ci);
+  MX_CHECK_ARG(ws_bytes >= (long)p.groups * Co * Ci * 4, "pw_bwd_small_fused: workspace too small");
+  const WgLaunch launch = wgf_dispatch(p, Co, Ci, G2 != nullptr);
+  MX_CHECK_ARG(launch, "pw_bwd_small_fused: no kernel for Co=%d Ci=%d", Co, Ci);
+  WgArgs a{};
+  a.G = G; a.X = MxOperand{X, nullptr, nullptr, nullptr, MX_PLAIN, 1}; a.G2 = G2; a.gcoef = coef;
+  a.part = (float*)ws; a.R = R; a.Co = Co; a.Ci = Ci; a.ldg = ldg; a.ldx = ldx;
+  a.rows_per_wg = p.rows_per_wg; a.WCO = p.wco; a.WCI = p.wci; a.SG = p.SG; a.SX = p.SX;
+  a.W = W; a.dX = dX; a.res = residual; a.lddx = lddx;
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = launch(a, p, st);
+  if (rc != MX_OK) return rc;
+  MX_LAUNCH_CHECK();
+  if (dW) {
+    hipLaunchKernelGGL(wgrad_parts_reduce_kernel, dim3(cdiv((long)Co * Ci, 64)), dim3(256), 0, st, (const float*)ws, p.groups, Co * Ci, dW);
+    MX_LAUNCH_CHECK();
+  }
+  return MX_OK;
+}
+
+// dW[n] += sum_g part[g][n] in the fixed order of the weight-gradient kernels (n a multiple of 4): the deferred half of
+// mx_pw_bwd_small_fused(dW = null)
+int mx_pw_parts_reduce(const float* part, int groups, int n, float* dW, void* stream) {
+  MX_CHECK_ARG(part && dW && groups > 0 && n > 0 && n % 4 == 0, "pw_parts_reduce: bad arguments");
+  MX_CHECK_ARG((((uintptr_t)part | (uintptr_t)dW) & 15) == 0, "pw_parts_reduce: pointers must be 16-byte aligned");
+  mx_launch_parts_reduce(part, groups, n, dW, (hipStream_t)stream);
+  MX_LAUNCH_CHECK();
+  return MX_OK;
 }
 
 bool mx_wgrad_uses_split(int R, int Co, int Ci) {

@@ -389,6 +389,11 @@ FOLD_BN0_EARLY = os.environ.get("MUSCLE_FOLD_BN0_EARLY", "1") == "1"
 # Stride-2 depthwise backward as ONE kernel (ops.dwconv_bwd_fused_s2), as stride 1 has had it since round 1.  MUSCLE_DW_S2_FUSED=0
 # (or flipping `engine.DW_S2_FUSED` at run time) restores bn_bwd_apply + dwconv_bwd_weight + dwconv_bwd_data + the BN0 reduction.
 DW_S2_FUSED = os.environ.get("MUSCLE_DW_S2_FUSED", "1") == "1"
+# Expand convs whose data AND weight gradients are HBM-bound (288 x 48 and 192 x 32 of stage 2, either stride): where
+# ops.bnbwd_fold_takes answers "fused", one kernel (ops.pw_bwd_fused) reads (gx, e_raw) once and leaves both gradients; the apply
+# pass, the data-gradient GEMM and the lane's weight-gradient entry are gone for those blocks.  MUSCLE_PW_BWD_FUSED=0 (or flipping
+# `engine.PW_BWD_FUSED` at run time) restores the schedule above.
+PW_BWD_FUSED = os.environ.get("MUSCLE_PW_BWD_FUSED", "1") == "1"
 # Weight-gradient GEMMs on a second HIP stream (MUSCLE_WGRAD_STREAM=0 turns it off; `engine.WGRAD_SIDE_STREAM` can be
 # flipped at run time).  Nothing in the backward chain consumes them (only the optimizer and the gradient exchange do),
 # they are MFMA-bound, and the chain between two of them (BN backward, SE, depthwise) is HBM-bound.  Measured on
@@ -429,6 +434,10 @@ class _WgradLane:
     def dw_reduce(self, scratch, dW):
         """Queue the addition of a depthwise weight gradient's partial rows (ops.dw_parts_reduce): no consumer before Adam."""
         return self._queue(lambda: ops.dw_parts_reduce(scratch, dW), scratch)
+
+    def pw_reduce(self, part, dW):
+        """Queue the addition of a fused expand-conv backward's partial matrices (ops.pw_parts_reduce): no consumer before Adam."""
+        return self._queue(lambda: ops.pw_parts_reduce(part, dW), part)
 
     def flush(self):
         if self.s is None or not self.pending:
@@ -536,7 +545,19 @@ def _bn0_expand_backward(lane, backbone, cfg: NetCfg, tape: Tape, t: BlockTape, 
     if part0 is not None:
         c0 = ops.bn_bwd_coeffs(part0, M, bn_mod, dw_st, sink.of(bn_mod.weight), sink.of(bn_mod.bias), training)
         wtp = tape.wtp.get(id(m._expand_conv.weight)) if b.expand else None
-        if FOLD_BN0_EARLY and b.stride == 1 and wtp is not None and ops.bnbwd_fold_takes(M, b.cexp, b.cin) == "small":
+        takes = None
+        if FOLD_BN0_EARLY and b.expand and (wtp is not None if b.stride == 1 else PW_BWD_FUSED):
+            takes = ops.bnbwd_fold_takes(M, b.cexp, b.cin)
+            if takes == "fused" and not PW_BWD_FUSED:
+                takes = ops.bnbwd_fold_takes_split(M, b.cexp, b.cin)
+        if takes == "fused":
+            # one kernel on the main stream forms dz slab by slab and leaves both gradients; only the addition of its partial
+            # matrices goes to the lane
+            g_in = ops.pw_bwd_fused(gx2, raw2, c0, t.x.view(M, b.cin), m._expand_conv.weight.view(b.cexp, b.cin),
+                                    sink.of(m._expand_conv.weight).view(b.cexp, b.cin), residual=res, defer=lane.pw_reduce)
+            lane.flush()
+            return g_in.view(N, t.H, t.W, b.cin)
+        if takes == "small" and b.stride == 1:
             # the early fold: both GEMMs form dz in their operand loads, it is never written
             lane.wgrad_bnbwd(gx2, raw2, c0, t.x.view(M, b.cin), sink.of(m._expand_conv.weight).view(b.cexp, b.cin))
             g_in = ops.pw_dgrad_bnbwd_planes(gx2, raw2, c0, wtp, b.cin, residual=res)

@@ -279,11 +279,19 @@ def pw_dgrad_bnbwd_planes(G, X, coef, planes, N_in, *, residual=None):
     return out
 
 
-@_per_mode
 def bnbwd_fold_takes(M, K, N):
-    """Which weight-gradient kernel can fold the BatchNorm backward apply for dZ [M, K] (data gradient against W^T [N, K], weight
-    gradient dW [K, N]) in the current arithmetic, given that the data gradient takes the planes kernel: "small" (the HBM-bound
-    small-output kernel of stages 1-2), "tile" (the split-arithmetic tiled kernel) or None."""
+    """Which kernel can fold the BatchNorm backward apply for dZ [M, K] (data gradient against W^T [N, K], weight gradient
+    dW [K, N]) in the current arithmetic: "fused" (pw_bwd_fused: both gradients from one pass, exact fp32 in every arithmetic), or,
+    given that the data gradient takes the planes kernel, "small" (the HBM-bound small-output weight-gradient kernel of stages 1-2)
+    or "tile" (the split-arithmetic tiled kernel), or None."""
+    if lib().mx_pw_bwd_small_fused_ok(M, K, N):
+        return "fused"
+    return bnbwd_fold_takes_split(M, K, N)
+
+
+@_per_mode
+def bnbwd_fold_takes_split(M, K, N):
+    """bnbwd_fold_takes without the fused kernel: "small", "tile" or None (the answer where pw_bwd_fused is switched off)."""
     if not _planes_take(M, K, N):
         return None
     if lib().mx_pw_wgrad_small_bnbwd_ok(M, K, N):
@@ -305,6 +313,50 @@ def pw_wgrad_bnbwd(G, G2, coef, X, dW):
     need = lib().mx_pw_wgrad_tile_ws(R, Co, Ci, PLAIN)
     ws = _wgrad_workspace(G.device, max(need, 16))
     call("mx_pw_wgrad_tile_bnbwd", ptr(G), ptr(G2), ptr(coef), ptr(X), ptr(dW), R, Co, Ci, G.stride(0), X.stride(0), ws.data_ptr(), ws.numel(), stream())
+
+
+def _rows_ptr(t, what):
+    """Device pointer of a 2-D fp32 row view (unit column stride, any leading dimension)."""
+    if t is None:
+        return None
+    if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1:
+        raise ValueError(f"pw_bwd_fused: {what} must be a 2-D fp32 CUDA tensor with unit column stride")
+    return t.data_ptr()
+
+
+def pw_parts_reduce(part, dW):
+    """dW += the partial matrices a deferred pw_bwd_fused left in `part` [groups, Co*Ci], in the weight-gradient kernels' fixed order."""
+    P, n = part.shape
+    call("mx_pw_parts_reduce", ptr(part), P, n, ptr(dW), stream())
+
+
+def pw_bwd_fused(G, G2, coef, X, W, dW, *, residual=None, defer=None, out=None):
+    """The whole backward of a small expand conv (bnbwd_fold_takes == "fused": 288 x 48 and 192 x 32) in one pass over its wide
+    operands: dW[Co, Ci] += dZ^T X and dX[R, Ci] = dZ W (+ residual), with dZ = c1*G + c2*G2 + c3 (coef [3, Co]) or dZ = G where
+    G2 and coef are None.  Returns dX.  Operands may be row views (leading dimension larger than the width); `out`, if given, is
+    dX's buffer and `residual` must share its leading dimension.
+    defer: a callable taking (part, dW) - the addition of the weight gradient's partial matrices is handed to it (e.g. queued for
+    the side stream, ops.pw_parts_reduce) instead of being launched behind the kernel."""
+    R, Co = G.shape
+    Ci = X.shape[1]
+    dX = out if out is not None else _f32(R, Ci, device=G.device)
+    if G2 is not None and G2.stride(0) != G.stride(0):
+        raise ValueError("pw_bwd_fused: G2 must share G's leading dimension")
+    if residual is not None and residual.stride(0) != dX.stride(0):
+        raise ValueError("pw_bwd_fused: residual must share dX's leading dimension")
+    groups = lib().mx_pw_bwd_small_fused_groups(R, Co, Ci)
+    if defer is not None and groups > 0:
+        part = _f32(groups, Co * Ci, device=G.device)          # its own buffer: the reduce runs later, beside the next launches
+        wsp, wsn, dwp = part.data_ptr(), part.numel() * 4, None
+    else:
+        part = None
+        ws = _wgrad_workspace(G.device, max(lib().mx_pw_wgrad_small_ws(R, Co, Ci, PLAIN), 16))
+        wsp, wsn, dwp = ws.data_ptr(), ws.numel(), ptr(dW)
+    call("mx_pw_bwd_small_fused", _rows_ptr(G, "G"), _rows_ptr(G2, "G2"), ptr(coef), _rows_ptr(X, "X"), ptr(W), dwp, _rows_ptr(dX, "dX"),
+         _rows_ptr(residual, "residual"), R, Co, Ci, G.stride(0), X.stride(0), dX.stride(0), wsp, wsn, stream())
+    if part is not None:
+        defer(part, dW)
+    return dX
 
 
 def wgrad_bnbwd_dz_takes(R, Co, Ci) -> bool:
