@@ -1,11 +1,12 @@
 // Exact-fp32 pointwise-convolution GEMMs on the CDNA4 matrix cores
 // (v_mfma_f32_32x32x2_f32: bit-for-bit an fp32 fma chain, 64 cycles / SIMD).
 //
-// One kernel template covers the three contractions the 1x1 convolutions of an MBConv block need
+// The three contractions the 1x1 convolutions of an MBConv block need
 // (reference: src/efficientnet_pytorch/model.py:77,86 forward; autograd's conv backward):
-//   NT : C[M,N]  = A'[M,K] * W[N,K]^T          forward   (W = conv weight [Cout,Cin])
+//   NT : C[M,N]  = A'[M,K] * W[N,K]^T          forward   (W = conv weight [Cout,Cin]; second-generation kernels below)
 //   NN : C[M,N]  = A'[M,K] * W[K,N]            dgrad     (W = conv weight [Cout,Cin], K=Cout, N=Cin)
 //   TN : C[M,N] += A'[R,M]^T * B'[R,N]         wgrad     (reduction over the R pixel rows, split over blocks)
+// NN and TN share the first kernel template (gemm_kernel).
 // A' / B' are activation matrices [rows, channels] (NHWC) read through an MxOperand prologue, so the
 // BN affine + SiLU + SE gate of the *producer* is applied on the consumer's load and never
 // round-trips HBM.  Epilogue: optional bias / residual / relu, and per-column sum and sum of
@@ -122,8 +123,9 @@ constexpr int gemm_min_waves(int acc_regs, int bk) { return (acc_regs == 64 && b
 template <int LAYOUT, int WM, int WN, int TM, int TN, int BK>
 __global__ __launch_bounds__(256, gemm_min_waves(TM * TN * 16, BK)) void gemm_kernel(GemmArgs g) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
+  static_assert(LAYOUT == L_NN || LAYOUT == L_TN, "gemm_kernel: NN and TN only (NT runs on gemm_nt_kernel)");
   constexpr int PADA = (LAYOUT == L_TN) ? 4 : 1;
-  constexpr int PADB = (LAYOUT == L_NT) ? 1 : 4;
+  constexpr int PADB = 4;
   constexpr int SA = BM + PADA, SB = BN + PADB;
   __shared__ __attribute__((aligned(16))) float smem[2 * BK * SA + 2 * BK * SB];
   float* As = smem;
@@ -179,13 +181,11 @@ __global__ __launch_bounds__(256, gemm_min_waves(TM * TN * 16, BK)) void gemm_ke
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
   typename std::conditional<LAYOUT == L_TN, SlabN<BM, PADA, BK>, SlabK<BM, PADA, BK>>::type sa;
-  typename std::conditional<LAYOUT == L_NT, SlabK<BN, PADB, BK>, SlabN<BN, PADB, BK>>::type sb;
+  SlabN<BN, PADB, BK> sb;
 
   auto load = [&](int k0) {
-    if constexpr (LAYOUT == L_TN) sa.load(g.a, A, g.lda, m0, g.M, k0, kend, tid);
-    else sa.load(g.a, A, g.lda, m0, g.M, k0, kend, tid);
-    if constexpr (LAYOUT == L_NT) sb.load(g.b, B, g.ldb, n0, g.N, k0, kend, tid);
-    else sb.load(g.b, B, g.ldb, n0, g.N, k0, kend, tid);
+    sa.load(g.a, A, g.lda, m0, g.M, k0, kend, tid);
+    sb.load(g.b, B, g.ldb, n0, g.N, k0, kend, tid);
   };
 
   MX_GEMM_STAMP(g, 0);
@@ -332,44 +332,32 @@ static void launch(const GemmArgs& g, int batch_or_splits, hipStream_t st) {
 
 // Tile configurations (block tile BM x BN; 4 waves).  EfficientNet's channel counts (48, 80, 160, 224, 288, 480,
 // 1344, ...) are multiples of 32 but rarely of 128, so BN is chosen per call.  Measured on MI355X over the B7
-// shapes (tools/gemm_sweep.py, profiles/r01_gemm_sweep.txt): the small 128x32 tile (7 workgroups per CU hide the
+// shapes (profiles/r01_gemm_sweep.txt): the small 128x32 tile (7 workgroups per CU hide the
 // staging latency; the A re-reads it causes are absorbed by L2) wins or ties everywhere except where N is a
 // multiple of 96 or 128; tiles wider than 128 and 256-row tiles lose at every shape and were dropped.
+// Only the tiles pick_cfg can return, per layout, are compiled.
 struct TileCfg { int bm, bn; };
+enum Tile { T128x128, T128x96, T128x64, T128x32 };
 static const TileCfg kCfgs[] = {
-    {128, 128},   // 0: 2x2 waves, 2x2 MFMA tiles each
-    {128, 96},    // 1: 4x1 waves, 1x3
-    {128, 32},    // 2: 4x1 waves, 1x1
-    {256, 64},    // 3: 4x1 waves, 2x2   (kept for the tuning sweep)
-    {128, 64},    // 4: 4x1 waves, 1x2   (kept for the tuning sweep)
-    {128, 128},   // 5: as 0 with BK = 32
-    {128, 64},    // 6: 2x2 waves, 2x1
-    {128, 64},    // 7: 2x2 waves, 2x1, BK = 32
-    {128, 32},    // 8: as 2 with BK = 32
-    {128, 96},    // 9: as 1 with BK = 32
-    {256, 128},   // 10: 2x2 waves, 4x2 tiles
-    {128, 256},   // 11: 2x2 waves, 2x4 tiles
+    {128, 128},   // T128x128: 2x2 waves, 2x2 MFMA tiles each
+    {128, 96},    // T128x96:  4x1 waves, 1x3
+    {128, 64},    // T128x64:  4x1 waves, 1x2   (NN only)
+    {128, 32},    // T128x32:  4x1 waves, 1x1
 };
-constexpr int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
 
 // Tile choice.  For the weight gradient (TN: the reduction is split until the grid fills the chip anyway) the measured
 // rule stands: 128x128 when N is a multiple of 128, 128x96 when a multiple of 96, else 128x32.  For the forward and
 // data-gradient GEMMs one more effect matters on 256 CUs: with few tiles per CU the slowest CU sets the time.
 // N = 384 at M = 25088 is 588 tiles of 128x128 = 2.3 per CU (some CUs run 3: 77 % balance) but 1176 tiles of 128x64 =
 // 4.6 per CU (92 %): measured 487 -> 407 us.  score = tile efficiency x (1 - N padding) x per-CU balance.
-static int pick_cfg(int layout, int M, int N, int K) {
-  (void)K;
-  if (const char* e = getenv("MX_GEMM_CFG")) {           // tuning override (tools/gemm_sweep.py)
-    int forced = atoi(e);
-    if (forced >= 0 && forced < kNumCfgs) return forced;
-  }
+static Tile pick_cfg(int layout, int M, int N) {
   if (layout == L_TN) {
-    if (N >= 384 && N % 128 == 0) return 0;
-    if (N % 96 == 0) return 1;
-    return 2;
+    if (N >= 384 && N % 128 == 0) return T128x128;
+    if (N % 96 == 0) return T128x96;
+    return T128x32;
   }
-  static const struct { int cfg; double eff; } cand[] = {{0, 1.00}, {1, 0.97}, {4, 0.95}, {2, 0.85}};   // big-shape TFLOP/s ratios
-  int best = 2;
+  static const struct { Tile cfg; double eff; } cand[] = {{T128x128, 1.00}, {T128x96, 0.97}, {T128x64, 0.95}, {T128x32, 0.85}};   // big-shape TFLOP/s ratios
+  Tile best = T128x32;
   double best_score = -1.0;
   for (const auto& c : cand) {
     const TileCfg t = kCfgs[c.cfg];
@@ -377,7 +365,7 @@ static int pick_cfg(int layout, int M, int N, int K) {
     const double pad = (double)N / (double)(nt * t.bn);
     const double per_cu = (double)tiles / 256.0;
     const double balance = per_cu / (double)(long)(per_cu + 0.999999);
-    if (c.cfg == 4 && N % 64 != 0) continue;               // 128x64 is only measured where it needs no padding
+    if (c.cfg == T128x64 && N % 64 != 0) continue;         // 128x64 is only measured where it needs no padding
     double score = c.eff * pad * balance;
     if (per_cu < 2.0) score *= 0.85;                         // a lone workgroup per CU cannot hide its own latencies
     if (score > best_score + 1e-9) { best_score = score; best = c.cfg; }
@@ -387,19 +375,13 @@ static int pick_cfg(int layout, int M, int N, int K) {
 
 template <int LAYOUT>
 static void dispatch(const GemmArgs& g, int zdim, hipStream_t st) {
-  switch (pick_cfg(LAYOUT, g.M, g.N, g.K)) {
-    case 0: launch<LAYOUT, 2, 2, 2, 2>(g, zdim, st); break;
-    case 1: launch<LAYOUT, 4, 1, 1, 3>(g, zdim, st); break;
-    case 2: launch<LAYOUT, 4, 1, 1, 1>(g, zdim, st); break;
-    case 3: launch<LAYOUT, 4, 1, 2, 2>(g, zdim, st); break;
-    case 4: launch<LAYOUT, 4, 1, 1, 2>(g, zdim, st); break;
-    case 5: launch<LAYOUT, 2, 2, 2, 2, 32>(g, zdim, st); break;
-    case 6: launch<LAYOUT, 2, 2, 2, 1>(g, zdim, st); break;
-    case 7: launch<LAYOUT, 2, 2, 2, 1, 32>(g, zdim, st); break;
-    case 8: launch<LAYOUT, 4, 1, 1, 1, 32>(g, zdim, st); break;
-    case 9: launch<LAYOUT, 4, 1, 1, 3, 32>(g, zdim, st); break;
-    case 10: launch<LAYOUT, 2, 2, 4, 2>(g, zdim, st); break;
-    default: launch<LAYOUT, 2, 2, 2, 4>(g, zdim, st); break;
+  switch (pick_cfg(LAYOUT, g.M, g.N)) {
+    case T128x128: launch<LAYOUT, 2, 2, 2, 2>(g, zdim, st); break;
+    case T128x96: launch<LAYOUT, 4, 1, 1, 3>(g, zdim, st); break;
+    case T128x64:
+      if constexpr (LAYOUT == L_NN) launch<LAYOUT, 4, 1, 1, 2>(g, zdim, st);     // (the TN rule never takes it)
+      break;
+    case T128x32: launch<LAYOUT, 4, 1, 1, 1>(g, zdim, st); break;
   }
 }
 
@@ -723,7 +705,8 @@ static __device__ __forceinline__ void split3_pair(float x0, float x1, unsigned&
 
 // NJ = 32-column MFMA tiles per wave: tile 128 x (64 NJ).  NJ = 1 doubles the tile count where 128 x 128 leaves CUs idle.
 template <int AMODE, int NJ>
-__global__ __launch_bounds__(256, NJ == 4 ? 2 : 3) void gemm_nt_split_kernel(GemmArgs g) {
+__global__ __launch_bounds__(256, 3) void gemm_nt_split_kernel(GemmArgs g) {
+  static_assert(NJ == 1 || NJ == 2, "gemm_nt_split_kernel: 128 x 64 and 128 x 128 tiles only");
   constexpr int BM = 128, BN = 64 * NJ, WN = 2, WNC = 32 * NJ;   // WNC: columns per wave
   constexpr int PA_ = 128 * 32, PB_ = BN * 32;              // bytes of one [rows][16 bf16] plane of A / B
   constexpr int STAGE = 3 * PA_ + 3 * PB_;
@@ -1217,7 +1200,7 @@ static void launch_nt_split_t(const GemmArgs& g, int batch, hipStream_t st) {
 }
 
 // 128 x 128 unless the narrower tile pads fewer columns or balances the 768 resident workgroups (3 per CU) better
-static int g_split_nj = getenv("MX_GEMM_SPLIT_NJ") ? atoi(getenv("MX_GEMM_SPLIT_NJ")) : 0;     // tile override of both split generations (tools/gemm_nj.py, gemm_lab): 1 force 128 x 64, 2 force 128 x 128, 3: 64 / 128 only, >= 16: that width (second generation)
+static int g_split_nj = 0;     // tile override of both split generations (lab hook: tools/hip/gemm_lab.hip assigns it): 1 force 128 x 64, 2 force 128 x 128, 3: 64 / 128 only, >= 16: that width (second generation)
 static void launch_nt_split(const GemmArgs& g, int batch, hipStream_t st) {
   const int forced = g_split_nj;
   auto score = [&](int bn, double eff) {
@@ -1228,7 +1211,7 @@ static void launch_nt_split(const GemmArgs& g, int batch, hipStream_t st) {
     return eff * pad * balance;
   };
   // Long reductions (the project convs and their mirror, the expand data gradient: K = Cexp) are priced with a model fitted to
-  // measurements (tools/gemm_nj.py): a launch costs floor(rounds) + min(1, tail + 0.12) rounds of 768 workgroups - a partly
+  // measurements: a launch costs floor(rounds) + min(1, tail + 0.12) rounds of 768 workgroups - a partly
   // filled last round is cheaper than a full one because its workgroups share their CU with fewer neighbours - and the
   // 64-wide tile does 0.87 of the 128-wide tile's work per unit time.  (K = 3840 -> N = 640 took 876 us with the 64-wide tile
   // the first rule picked and 788 us with the 128-wide one.)
@@ -1240,8 +1223,7 @@ static void launch_nt_split(const GemmArgs& g, int batch, hipStream_t st) {
   const bool narrow = forced ? forced == 1
                     : g.K >= 1024 ? cost(64, 0.87) < cost(128, 1.0)
                                   : score(64, 0.92) > score(128, 1.0) + 1e-9;
-  if (forced == 4) launch_nt_split_t<4>(g, batch, st);
-  else if (narrow) launch_nt_split_t<1>(g, batch, st);
+  if (narrow) launch_nt_split_t<1>(g, batch, st);
   else launch_nt_split_t<2>(g, batch, st);
 }
 
@@ -1377,7 +1359,7 @@ static int check_operand(const MxOperand& o, const char* nm) {
 
 // TN (weight gradient): the pixel reduction is split so the grid fills the chip (>= ~1024 blocks), >= 512 rows per slice
 static int tn_splits(int M, int N, int K, int* ksplit) {
-  const TileCfg tc = kCfgs[pick_cfg(L_TN, M, N, K)];
+  const TileCfg tc = kCfgs[pick_cfg(L_TN, M, N)];
   long tiles = (long)cdiv(M, tc.bm) * cdiv(N, tc.bn);
   // workgroup target of the split (swept 1024/1536/2048/3072/4096 on the final code: 150.7 / 149.6 / 148.9 / 149.8 / 149.6 ms per step)
   constexpr long SPLIT_TARGET = 2048;
@@ -1400,8 +1382,8 @@ static int gemm_common(int layout, GemmArgs& g, int batch, hipStream_t st) {
   g.stamps = mx_gemm_stamps;
   if (layout == L_NT) {
     MX_CHECK_ARG(g.K % 4 == 0, "gemm NT: K=%d must be a multiple of 4", g.K);
-    if (g.b.mode == MX_PLAIN) dispatch_nt(g, batch, st);        // second-generation NT kernels (profiles/r02_gemm_nt_v2_vs_short.txt)
-    else dispatch<L_NT>(g, batch, st);
+    MX_CHECK_ARG(g.b.mode == MX_PLAIN, "gemm NT: operand B must be plain (mode %d given): the NT kernels apply a prologue to A only", g.b.mode);
+    dispatch_nt(g, batch, st);                                   // second-generation NT kernels (profiles/r02_gemm_nt_v2_vs_short.txt)
   } else if (layout == L_NN) {
     MX_CHECK_ARG(g.K % 4 == 0 && g.N % 4 == 0, "gemm NN: K=%d and N=%d must be multiples of 4", g.K, g.N);
     dispatch<L_NN>(g, batch, st);

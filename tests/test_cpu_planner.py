@@ -53,3 +53,22 @@ def test_the_pipelined_wgrad_kernel_is_gone(restore_settings):
     assert L.mx_get_wgrad_kernel() == 2
     for kern in (0, 2):
         assert L.mx_set_wgrad_kernel(kern, 0) == 0 and L.mx_get_wgrad_kernel() == kern
+
+
+def test_only_the_gemm_kernels_a_planner_can_select_are_compiled():
+    """The built library holds the first-generation gemm_kernel for exactly the (layout, tile) pairs its dispatch can reach,
+    no 128 x 256 split tile, and reads no tile override from the environment.  Read from the host stubs' mangled names."""
+    import re
+    from muscle_amd import _build
+    blob = open(_build.LIB, "rb").read()
+    got = {tuple(int(x) for x in m) for m in
+           re.findall(rb"__device_stub__gemm_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)EE", blob)}
+    NN, TN = 1, 2                                   # (layout 0 is NT: the second-generation kernels)
+    want = {(NN, 2, 2, 2, 2, 16), (NN, 4, 1, 1, 3, 16), (NN, 4, 1, 1, 2, 16), (NN, 4, 1, 1, 1, 16),       # 128x128, 128x96, 128x64, 128x32
+            (TN, 2, 2, 2, 2, 16), (TN, 4, 1, 1, 3, 16), (TN, 4, 1, 1, 1, 16)}                             # 128x128, 128x96, 128x32
+    assert got == want, sorted(got ^ want)
+    assert b"gemm_kernelILi0E" not in blob
+    split = {tuple(int(x) for x in m) for m in re.findall(rb"__device_stub__gemm_nt_split_kernelILi(\d+)ELi(\d+)EE", blob)}
+    assert split and all(nj != 4 for _, nj in split), sorted(split)
+    assert b"MX_GEMM_SPLIT" in blob
+    assert b"MX_GEMM_CFG" not in blob and b"MX_GEMM_SPLIT_NJ" not in blob

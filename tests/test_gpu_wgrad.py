@@ -152,3 +152,68 @@ def test_exact_fp32_wgrad_on_specialised_waves_vs_fp64(R, Co, Ci, pad):
         assert err <= 2e-6 * scale + 4e-7 * float(R) ** 0.5 * 4.0, (err, scale)
     finally:
         ops.set_gemm_mode(prev)
+
+
+def _gen1_tile(layout, M, N):
+    """The first-generation GEMM's tile rule (gemm.hip pick_cfg), restated to derive the shapes below: BN of the 128 x BN tile."""
+    if layout == "TN":
+        return 128 if N >= 384 and N % 128 == 0 else 96 if N % 96 == 0 else 32
+    best, best_score = 32, -1.0
+    for bn, eff in ((128, 1.00), (96, 0.97), (64, 0.95), (32, 0.85)):
+        if bn == 64 and N % 64:
+            continue
+        nt = -(-N // bn)
+        per_cu = -(-M // 128) * nt / 256.0
+        score = eff * (N / (nt * bn)) * (per_cu / int(per_cu + 0.999999)) * (0.85 if per_cu < 2.0 else 1.0)
+        if score > best_score + 1e-9:
+            best, best_score = bn, score
+    return best
+
+
+# One case per (layout, tile) the library compiles, at the smallest shape the rule above sends to that tile.
+# TN (rows M = Co, columns N = Ci): the rule reads Ci alone - 384 (>= 384 and a multiple of 128), 96, 32; Co = 200 gives two
+# row tiles, the second ragged.  R = 301 is one reduction slice, added straight into dW; R = 1101 is three slices of 384 rows
+# (the last ragged) through the partial matrices and their in-order join.
+# NN: searched over M tiles and N in steps of 4 for the smallest M * N per tile; M is then taken 5 rows short of the tile edge.
+# 128 x 128 needs the wide tile's padding and balance to beat four times as many 128 x 32 workgroups, first at 193 row tiles and
+# N = 100; 128 x 96 needs two full workgroups per CU (512 row tiles) at a width only it pads least, N = 68; 128 x 64 first wins
+# at 43 row tiles x N = 192.  The second 128 x 64 shape (65 row tiles x 2 column tiles, 0.8 % larger) is the smallest that
+# takes the XCD-ordered 1-D grid.  128 x 32 takes every small shape: three ragged row tiles x two column tiles, two batches.
+# K = 20 / 36 are multiples of 4 (the NN contract) and not of 16: a ragged last K slab.
+_GEN1_CASES = [("TN", 200, 384, 301, 128), ("TN", 200, 384, 1101, 128), ("TN", 200, 96, 301, 96), ("TN", 200, 96, 1101, 96),
+               ("TN", 200, 32, 301, 32), ("TN", 200, 32, 1101, 32),
+               ("NN", 24699, 100, 20, 128), ("NN", 65531, 68, 20, 96), ("NN", 5499, 192, 36, 64), ("NN", 8315, 128, 20, 64),
+               ("NN", 333, 36, 20, 32)]
+
+
+@pytest.mark.parametrize("layout,M,N,K,bn", _GEN1_CASES)
+def test_first_generation_gemm_tiles_vs_fp64(layout, M, N, K, bn):
+    """gemm_kernel (exact-fp32 MFMA, NN and TN) on each tile its dispatch instantiates, against numpy fp64, held to the
+    bound of the exact-fp32 weight-gradient cases above (the error of an fp32 dot product of the reduction's length)."""
+    from muscle_amd import ops
+    assert _gen1_tile(layout, M, N) == bn
+    g = torch.Generator(device=DEV).manual_seed(M * 3 + N + K)
+    if layout == "TN":
+        G = torch.randn(K, M, device=DEV, generator=g)
+        X = torch.randn(K, N, device=DEV, generator=g)
+        base = torch.randn(M, N, device=DEV, generator=g)          # dW += : the running sum must be kept
+        ref = G.cpu().numpy().astype(np.float64).T @ X.cpu().numpy().astype(np.float64)
+        out = base.clone()
+        ops.WGRAD_SMALL = ops.WGRAD_TILE = False
+        try:
+            ops.pw_wgrad(G, X, out)
+        finally:
+            ops.WGRAD_SMALL = ops.WGRAD_TILE = True
+        got = out.cpu().numpy().astype(np.float64) - base.cpu().numpy().astype(np.float64)
+    else:
+        nb = 2 if bn == 32 else 1
+        A = torch.randn(nb, M, K, device=DEV, generator=g)
+        B = torch.randn(nb, K, N, device=DEV, generator=g)
+        ref = A.cpu().numpy().astype(np.float64) @ B.cpu().numpy().astype(np.float64)
+        out = torch.full((nb, M, N), float("nan"), device=DEV)
+        ops.bgemm(1, A, B, out, M, N, K)
+        got = out.cpu().numpy().astype(np.float64)
+    scale = float(np.abs(ref).max())
+    err = float(np.abs(got - ref).max())               # (a NaN left in `out` fails the comparison below)
+    print(f"{layout} M={M} N={N} K={K} tile 128x{bn}: err {err:.3g} scale {scale:.3g}")
+    assert err <= 2e-6 * scale + 4e-7 * float(K) ** 0.5 * 4.0, (err, scale)

@@ -315,7 +315,7 @@ static void run_chunk(int M, int K, int N) {
   CK(hipFree(planes)); CK(hipFree(table));
 }
 
-// second-generation split kernel: every tile width on one shape (forced through MX_GEMM_SPLIT_NJ's lab values)
+// second-generation split kernel: every tile width on one shape (forced through gemm.hip's g_split_nj hook, values >= 16)
 static void run_widths(int M, int K, int N) {
   float* A = dalloc((long)M * K, 1, 1.f); float* W = dalloc((long)N * K, 2, 0.05f);
   float* C2 = dalloc((long)M * N, 5, 0.f);
