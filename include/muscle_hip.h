@@ -160,6 +160,21 @@ int mx_pw_bwd_small_fused(const float* G, const float* G2, const float* coef, co
                           const float* residual, int R, int Co, int Ci, int ldg, int ldx, int lddx, void* ws, long ws_bytes, void* stream);
 int mx_pw_parts_reduce(const float* part, int groups, int n, float* dW, void* stream);
 
+/* The whole backward of the project convolution (backward of model.py:87 and of the SE / BN1 pair in front of it) where its GEMMs are
+ * HBM-bound - (Cout, Cexp) = (48, 288) and (48, 192) only: the small-output kernel's pass over dp [R, Cout] and d_raw [R, Cexp] leaves
+ * dW[Cout,Cexp] += dp^T X' with X' = swish(scale*d_raw + shift)*gate[sample] (bit for bit mx_pw_wgrad_small with MX_BNACT where both cut
+ * the rows into the same groups: below 131 072 rows), dA[R,Cexp] = dp Wp (Wp the parameter itself, row-major; exact fp32 MFMA in every
+ * GEMM mode) and out5[5][N][Cexp], the sums of mx_se_bn1_pool over (dA, d_raw), formed from dA while it is on chip.  Deterministic: no
+ * atomics.  rows_per_sample must be a MULTIPLE OF 16 (other values are not handled) that divides R, with at most 65 535 samples.  Scratch:
+ * [groups][Cout*Cexp] + [groups + N - 1][5][Cexp] floats, N = R / rows_per_sample; dW = null leaves the partial matrices at its head for
+ * mx_pw_parts_reduce.  _ok: 1 where the engine takes it (an admitted shape, R >= 65536, rows_per_sample as above); _groups: the row
+ * groups, 0 = not taken; the entry point itself runs any R >= 1 and answers MX_EARG for everything else before any launch. */
+int mx_pw_proj_bwd_fused_ok(int R, int Cout, int Cexp, int rows_per_sample);
+int mx_pw_proj_bwd_fused_groups(int R, int Cout, int Cexp, int rows_per_sample);
+int mx_pw_proj_bwd_fused(const float* dp, const float* d_raw, const float* scale, const float* shift, const float* gate, int rows_per_sample,
+                         const float* Wp, float* dW, float* dA, float* out5, int R, int Cout, int Cexp, int lddp, int ldraw, int ldda,
+                         void* ws, long ws_bytes, void* stream);
+
 /* The same weight gradient for LARGE outputs (Co*Ci >= 16384): dW cut into 128/64-wide tiles, the rows into groups, partial
  * tiles per group added in a fixed order - deterministic, no atomics; workgroup ids are XCD-aware so that a row slab crosses
  * the fabric once.  mx_pw_wgrad_tile_ws: bytes of scratch needed for contiguous operands (ldg = Co, ldx = Ci), 0 = shape not taken.

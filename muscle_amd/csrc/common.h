@@ -54,6 +54,10 @@ static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 // dW[e] += sum_g part[g][e] in a fixed order (wgrad.hip); n = elements per partial matrix, a multiple of 4
 void mx_launch_parts_reduce(const float* part, int groups, int n, float* dW, hipStream_t st);
 
+// tiling and row groups of the small-output weight-gradient kernel (wgrad.hip) for dW[Co, Ci] over R rows; false = shape not taken
+struct WgPlan { int nw, wco, wci, tco, tci, groups, rows_per_wg, SG, SX; long lds_bytes; };
+bool mx_wgrad_small_plan(int R, int Co, int Ci, WgPlan* p);
+
 // ---------------------------------------------------------------------------
 // device helpers
 // ---------------------------------------------------------------------------

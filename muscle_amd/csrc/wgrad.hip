@@ -271,8 +271,6 @@ static int wg_pad16(int c) {           // smallest stride >= c (rounded to 16) t
   return (s % 32 == 16) ? s : s + 16;
 }
 
-struct WgPlan { int nw, wco, wci, tco, tci, groups, rows_per_wg, SG, SX; long lds_bytes; };
-
 void mx_launch_parts_reduce(const float* part, int groups, int n, float* dW, hipStream_t st) {
   hipLaunchKernelGGL(wgrad_parts_reduce_kernel, dim3(cdiv(n, 64)), dim3(256), 0, st, part, groups, n, dW);
 }
@@ -308,6 +306,8 @@ static bool wg_plan(int R, int Co, int Ci, WgPlan* p) {
   p->groups = cdiv(R, rows);
   return true;
 }
+
+bool mx_wgrad_small_plan(int R, int Co, int Ci, WgPlan* p) { return wg_plan(R, Co, Ci, p); }      // for wgrad_proj.hip
 
 template <int TCO, int TCI, int NW, int GI, int XI, int XMODE, bool GBN = false>
 static int wg_launch_one(const WgArgs& a, const WgPlan& p, hipStream_t st) {

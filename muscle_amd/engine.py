@@ -15,6 +15,7 @@ e_raw, d_raw, p_raw, out (and `a` where materialised) are what exists in HBM; th
 Per block, backward:
     g_out --BN2 bwd (reduce, finalise, apply)--> dp --pw_wgrad / pw_dgrad--> dA
     (dA, d_raw) --se_bn1_pool (one pass: SE gate gradient + BN1 backward sums per sample)--> se_bwd --> gh --bn1_coeffs--> add, c1..c3
+    (project convs 48 x 288 / 48 x 192 at 65 536 rows or more: (dp, d_raw) --pw_proj_bwd_fused--> dA, dW and those sums in one pass)
     stride 1: dwconv_bwd_fused[BN1 data gradient on the fly; dW, dX, *swish'(bn0), BN0 sums] --> gz
     stride 2: dwconv_bwd_fused_s2[the same fusion over 8 x 32 input-pixel tiles, taps by pixel parity] --> gz
               (DW_S2_FUSED off, or a plain depthwise input: bn_bwd_apply --> dwconv_bwd_weight, dwconv_bwd_data --> ge --BN0 bwd reduce)
@@ -394,6 +395,12 @@ DW_S2_FUSED = os.environ.get("MUSCLE_DW_S2_FUSED", "1") == "1"
 # pass, the data-gradient GEMM and the lane's weight-gradient entry are gone for those blocks.  MUSCLE_PW_BWD_FUSED=0 (or flipping
 # `engine.PW_BWD_FUSED` at run time) restores the schedule above.
 PW_BWD_FUSED = os.environ.get("MUSCLE_PW_BWD_FUSED", "1") == "1"
+# Project convs whose data AND weight gradients are HBM-bound (48 x 288 and 48 x 192 of stage 2, read through the BN1 + SiLU + gate
+# prologue): where ops.pw_proj_bwd_fused_takes says so, one kernel (ops.pw_proj_bwd_fused) reads (dp, d_raw) once and leaves dA, the
+# weight gradient's partial matrices and the five sums of se_bn1_pool; the data-gradient GEMM, the lane's weight-gradient entry and the
+# se_bn1_pool pass are gone for those blocks.  MUSCLE_PW_PROJ_BWD_FUSED=0 (or flipping `engine.PW_PROJ_BWD_FUSED` at run time)
+# restores the schedule above.
+PW_PROJ_BWD_FUSED = os.environ.get("MUSCLE_PW_PROJ_BWD_FUSED", "1") == "1"
 # Weight-gradient GEMMs on a second HIP stream (MUSCLE_WGRAD_STREAM=0 turns it off; `engine.WGRAD_SIDE_STREAM` can be
 # flipped at run time).  Nothing in the backward chain consumes them (only the optimizer and the gradient exchange do),
 # they are MFMA-bound, and the chain between two of them (BN backward, SE, depthwise) is HBM-bound.  Measured on
@@ -475,12 +482,23 @@ def _dw_input(t: BlockTape):
 
 
 def _project_backward(lane, tape: Tape, t: BlockTape, m, g_out, sink: GradSink):
-    """g_out --BN2 bwd--> dp --pw_wgrad / pw_dgrad--> dA = dL/d(act*gate) [Mo, Cexp]."""
+    """g_out --BN2 bwd--> dp --pw_wgrad / pw_dgrad--> dA = dL/d(act*gate) [Mo, Cexp].  Returns (dA, the five SE / BN1 sums where the
+    fused kernel has formed them, else None)."""
     b, hw = t.cfg, t.Ho * t.Wo
     Mo = tape.N * hw
     # BN2 backward (upstream gradient carries the drop_connect scale of the sample)
     dp = ops.bn_backward(g_out.reshape(Mo, b.cout), t.p_raw, m._bn2, t.bn2, sink.of(m._bn2.weight), sink.of(m._bn2.bias), tape.training,
                          row_scale=t.row_scale, rows_per_sample=hw)
+    if t.a is None and PW_PROJ_BWD_FUSED:
+        # (asked outside the call log of a stand-in for `ops`: one that does not know the kernel answers no)
+        takes = getattr(ops, "pw_proj_bwd_fused_takes", None)
+        if takes is not None and takes(Mo, b.cout, b.cexp, hw):
+            # one kernel on the main stream reads (dp, d_raw) once and leaves dA, the partial matrices of dW and the sums of
+            # se_bn1_pool; only the addition of the partial matrices goes to the lane
+            ga, pooled5 = ops.pw_proj_bwd_fused(dp, t.d_raw.view(Mo, b.cexp), t.bn1, t.gate, hw, m._project_conv.weight.view(b.cout, b.cexp),
+                                                sink.of(m._project_conv.weight).view(b.cout, b.cexp), defer=lane.pw_reduce)
+            lane.flush()
+            return ga, pooled5
     # project conv: weight gradient against the recomputed activated+gated input, then data gradient
     if t.a is not None:
         lane.wgrad(dp, t.a, sink.of(m._project_conv.weight).view(b.cout, b.cexp))
@@ -491,16 +509,18 @@ def _project_backward(lane, tape: Tape, t: BlockTape, m, g_out, sink: GradSink):
     ga = ops.pw_dgrad(dp, m._project_conv.weight.view(b.cout, b.cexp), b.cexp, wt=tape.wt.get(id(m._project_conv.weight)),
                       planes=tape.wtp.get(id(m._project_conv.weight)))
     lane.flush()
-    return ga
+    return ga, None
 
 
-def _se_bn1_coeffs(tape: Tape, t: BlockTape, m, ga, sink: GradSink):
+def _se_bn1_coeffs(tape: Tape, t: BlockTape, m, ga, pooled5, sink: GradSink):
     """(dA, d_raw) --se_bn1_pool--> se_bwd --> gh --bn1_coeffs--> (c1..c3 of the BN1 data gradient, pooled-path gradient `add`).
-    One pass over (ga, d_raw) yields the SE gate gradient sum_hw ga*act AND the per-sample pieces of the BN1 backward sums; the
-    excitation backward then gives `add`, and the BN1 sums follow without touching the big tensors again."""
+    One pass over (ga, d_raw) yields the SE gate gradient sum_hw ga*act AND the per-sample pieces of the BN1 backward sums (pooled5:
+    already there where the fused project-conv backward formed them); the excitation backward then gives `add`, and the BN1 sums
+    follow without touching the big tensors again."""
     b, hw = t.cfg, t.Ho * t.Wo
     Mo = tape.N * hw
-    pooled5 = ops.se_bn1_pool(ga, t.d_raw.view(Mo, b.cexp), t.bn1, hw)
+    if pooled5 is None:
+        pooled5 = ops.se_bn1_pool(ga, t.d_raw.view(Mo, b.cexp), t.bn1, hw)
     gh = ops.se_bwd(pooled5[0], t.gate, t.s, t.h, m._se_expand.weight.view(b.cexp, b.se),
                     sink.of(m._se_reduce.weight).view(b.se, b.cexp), sink.of(m._se_reduce.bias),
                     sink.of(m._se_expand.weight).view(b.cexp, b.se), sink.of(m._se_expand.bias))
@@ -594,8 +614,8 @@ def backbone_backward(backbone, cfg: NetCfg, tape: Tape, tap_grads: Dict[int, to
             g_out = tg if g_out is None else g_out + tg
         if g_out is None:
             continue                                   # blocks after the last tap get no gradient
-        ga = _project_backward(lane, tape, t, m, g_out, sink)
-        c1, add = _se_bn1_coeffs(tape, t, m, ga, sink)
+        ga, pooled5 = _project_backward(lane, tape, t, m, g_out, sink)
+        c1, add = _se_bn1_coeffs(tape, t, m, ga, pooled5, sink)
         skip_res = g_out if t.cfg.skip else None        # d out / d x through the identity branch
         gx, part0 = _depthwise_backward(lane, tape, t, m, ga, c1, add, skip_res, sink)
         del ga

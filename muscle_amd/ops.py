@@ -320,7 +320,7 @@ def _rows_ptr(t, what):
     if t is None:
         return None
     if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1:
-        raise ValueError(f"pw_bwd_fused: {what} must be a 2-D fp32 CUDA tensor with unit column stride")
+        raise ValueError(f"{what} must be a 2-D fp32 CUDA tensor with unit column stride")
     return t.data_ptr()
 
 
@@ -357,6 +357,42 @@ def pw_bwd_fused(G, G2, coef, X, W, dW, *, residual=None, defer=None, out=None):
     if part is not None:
         defer(part, dW)
     return dX
+
+
+def pw_proj_bwd_fused_takes(R, Cout, Cexp, rows_per_sample) -> bool:
+    """True where the engine should take pw_proj_bwd_fused for a project conv [Cout, Cexp] over R rows (mx_pw_proj_bwd_fused_ok)."""
+    return bool(lib().mx_pw_proj_bwd_fused_ok(R, Cout, Cexp, rows_per_sample))
+
+
+def pw_proj_bwd_fused(dp, d_raw2d, st1: "BNState", gate, rows_per_sample, Wp, dW, *, defer=None, out=None):
+    """The whole backward of a small project conv (48 x 288 and 48 x 192) and of the SE / BN1 pair in front of it, in one pass over
+    dp [R, Cout] and d_raw [R, Cexp]: dW[Cout, Cexp] += dp^T (swish(bn1(d_raw)) * gate), dA[R, Cexp] = dp Wp and pooled5 [5, N, Cexp],
+    the sums se_bn1_pool forms from (dA, d_raw).  Returns (dA, pooled5).  rows_per_sample must be a multiple of 16 that divides R.
+    Operands may be row views; `out`, if given, is dA's buffer.
+    defer: a callable taking (part, dW) - the addition of the weight gradient's partial matrices is handed to it (e.g. queued for
+    the side stream, ops.pw_parts_reduce) instead of being launched behind the kernel."""
+    R, Cout = dp.shape
+    Cexp = d_raw2d.shape[1]
+    groups = lib().mx_pw_proj_bwd_fused_groups(R, Cout, Cexp, rows_per_sample)
+    if groups <= 0:
+        raise ValueError(f"pw_proj_bwd_fused: R={R} Cout={Cout} Cexp={Cexp} rows_per_sample={rows_per_sample} not taken")
+    N = R // rows_per_sample
+    dA = out if out is not None else _f32(R, Cexp, device=dp.device)
+    pooled5 = _f32(5, N, Cexp, device=dp.device)
+    # scratch: the partial matrices [groups, Cout*Cexp], then the partial sums [groups + N - 1, 5, Cexp]; its own buffer when the
+    # reduce runs later, beside the next launches
+    n_part, n_pool = groups * Cout * Cexp, (groups + N - 1) * 5 * Cexp
+    if defer is not None:
+        ws = _f32(n_part + n_pool, device=dp.device)
+        wsp, wsn, dwp = ws.data_ptr(), ws.numel() * 4, None
+    else:
+        ws = _wgrad_workspace(dp.device, (n_part + n_pool) * 4)
+        wsp, wsn, dwp = ws.data_ptr(), ws.numel(), ptr(dW)
+    call("mx_pw_proj_bwd_fused", _rows_ptr(dp, "dp"), _rows_ptr(d_raw2d, "d_raw"), ptr(st1.scale), ptr(st1.shift), ptr(gate), rows_per_sample,
+         ptr(Wp), dwp, _rows_ptr(dA, "dA"), ptr(pooled5), R, Cout, Cexp, dp.stride(0), d_raw2d.stride(0), dA.stride(0), wsp, wsn, stream())
+    if defer is not None:
+        defer(ws[:n_part].view(groups, Cout * Cexp), dW)
+    return dA, pooled5
 
 
 def wgrad_bnbwd_dz_takes(R, Co, Ci) -> bool:
