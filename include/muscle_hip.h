@@ -431,6 +431,21 @@ int mx_resample(const unsigned char* src, const int* jobs, const int* tabs, unsi
  * mx_input_stage. */
 int mx_mask_stage(const void* src, const int* jobs, const int* tabs, float* dst, int n, int C, int S, int span_cap, void* stream);
 
+/* mx_label_stage: the same item when its label is a hard label map (mask_type="label": one class index per pixel, 255 =
+ * ignore; ours, the reference's unused 'hard' branch pads with class 0 and has no ignore index).  dst[n,S,S] (uint8, fully
+ * written) = the label of item n after a NEAREST resize (what PIL.Image.resize(.., NEAREST) returns), the crop window
+ * pasted into a container filled with `fill` (255: padding is ignored by mx_ce_label, not trained as background) and
+ * np.fliplr of the container:
+ *   window top <= y < top+ch, left <= x < left+cw of the container:  c[y, x] = src[ys[y-top]][xs[x-left]];  fill elsewhere;
+ *   dst[n, y, x] = flip ? c[y, S-1-x] : c[y, x].
+ * src: the shipped uint8 source rows [sh,sw] of every item at BYTE offsets of any alignment (sw is usually odd: the kernel
+ * loads single bytes and assumes no alignment); jobs: n x 16 int32 {byte offset into src, sh, sw, top, left, ch, cw, flip,
+ * ty_off, tx_off (int32 words into tabs), 0 x 6}; tabs at ty_off: ys[ch], at tx_off: xs[cw], the int32 source row / column of
+ * every window row / column relative to the shipped rows (muscle_amd/segdata.py:nearest_axis_table), clamped to the shipped
+ * rows by the kernel.  0 <= fill <= 255.  One launch per batch, every output byte has one writer, no atomics. */
+int mx_label_stage(const unsigned char* src, const int* jobs, const int* tabs, unsigned char* dst, int n, int S, int fill,
+                   void* stream);
+
 /* ---- input stage of IRN training (VOC12AffinityDataset.__getitem__, src/data.py:659-705) ---------------------------------
  * mx_irn_input_stage: one launch writes both outputs of a batch of n items, S = crop size (S % 16 == 0):
  *   img[n,3,S,S] (fp32, fully written) = TorchvisionNormalize (src/data.py:596-609: fp64 (u8 / 255 - mean) / std, one
@@ -635,6 +650,17 @@ int mx_resize_nhwc_bwd(const float* gdst, float* gsrc, int N, int Hs, int Ws, in
 /* CrossEntropyLoss(seg [N,K,HW], argmax_k mask) (train_muscle.py:189-191): loss[0] += mean; bwd: gseg = gup[0]*dL/dseg */
 int mx_ce_argmax(const float* seg, const float* mask, const float* gup, float* loss, float* gseg, int N, int K, long HW, int bwd,
                  void* ws /* forward: 8 bytes, the fixed-point sum */, long ws_bytes, void* stream);
+/* F.cross_entropy(seg [N,K,HW], label [N,HW] uint8, ignore_index=ignore) against a hard label map (mask_type="label").  A pixel
+ * is VALID when label != ignore and label < K; every other value (ignore itself, and any value >= K, which only the raw ABI
+ * can deliver) is ignored and never used as an index.  count = number of valid pixels (an integer).
+ *   forward (bwd == 0): loss[0] += sum over valid pixels of (log sum exp(seg) - seg[label]) / count; count == 0: loss[0] is
+ *     left unchanged (torch gives NaN there).  The sum is kept in 64-bit fixed point as mx_ce_argmax keeps it.
+ *   backward (bwd != 0): gseg = gup[0] * (softmax(seg) - onehot(label)) / count at valid pixels and exactly 0 at ignored
+ *     ones (all zeros when count == 0), over whatever gseg held; the call counts the valid pixels itself.
+ * ws: 16 bytes, 8-byte aligned, in both directions {uint64 fixed-point sum, uint64 count}; contents on entry do not matter.
+ * Integer atomics only: the same bits every run. */
+int mx_ce_label(const float* seg, const unsigned char* label, int ignore, const float* gup, float* loss, float* gseg, int N, int K,
+                long HW, int bwd, void* ws, long ws_bytes, void* stream);
 /* clip_grad_norm_(max_norm, 2) on a flat gradient arena (train_muscle.py:202); norm_out (optional) = total norm;
  * sq_scratch: 2048 doubles (per-workgroup partial square sums, added in a fixed order) */
 int mx_clip_grad_norm(float* grads, long n, float max_norm, double* sq_scratch, float* norm_out, void* stream);
@@ -646,9 +672,16 @@ int mx_field_edges(const float* seg, const float* lab_fg, float beta, float* pro
 int mx_field_select(const float* mag, const unsigned char* orient, const unsigned* mx, const int* slots, int nslots, int step,
                     int* out_list, int* in_list, int* counts, int F, int H, int W, void* stream);
 /* stage 3: channel-softmaxed dense features (mode 0 full-res NCHW, mode 1 low-res NHWC upsampled on the fly) and
- * class-softmaxed mask at the sampled points pts {n, pixel} */
+ * class-softmaxed mask at the sampled points pts {n, pixel}.  mask == NULL: the mask rows are not written (mfeat may be
+ * NULL too); mx_field_mask_label writes them from a label map instead */
 int mx_field_gather(const float* dense, int mode, int h, int w, const float* mask, const int* pts, int npts, float* feat, float* mfeat,
                     int CH, int K, int ML, int H, int W, void* stream);
+/* stage 3 for a hard label map label [N,H,W] uint8 (mask_type="label"): the mask rows mfeat [npts, ML] at pts {n, pixel}.
+ * label t < K (and != ignore): softmax over the K classes of onehot(t), i.e. 1 / (1 + (K-1)/e) in column t and
+ * (1/e) / (1 + (K-1)/e) in the other K-1; an ignored point (ignore, or any value >= K): uniform 1/K, what the soft path's
+ * zero padding gives; columns K..ML-1 are 0.  The three values are rounded once from double.  No [N,K,H,W] tensor exists. */
+int mx_field_mask_label(const unsigned char* label, const int* pts, int npts, float* mfeat, int K, int ML, int H, int W, int ignore,
+                        void* stream);
 /* stage 5 (edge.py:231-261,330-347): loss += terms/nsamples, gsim = d loss / d sim, per slot of k x k similarities */
 int mx_field_terms(const float* sim, const float* simm, int nslots, int k, float inv_n, float* loss, float* gsim,
                    float* slot_loss /* nslots floats of scratch */, void* stream);

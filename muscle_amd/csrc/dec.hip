@@ -145,6 +145,83 @@ __global__ __launch_bounds__(256) void ce_argmax_kernel(const float* seg, const 
 }
 
 // ---------------------------------------------------------------------------
+// F.cross_entropy(seg [N,K,HW], label [N,HW] uint8, ignore_index) against a hard label map, and its gradient
+// ---------------------------------------------------------------------------
+// A pixel is valid when label != ignore && label < K.  acc = {fixed-point sum of the valid pixels' terms, their count}: both integers,
+// added with integer atomics (associative: same bits every run).  Consecutive lanes read consecutive label bytes and, per class,
+// consecutive floats of seg; an ignored pixel reads nothing of seg.
+__device__ __forceinline__ bool ce_label_valid(int t, int ignore, int K) { return t != ignore && t < K; }
+
+__global__ __launch_bounds__(256) void ce_label_count_kernel(const unsigned char* label, int ignore, int K, long total, unsigned long long* acc) {
+  unsigned cnt = 0;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) cnt += ce_label_valid(label[i], ignore, K) ? 1u : 0u;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+  if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(acc + 1, (unsigned long long)cnt);
+}
+__global__ void ce_label_finish_kernel(const unsigned long long* acc, float* loss) {
+  if (acc[1]) loss[0] += (float)((double)acc[0] / (double)CE_FIX / (double)acc[1]);
+}
+__global__ __launch_bounds__(256) void ce_label_kernel(const float* seg, const unsigned char* label, int ignore, const float* gup,
+                                                       unsigned long long* acc, float* gseg, int N, int K, long HW, int bwd) {
+  const long total = (long)N * HW;
+  float sum = 0.f, g = 0.f;
+  unsigned cnt = 0;
+  if (bwd) {                                                // the count is complete: ce_label_count_kernel ran before this launch
+    const unsigned long long c = acc[1];
+    g = c ? gup[0] * (1.f / (float)c) : 0.f;
+  }
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const long n = i / HW, p = i - n * HW;
+    const int t = label[i];
+    const bool valid = ce_label_valid(t, ignore, K);
+    const float* s = seg + n * K * HW + p;
+    if (!valid) {
+      if (bwd) {
+        float* o = gseg + n * K * HW + p;
+        for (int k = 0; k < K; ++k) o[k * HW] = 0.f;
+      }
+      continue;
+    }
+    float mx = s[0];
+    for (int k = 1; k < K; ++k) mx = fmaxf(mx, s[k * HW]);
+    float se = 0.f;
+    for (int k = 0; k < K; ++k) se += __expf(s[k * HW] - mx);
+    const float lse = mx + __logf(se);
+    if (!bwd) { sum += lse - s[t * HW]; ++cnt; }
+    else {
+      float* o = gseg + n * K * HW + p;
+      for (int k = 0; k < K; ++k) o[k * HW] = g * (__expf(s[k * HW] - lse) - (k == t ? 1.f : 0.f));
+    }
+  }
+  if (!bwd) {
+    sum = wave_sum(sum);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    if ((threadIdx.x & 63) == 0) {
+      if (sum > 0.f) atomicAdd(acc, (unsigned long long)(sum * CE_FIX));
+      if (cnt) atomicAdd(acc + 1, (unsigned long long)cnt);
+    }
+  }
+}
+
+// FieldLoss stage 3 for a hard label map: the mask rows of the sampled points.  One thread per (point, column); the three values a
+// row can hold are computed by the host in double and rounded once.
+__global__ __launch_bounds__(256) void field_mask_label_kernel(const unsigned char* label, const int* pts, int npts, float* mfeat, int K,
+                                                               int ML, long HW, int ignore, float p_hit, float p_miss, float p_uniform) {
+  const long i = blockIdx.x * 256L + threadIdx.x;
+  if (i >= (long)npts * ML) return;
+  const int q = (int)(i / ML), c = (int)(i - (long)q * ML);
+  const int n = pts[2 * q], p = pts[2 * q + 1];
+  float v = 0.f;
+  if (c < K) {
+    const int t = (p >= 0 && p < HW) ? (int)label[(long)n * HW + p] : ignore;
+    v = ce_label_valid(t, ignore, K) ? (c == t ? p_hit : p_miss) : p_uniform;
+  }
+  mfeat[i] = v;
+}
+
+// ---------------------------------------------------------------------------
 // clip_grad_norm_: sq[0] += sum x^2 (fp64); then x *= min(1, max_norm / (sqrt(sq) + 1e-6))
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void sqsum_kernel(const float* x, long n, double* sq /*[gridDim.x]*/) {
@@ -364,6 +441,7 @@ __global__ __launch_bounds__(256) void field_gather_kernel(const float* dense, i
     se = wave_sum(se); cnt = 0;
     for (int c = lane; c < CH; c += 64, ++cnt) feat[(long)q * CH + c] = v[cnt] / se;
     // mask softmax over K classes (lanes < K), padded to ML columns with zeros
+    if (!mask) continue;                           // (uniform) a label map's rows come from field_mask_label_kernel
     float mv = (lane < K) ? mask[((long)n * K + lane) * HW + p] : -INFINITY;
     float mm = wave_max(mv);
     float me = (lane < K) ? expf(mv - mm) : 0.f;
@@ -542,6 +620,21 @@ int mx_ce_argmax(const float* seg, const float* mask, const float* gup, float* l
   return MX_OK;
 }
 
+int mx_ce_label(const float* seg, const unsigned char* label, int ignore, const float* gup, float* loss, float* gseg, int N, int K,
+                long HW, int bwd, void* ws, long ws_bytes, void* stream) {
+  MX_CHECK_ARG(seg && label && N > 0 && K > 1 && K <= 256 && HW > 0 && (bwd ? (gup && gseg) : (loss != nullptr)), "ce_label: bad args");
+  MX_CHECK_ARG(ws && ws_bytes >= 16 && ((uintptr_t)ws & 7) == 0, "ce_label: needs 16 bytes of 8-byte aligned scratch (sum, count)");
+  hipStream_t st = (hipStream_t)stream;
+  unsigned long long* acc = (unsigned long long*)ws;
+  const long total = (long)N * HW;
+  hipMemsetAsync(ws, 0, 16, st);
+  if (bwd) hipLaunchKernelGGL(ce_label_count_kernel, dim3(gs(total)), dim3(256), 0, st, label, ignore, K, total, acc);
+  hipLaunchKernelGGL(ce_label_kernel, dim3(gs(total)), dim3(256), 0, st, seg, label, ignore, gup, acc, gseg, N, K, HW, bwd);
+  if (!bwd) hipLaunchKernelGGL(ce_label_finish_kernel, dim3(1), dim3(1), 0, st, (const unsigned long long*)acc, loss);
+  MX_LAUNCH_CHECK();
+  return MX_OK;
+}
+
 // sq_scratch: 2048 doubles (one partial square sum per workgroup, added in a fixed order)
 int mx_clip_grad_norm(float* grads, long n, float max_norm, double* sq_scratch, float* norm_out, void* stream) {
   MX_CHECK_ARG(grads && sq_scratch && n > 0 && max_norm > 0, "clip_grad_norm: bad args");
@@ -576,10 +669,20 @@ int mx_field_select(const float* mag, const unsigned char* orient, const unsigne
 
 int mx_field_gather(const float* dense, int mode, int h, int w, const float* mask, const int* pts, int npts, float* feat, float* mfeat,
                     int CH, int K, int ML, int H, int W, void* stream) {
-  MX_CHECK_ARG(dense && mask && pts && feat && mfeat && npts > 0 && CH > 0 && CH <= 1024 && K <= 64 && ML >= K && ML <= 64,
+  MX_CHECK_ARG(dense && pts && feat && (mfeat || !mask) && npts > 0 && CH > 0 && CH <= 1024 && K <= 64 && ML >= K && ML <= 64,
                "field_gather: bad args");
   hipLaunchKernelGGL(field_gather_kernel, dim3(cdiv(npts, 4)), dim3(256), 0, (hipStream_t)stream, dense, mode, h, w, mask, pts, npts,
                      feat, mfeat, CH, K, ML, H, W);
+  MX_LAUNCH_CHECK();
+  return MX_OK;
+}
+
+int mx_field_mask_label(const unsigned char* label, const int* pts, int npts, float* mfeat, int K, int ML, int H, int W, int ignore,
+                        void* stream) {
+  MX_CHECK_ARG(label && pts && mfeat && npts > 0 && K > 1 && K <= 64 && ML >= K && ML <= 64 && H > 0 && W > 0, "field_mask_label: bad args");
+  const double miss = exp(-1.0), den = 1.0 + (double)(K - 1) * miss;       // softmax(onehot): exp(1 - 1) = 1 on the label, exp(0 - 1) elsewhere
+  hipLaunchKernelGGL(field_mask_label_kernel, dim3(cdiv((long)npts * ML, 256)), dim3(256), 0, (hipStream_t)stream, label, pts, npts, mfeat, K,
+                     ML, (long)H * W, ignore, (float)(1.0 / den), (float)(miss / den), (float)(1.0 / (double)K));
   MX_LAUNCH_CHECK();
   return MX_OK;
 }

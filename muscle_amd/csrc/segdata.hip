@@ -79,7 +79,50 @@ __global__ __launch_bounds__(256) void mask_stage_kernel(const unsigned char* __
   }
 }
 
+// The same stage for a hard label map (mask_type="label"): a NEAREST resize is a gather, so the whole stage is
+//   dst[n, y, x] = inside the window ? src[ys[y - top]][xs[xc - left]] : fill,   xc = flip ? S-1-x : x (fliplr of the container).
+// A thread owns four neighbouring output bytes of one row: it gathers them with byte loads (the shipped rows start at any byte
+// offset and sw is usually odd) and writes them as ONE 32-bit store where the four lie inside the row and the address is
+// aligned, as single bytes otherwise (a row tail, S % 4 != 0).  64 lanes cover 256 consecutive output bytes and read runs of
+// neighbouring source bytes of one source row.  Every output byte has exactly one writer.
+struct LabelJob { int src_off, sh, sw, top, left, ch, cw, flip, ty_off, tx_off, pad[6]; };
+
+__global__ __launch_bounds__(256) void label_stage_kernel(const unsigned char* __restrict__ src, const LabelJob* __restrict__ jobs,
+                                                          const int* __restrict__ tabs, unsigned char* __restrict__ dst, int S, int fill) {
+  const LabelJob jb = jobs[blockIdx.z];
+  const int y = blockIdx.y * 4 + (threadIdx.x >> 6), x0 = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4;      // a wave per output row
+  if (y >= S || x0 >= S) return;
+  const int ty = y - jb.top;
+  const bool row_in = ty >= 0 && ty < jb.ch && jb.sh > 0 && jb.sw > 0;
+  const unsigned char* row = nullptr;
+  if (row_in) row = src + jb.src_off + (long)min(max(tabs[jb.ty_off + ty], 0), jb.sh - 1) * jb.sw;
+  const int* xs = tabs + jb.tx_off;
+  unsigned v[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int x = x0 + j;
+    const int tx = (jb.flip ? S - 1 - x : x) - jb.left;
+    v[j] = (unsigned)fill;
+    if (row_in && x < S && tx >= 0 && tx < jb.cw) v[j] = row[min(max(xs[tx], 0), jb.sw - 1)];
+  }
+  unsigned char* o = dst + ((long)blockIdx.z * S + y) * S + x0;
+  if (x0 + 4 <= S && ((uintptr_t)o & 3) == 0) {
+    *reinterpret_cast<unsigned*>(o) = v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24);
+  } else {
+    for (int j = 0; j < 4 && x0 + j < S; ++j) o[j] = (unsigned char)v[j];
+  }
+}
+
 extern "C" {
+
+int mx_label_stage(const unsigned char* src, const int* jobs, const int* tabs, unsigned char* dst, int n, int S, int fill, void* stream) {
+  MX_CHECK_ARG(src && jobs && tabs && dst, "label_stage: null pointer");
+  MX_CHECK_ARG(n > 0 && n <= 65535 && S > 0 && S <= 65535 && fill >= 0 && fill <= 255, "label_stage: bad extents n=%d S=%d fill=%d", n, S, fill);
+  hipLaunchKernelGGL(label_stage_kernel, dim3(cdiv(S, 256), cdiv(S, 4), n), dim3(256), 0, (hipStream_t)stream, src, (const LabelJob*)jobs, tabs,
+                     dst, S, fill);
+  MX_LAUNCH_CHECK();
+  return MX_OK;
+}
 
 int mx_mask_stage(const void* src, const int* jobs, const int* tabs, float* dst, int n, int C, int S, int span_cap, void* stream) {
   MX_CHECK_ARG(src && jobs && tabs && dst, "mask_stage: null pointer");

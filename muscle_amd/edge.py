@@ -20,6 +20,7 @@ from . import ops
 from ._lib import call, ptr, stream
 
 _ML = 24
+IGNORE_LABEL = 255          # the ignore value of a hard label map (mask_type="label")
 
 
 class _FieldLossFn(torch.autograd.Function):
@@ -32,9 +33,13 @@ class _FieldLossFn(torch.autograd.Function):
         npts = S * k
         feat = torch.empty(2, npts, CH, dtype=torch.float32, device=dev)          # [out | in]
         mfeat = torch.empty(2, npts, _ML, dtype=torch.float32, device=dev)
+        lmap = plan.get("label")                                                  # a hard label map [N,H,W] uint8, or None
         for side in (0, 1):
             call("mx_field_gather", ptr(dense), mode, h, w, ptr(plan["mask"]), ptr(plan["pts"][side]), npts, ptr(feat[side]),
-                 ptr(mfeat[side]), CH, K, _ML, H, W, stream())
+                 ptr(mfeat[side]) if lmap is None else None, CH, K, _ML, H, W, stream())
+            if lmap is not None:
+                call("mx_field_mask_label", ptr(lmap), ptr(plan["pts"][side]), npts, ptr(mfeat[side]), K, _ML, H, W, IGNORE_LABEL,
+                     stream())
         sim = torch.empty(S, k, k, dtype=torch.float32, device=dev)
         simm = torch.empty(S, k, k, dtype=torch.float32, device=dev)
         ops.bgemm(0, feat[0].view(S, k, CH), feat[1].view(S, k, CH), sim, k, k, CH)
@@ -82,9 +87,18 @@ class FieldLoss(nn.Module):
         """Returns (loss, edge magnitude [N,H,W]); loss is a tensor, the int 0 when no class has more than k points on
         both sides, or False when fewer than 10 boundary pixels exist (edge.py:376-383).
         dense_ft: [N,CH,H,W] as MuSCLe.forward(cam='seg') returns it, or — dense_is_lowres_nhwc — the decoder's
-        1/8-resolution NHWC map, upsampled on the fly at the sampled points only."""
+        1/8-resolution NHWC map, upsampled on the fly at the sampled points only.
+        mask: the soft label [N,K,H,W], or a hard label map [N,H,W] uint8 (mask_type="label"): then the mask row of a sampled
+        point is softmax(onehot(label)) - uniform 1/K at an ignored (255) point, what the soft path's zero padding gives - written
+        by mx_field_mask_label; no float tensor of the label is made."""
         seg = seg_map.detach().contiguous().float()
         N, K, H, W = seg.shape
+        if mask.dtype == torch.uint8:
+            if tuple(mask.shape) != (N, H, W):
+                raise ValueError(f"a label map must be [N,H,W] = {(N, H, W)} uint8 (got {tuple(mask.shape)})")
+            mask_kw = dict(mask=None, label=mask.detach().contiguous())
+        else:
+            mask_kw = dict(mask=mask.detach().contiguous().float())
         dev = seg.device
         F_ = K - 1
         lab = label_with_bg[:, 1:].contiguous().float()
@@ -111,7 +125,7 @@ class FieldLoss(nn.Module):
                 mode, h, w, CH = 1, dense.shape[1], dense.shape[2], dense.shape[3]
             else:
                 mode, h, w, CH = 0, 0, 0, dense.shape[1]
-            plan = dict(S=S, k=k, CH=CH, seg_shape=(N, K, H, W), mode=mode, h=h, w=w, pts=pts, mask=mask.detach().contiguous().float())
+            plan = dict(S=S, k=k, CH=CH, seg_shape=(N, K, H, W), mode=mode, h=h, w=w, pts=pts, **mask_kw)
             return _FieldLossFn.apply(dense, plan), edge_fg
         lab_h = lab.cpu()
         slots = [(b, c) for b in range(N) for c in range(F_) if lab_h[b, c] != 0]
@@ -150,7 +164,7 @@ class FieldLoss(nn.Module):
             mode, h, w, CH = 1, dense.shape[1], dense.shape[2], dense.shape[3]
         else:
             mode, h, w, CH = 0, 0, 0, dense.shape[1]
-        plan = dict(S=S, k=k, CH=CH, seg_shape=(N, K, H, W), mode=mode, h=h, w=w, pts=pts, mask=mask.detach().contiguous().float())
+        plan = dict(S=S, k=k, CH=CH, seg_shape=(N, K, H, W), mode=mode, h=h, w=w, pts=pts, **mask_kw)
         return _FieldLossFn.apply(dense, plan), edge_fg
 
 
@@ -177,6 +191,37 @@ class _CEArgmax(torch.autograd.Function):
 def cross_entropy_argmax(seg_map, soft_mask):
     """nn.CrossEntropyLoss()(seg_map, torch.argmax(soft_mask, dim=1)) (train_muscle.py:189-191) in one kernel."""
     return _CEArgmax.apply(seg_map, soft_mask)
+
+
+class _CELabel(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, seg, label):
+        seg, label = seg.contiguous().float(), label.contiguous()
+        N, K, H, W = seg.shape
+        if label.dtype != torch.uint8 or tuple(label.shape) != (N, H, W):
+            raise ValueError(f"a label map must be [N,H,W] = {(N, H, W)} uint8 (got {label.dtype} {tuple(label.shape)})")
+        loss = torch.zeros(1, dtype=torch.float32, device=seg.device)
+        ws = torch.empty(2, dtype=torch.int64, device=seg.device)
+        call("mx_ce_label", ptr(seg), ptr(label), IGNORE_LABEL, None, ptr(loss), None, N, K, H * W, 0, ws.data_ptr(), 16, stream())
+        ctx.save_for_backward(seg, label)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        seg, label = ctx.saved_tensors
+        N, K, H, W = seg.shape
+        out = torch.empty_like(seg)
+        ws = torch.empty(2, dtype=torch.int64, device=seg.device)
+        call("mx_ce_label", ptr(seg), ptr(label), IGNORE_LABEL, ptr(g.contiguous().float().reshape(1)), None, ptr(out), N, K, H * W, 1,
+             ws.data_ptr(), 16, stream())
+        return out, None
+
+
+def cross_entropy_label(seg_map, label):
+    """F.cross_entropy(seg_map, label.long(), ignore_index=255) for a hard label map [N,H,W] uint8, in one kernel: the mean
+    of log sum exp - seg[label] over the pixels whose label is not 255.  Where torch returns NaN - no valid pixel at all -
+    the loss is 0 and the gradient all zeros, so a batch of pure padding leaves the weights alone."""
+    return _CELabel.apply(seg_map, label)
 
 
 def clip_grad_norm_(model, max_norm: float):

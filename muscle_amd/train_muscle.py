@@ -6,6 +6,9 @@ Differences a caller can see:
     flips image and label; --mask_root holds what `python -m muscle_amd.infer_irn --soft_output 1` writes (<name>.npy) or
     its compact form (--soft_output 2, <name>.npz), chosen by --mask_format (new; auto: the .npy where it exists, else the
     .npz); the compact form is expanded on the device to the same float16 rows, bit for bit;
+  * --mask_type label (new; default soft): --mask_root holds label maps <name>.png instead - what `infer_irn --soft_output 0`
+    and `infer_seg --out_seg` write, or SegmentationClass[Aug] itself; 255 is ignored by the loss, the resize is NEAREST and
+    the crop padding is 255 (muscle_amd/segdata.py);
   * --val_list (new, default data/val.txt: the list the reference hard-codes) names the images of the per-epoch validation;
   * --crf 1 runs the dense CRF of the validation on the GPU with t=1 (the exact windowed CRF of muscle_amd/crf.py, not
     pydensecrf's lattice filter);
@@ -42,6 +45,9 @@ def parse_args(argv: Optional[List[str]] = None):
     ap.add_argument("--mask_format", default="auto", choices=("auto", "dense", "compact"),
                     help="dense: <name>.npy; compact: <name>.npz (infer_irn --soft_output 2); auto: the .npy where it exists, "
                          "else the .npz")
+    ap.add_argument("--mask_type", default="soft", choices=("soft", "label"),
+                    help="soft: the soft pseudo-labels above; label: --mask_root holds label maps <name>.png (one class index "
+                         "per pixel, 255 = ignore)")
     ap.add_argument("--k", default=128, type=int)
     ap.add_argument("--step", default=7, type=int)
     ap.add_argument("--lamb", default=5e-2, type=float)
@@ -81,8 +87,8 @@ def main(argv: Optional[List[str]] = None) -> int:
     os.makedirs(args.tblog_dir, exist_ok=True)
     os.makedirs(args.session_name, exist_ok=True)
     train_dataset = VOC12SegDataset(args.train_list, args.voc12_root, args.mask_root, min_scale=0.5, max_scale=1.75,
-                                    crop_size=args.crop_size, mask_type="soft",
-                                    mask_format=args.mask_format)                           # :119-125
+                                    crop_size=args.crop_size, mask_type=args.mask_type,
+                                    mask_format=args.mask_format, num_classes=args.num_classes)   # :119-125
     if train_dataset.labels is None:
         raise FileNotFoundError("data/cls_labels.npy (the image-level labels, src/data.py:53-56) not found")
     loader = SegLoader(train_dataset, args.batch_size, dev, num_workers=args.num_workers, shuffle=True, drop_last=True,

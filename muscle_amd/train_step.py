@@ -221,7 +221,9 @@ def muscle_step(model, optimizer, batch: Dict[str, torch.Tensor], *, lamb: float
                 criterion2=None, drop_u=None, grad_hook=None, fused: bool = True):
     """One iteration of train_muscle.py:171-203 on the HIP path: seg forward of MuSCLe(mode='dec'), cross entropy against the
     arg-max of the soft pseudo-label, lamb * BEACON FieldLoss, backward, clip_grad_norm_(9), optimizer step.
-    batch: {"img" [N,3,S,S], "label" [N,20], "mask" [N,21,S,S]} on the GPU.
+    batch: {"img" [N,3,S,S], "label" [N,20], "mask" [N,21,S,S]} on the GPU.  A uint8 "mask" [N,S,S] is a hard label map
+    (mask_type="label" of muscle_amd.segdata, 255 = ignore): cross entropy with that ignore index, and the FieldLoss takes
+    the mask rows of its sampled points from the map.
     fused: the FieldLoss samples the decoder's 1/8-resolution features at the chosen points (the [N,256,S,S] dense_ft of
     MuSCLe.py:285 is never materialised); False goes through the public forward(cam='seg') tensors."""
     from . import edge
@@ -232,7 +234,10 @@ def muscle_step(model, optimizer, batch: Dict[str, torch.Tensor], *, lamb: float
     n = label.shape[0]
     label_with_bg = torch.cat((torch.ones((n, 1), dtype=label.dtype, device=label.device), label), dim=1)
     seg_map, ft = model(img, cam="seg_p3" if fused else "seg", drop_u=drop_u)
-    l1 = edge.cross_entropy_argmax(seg_map, mask)
+    if mask.dtype == torch.uint8 and mask.dim() == 3:           # a hard label map (mask_type="label"), 255 = ignore
+        l1 = edge.cross_entropy_label(seg_map, mask)
+    else:
+        l1 = edge.cross_entropy_argmax(seg_map, mask)
     loss, l2 = l1, 0
     if lamb > 0:
         crit = criterion2 if criterion2 is not None else edge.FieldLoss(sobel_size=5, beta=1e2, k=k)

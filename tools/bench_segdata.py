@@ -5,9 +5,13 @@ core, the muscle_step time of tools/bench_dec.py's configuration on the staged b
 restatement of the reference's label resize (tests/segdata_ref.py) on one core.  Not the contract bench.
   python tools/bench_segdata.py [--reps 30] [--no-step]
   python tools/bench_segdata.py --compact [--reps 30]
+  python tools/bench_segdata.py --mask_type label [--reps 30] [--no-step]
 --compact: the same 16 items (labels of three present classes from mx_irn_finish) staged from the dense float16 arrays and
 from their compact form (muscle_amd/softlabel.py), alternating in one run: per form the bytes of the one copy and the
-HIP-event time of the stage; the result is appended to profiles/segdata_bench.txt.  Nothing else is measured then."""
+HIP-event time of the stage; the result is appended to profiles/segdata_bench.txt.  Nothing else is measured then.
+--mask_type label: the same 16 items staged with their soft labels and with hard label maps (mask_type="label": uint8 rows,
+mx_label_stage), alternating in one run: bytes of the one copy, size of the staged mask, HIP-event time of the stage and the B7
+muscle_step on each staged batch; appended to the same file."""
 import os, sys, time, random
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -69,8 +73,68 @@ def compact_run():
         f.write("\n" + "\n".join(lines) + "\n")
 
 
+def label_run():
+    """--mask_type label: the same 16 items with their soft labels (dense float16) and with hard label maps (the arg-max of the
+    soft label as uint8), alternating in one run: bytes of the one copy, HIP-event time of the stage, and - unless --no-step -
+    the B7 muscle_step on each staged batch."""
+    maps = [m.astype(np.float32).argmax(2).astype(np.uint8) for m in masks]
+    forms = {}
+    for name in ("soft", "label"):
+        random.seed(0); torch.manual_seed(0)
+        plans = plan_all() if name == "soft" else [D.plan_label_item(ims[i], maps[i], scales[i], scales[i], S) for i in range(N)]
+        forms[name] = (plans, D.SegStager(dev, N, S))
+    label = torch.from_numpy(synth.synth_labels(N, 7))
+    out = {}
+    for name, (plans, stager) in forms.items():
+        for _ in range(3): out[name] = stager(plans, labels=label)
+    torch.cuda.synchronize()
+    same = torch.equal(out["soft"]["img"], out["label"]["img"])
+    ms = {name: 0.0 for name in forms}
+    rounds, per = 6, max(1, reps // 6)
+    for _ in range(rounds):                                   # alternating: both forms see the same clocks and the same neighbours
+        for name, (plans, stager) in forms.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(per): stager(plans, labels=label)
+            e1.record(); torch.cuda.synchronize()
+            ms[name] += e0.elapsed_time(e1) / (rounds * per)
+    lines = [f"tools/bench_segdata.py --mask_type label: batch {N} at {S}x{S} from {H}x{W} sources, scales {scales[0]:.2f} .. {scales[-1]:.2f}, "
+             f"{rounds} x {per} reps per form, alternating; staged images of the two forms bit-equal: {same}"]
+    kern = {"soft": "mx_mask_stage", "label": "mx_label_stage"}
+    for name, (plans, stager) in forms.items():
+        m = out[name]["mask"]
+        lines.append(f"  {name:5s}: {stager.last_bytes/1e6:8.2f} MB in the one copy, mask {tuple(m.shape)} {str(m.dtype).replace('torch.', '')} = "
+                     f"{m.numel() * m.element_size()/1e6:.2f} MB, {ms[name]:.3f} ms/batch between HIP events "
+                     f"(copy, mx_color_jitter, mx_resample, mx_input_stage, {kern[name]})")
+    if "--no-step" in sys.argv:
+        lines.append("  muscle_step: not measured (--no-step)")
+    else:
+        torch.manual_seed(0)
+        model = muscle_amd.MuSCLe(21, "efficientnet-b7", layers=3, last_pooling=True, mode="dec").to(dev)
+        opt = muscle_amd.FusedAdam(model.live_parameters("seg"), lr=1e-5, weight_decay=5e-5)
+        for name in forms:
+            for _ in range(3): res = muscle_amd.muscle_step(model, opt, out[name], lamb=0.05, step=7, k=128)
+        dt, rounds, per = {name: 0.0 for name in forms}, 3, 3
+        for _ in range(rounds):
+            for name in forms:
+                torch.cuda.synchronize(); t0 = time.perf_counter()
+                for _ in range(per): res = muscle_amd.muscle_step(model, opt, out[name], lamb=0.05, step=7, k=128)
+                torch.cuda.synchronize(); dt[name] += (time.perf_counter() - t0) / (rounds * per)
+        for name in forms:
+            lines.append(f"  {name:5s}: muscle_step B7 dec {S}x{S} bs{N} lamb=0.05 on the staged batch: {dt[name]*1e3:.1f} ms/step  "
+                         f"{N/dt[name]:.1f} img/s ({rounds} x {per} steps per form, alternating)")
+    print("\n".join(lines))
+    with open(os.path.join(ROOT, "profiles", "segdata_bench.txt"), "a") as f:
+        f.write("\n" + "\n".join(lines) + "\n")
+
+
 if "--compact" in sys.argv:
     compact_run()
+    sys.exit(0)
+if "--mask_type" in sys.argv:
+    if sys.argv[sys.argv.index("--mask_type") + 1] != "label":
+        sys.exit("--mask_type label is the only leg of that name (the soft path is the default run)")
+    label_run()
     sys.exit(0)
 
 plans = plan_all()
