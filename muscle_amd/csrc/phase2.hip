@@ -216,6 +216,7 @@ __global__ __launch_bounds__(256) void crop_resize_bwd_kernel(const float* gout_
   // grid.z cuts the image into bands of rows: workgroup (n, kg, band) owns the band's source pixels (96 workgroups for a batch
   // of 32 left the chip idle: 680 us).  An element still has one adder, and still meets its crops in table order.
   const int bh = (H + gridDim.z - 1) / gridDim.z, by0 = blockIdx.z * bh, by1 = min(H, by0 + bh);
+  const int nj = min(CROP_KG, FP - k0);   // columns of this group inside a packed row: the group at k0 = 21 (K > 21) has 3, not 7
   for (int ci = 0; ci < ncrops; ++ci) {
     const int* trow = table + ci * 8;
     if (trow[0] != n) continue;                   // (uniform over the workgroup)
@@ -244,7 +245,8 @@ __global__ __launch_bounds__(256) void crop_resize_bwd_kernel(const float* gout_
           const float* g = gout + (long)(r * rw + c) * FP + k0;
           const float wgt = wyy * wxx;
 #pragma unroll
-          for (int j = 0; j < CROP_KG; ++j) acc[j] += wgt * g[j];
+          for (int j = 0; j < CROP_KG; ++j)
+            if (j < nj) acc[j] += wgt * g[j];     // (uniform; g[j] past column FP - 1 is the next row, or past the buffer)
         }
       }
 #pragma unroll
@@ -475,7 +477,7 @@ __global__ __launch_bounds__(EMD_T) void emd_score_kernel(const float* feat, con
 // enumeration order: stable sort semantics, :318); loss += score/ns.  Pairs are spread over the threads; the per-sample
 // minimum is an LDS atomicMin on the 64-bit key (order-preserving score bits, rank) - a minimum does not depend on arrival order.
 __device__ __forceinline__ unsigned emd_ord(float f) {
-  const unsigned u = __float_as_uint(f);
+  const unsigned u = (f == 0.f) ? 0u : __float_as_uint(f);      // -0 and +0 compare equal in the reference's sort: one key
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __global__ __launch_bounds__(1024) void emd_best_kernel(const float* score, const int* pairs, int npairs, int nsamples, int* best, float* loss) {

@@ -14,6 +14,11 @@ import torch
 from ._lib import call, ptr, stream
 
 
+def _f32(x: float) -> float:
+    """x as the kernel receives it through a float argument."""
+    return torch.tensor(x, dtype=torch.float32).item()
+
+
 class FusedAdam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
@@ -150,6 +155,9 @@ class FusedAdam(torch.optim.Optimizer):
                 self._flatten(group)
                 self._apply_pending(group)
             b1, b2 = group["betas"]
+            # the kernel takes the betas as floats and forms 1 - beta from them; the bias corrections use the same rounded values
+            # (1 - float(0.999) is off by 1.3e-5 of 1 - 0.999: corrected with the exact beta, the first steps came out 6e-6 long)
+            b1r, b2r = _f32(b1), _f32(b2)
             ps, offs, sizes, steps = group["params"], group["_offs"], group["_sizes"], group["_steps"]
             arena, m, v = group["_arena"], group["_m"], group["_v"]
             dyn, touched = None, []
@@ -179,8 +187,8 @@ class FusedAdam(torch.optim.Optimizer):
                 # same expressions as the host path (double, then rounded to float by the kernel argument)
                 st["t"].add_(1.0)
                 st["dyn"][0] = st["lr"]
-                st["dyn"][1] = 1.0 - torch.pow(torch.full_like(st["t"], b1), st["t"])
-                st["dyn"][2] = torch.sqrt(1.0 - torch.pow(torch.full_like(st["t"], b2), st["t"]))
+                st["dyn"][1] = 1.0 - torch.pow(torch.full_like(st["t"], b1r), st["t"])
+                st["dyn"][2] = torch.sqrt(1.0 - torch.pow(torch.full_like(st["t"], b2r), st["t"]))
                 dyn = st["dyn"]
                 self._touched.append((group, touched))
             # runs of consecutive parameters that have gradients laid out contiguously and share a step count
@@ -197,15 +205,20 @@ class FusedAdam(torch.optim.Optimizer):
                        and ps[j].grad.is_contiguous()):
                     span = offs[j] - offs[i] + ps[j].numel()
                     j += 1
-                if j == i:       # gradient not where the arena layout expects it: single-tensor launch
+                if j == i or g0.data_ptr() % 16:
+                    # gradient not where the arena layout expects it, or not on the 16 bytes the kernel's float4 loads need (a
+                    # contiguous view at an odd offset of a larger tensor): single-tensor launch, from an aligned copy if need be
                     j, span = i + 1, p.numel()
-                    gptr = ptr(p.grad.contiguous())
+                    galigned = p.grad.contiguous()
+                    if galigned.data_ptr() % 16:
+                        galigned = galigned.clone()
+                    gptr = ptr(galigned)
                 else:
                     gptr = g0.data_ptr()
                 t = steps[i] + 1
                 call("mx_adam", arena.data_ptr() + 4 * offs[i], gptr, m.data_ptr() + 4 * offs[i], v.data_ptr() + 4 * offs[i],
                      span, float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
-                     1.0 - b1 ** t, math.sqrt(1.0 - b2 ** t), ptr(dyn), stream())
+                     1.0 - b1r ** t, math.sqrt(1.0 - b2r ** t), ptr(dyn), stream())
                 for q in range(i, j):
                     steps[q] = t
                     touched.append(q)
