@@ -70,6 +70,14 @@ int mx_get_wgrad_kernel(void);
 /* 1 if, in the current mode, this GEMM runs in split arithmetic on the bf16 pipe (kind 0: mx_pw_fwd / data gradient
  * C[M,N] = A[M,K] W[N,K]^T; kind 1: weight gradient dW[M=Co,N=Ci] over K=R rows), else 0 - for measurement code. */
 int mx_gemm_uses_split(int kind, int M, int N, int K);
+/* Which kernel a forward / data-gradient GEMM C[M,N] = A'[M,K] W[N,K]^T would launch in the current mode (tests and measurement;
+ * launches nothing, touches no device).  entry 0: the route of mx_pw_fwd, mx_bgemm layout 0 and mx_pw_dgrad_bnbwd (a_mode 3);
+ * entry 1: the planes route, mx_pw_fwd_planes (a_mode 0), mx_pw_fwd_planes_act (a_mode 1), mx_pw_dgrad_bnbwd_planes (a_mode 3).
+ * Answer = family * 10000 + tile width * 10 + grid form.  family: 1 gemm_nt_kernel (exact fp32), 2 gemm_nt_split_kernel (first
+ * split generation), 3 gemm_nt_split3_kernel (weight planes).  Tile width: the columns of the 128-row tile.  Grid form: 0 = 3-D
+ * grid, 1 = 1-D XCD-ordered ids, 2 = XCD-ordered in chunks of N tiles.  MX_EARG for extents the entry point would refuse.  The
+ * launchers run the same planning functions, so the answer is the launch. */
+int mx_pw_fwd_plan(int entry, int a_mode, int M, int K, int N, int batch);
 
 /* Second-generation split kernel (round 4): the weight of a 1x1 convolution (model.py:44,63: `_expand_conv`, `_project_conv`) is
  * split ONCE per optimizer step into three bf16 planes laid out as the kernel's LDS image (bytes: mx_pw_planes_bytes; K % 32 == 0,

@@ -622,8 +622,10 @@ __global__ __launch_bounds__(256, gemm_nt_waves(TM * TN * 4 + (AMODE == MX_BNBWD
         if (AMODE == MX_BNBWD) {
           if (oka[i] && kin) {                               // dX = c1*g + c2*x + c3 (bn_bwd_apply), also kept for the weight gradient
             const float4 x = gt[AMODE == MX_BNBWD ? i : 0];
-            v.x = sc4.x * v.x + sh4.x * x.x + c34.x; v.y = sc4.y * v.y + sh4.y * x.y + c34.y;
-            v.z = sc4.z * v.z + sh4.z * x.z + c34.z; v.w = sc4.w * v.w + sh4.w * x.w + c34.w;
+            // two fused roundings, c1*g + (c2*x + c3), as gemm_nt_split3_kernel and the weight-gradient side form it (left to right it
+            // is a product, an fma and an add: three roundings, and the stored dZ missed the bound the other producers keep)
+            v.x = sc4.x * v.x + (sh4.x * x.x + c34.x); v.y = sc4.y * v.y + (sh4.y * x.y + c34.y);
+            v.z = sc4.z * v.z + (sh4.z * x.z + c34.z); v.w = sc4.w * v.w + (sh4.w * x.w + c34.w);
             if (tile_n == 0) st4(g.a_out + (pa[i] - g.a.p) + k0, v);
           }
         } else if (AMODE != MX_PLAIN && oka[i] && kin) v = nt_prologue<AMODE>(v, sc4, sh4, gt[AMODE == MX_BNACT ? i : 0]);
@@ -1183,29 +1185,39 @@ static bool nt_uses_split(int N, int K) {
   return g_gemm_mode == 2 || (g_gemm_mode == 1 && K >= 128 && N >= 96 && (double)N / (64.0 * cdiv(N, 64)) >= 0.74);
 }
 
-template <int NJ>
-static void launch_nt_split_t(const GemmArgs& g, int batch, hipStream_t st) {
-  constexpr int BN = 64 * NJ;
-  const int mt = cdiv(g.M, 128), nt = cdiv(g.N, BN);
-  GemmArgs a = g;
-  a.mt = mt;
-  a.xcd_nt = 0;
-  dim3 grid(mt, nt, batch);
-  if (nt >= 2 && nt <= 16 && mt >= 64) { a.xcd_nt = nt; grid = dim3(8 * cdiv(mt, 8) * nt, 1, batch); }
-  switch (g.a.mode) {
-    case MX_PLAIN: hipLaunchKernelGGL((gemm_nt_split_kernel<MX_PLAIN, NJ>), grid, dim3(256), 0, st, a); break;
-    case MX_BNACT: hipLaunchKernelGGL((gemm_nt_split_kernel<MX_BNACT, NJ>), grid, dim3(256), 0, st, a); break;
-    default: hipLaunchKernelGGL((gemm_nt_split_kernel<MX_AFFINE, NJ>), grid, dim3(256), 0, st, a); break;
-  }
+// =====================================================================================================================
+// Launch plans of the NT family: pure host functions of the extents, the arithmetic mode and the two lab hooks.  The launchers
+// below AND the query mx_pw_fwd_plan call them, so what the query reports is what a launch does.
+static int g_split_nj = 0;     // tile override of both split generations (lab hook: tools/hip/gemm_lab.hip assigns it): 1 force 128 x 64, 2 force 128 x 128, 3: 64 / 128 only, >= 16: that width (second generation)
+static int g_split3_xcd_chunk = 6;     // N tiles per XCD-local chunk when there are more than 16 (lab hook: tools/hip/gemm_lab.hip chunk)
+
+// grid of one launch: form 0 = 3-D grid (M tiles, N tiles, batch); 1 = 1-D XCD-ordered ids, the xcd_nt N tiles of an M tile back to
+// back on one XCD; 2 = the same inside `chunks` chunks of xcd_nt N tiles each (second-generation split kernel only)
+struct NtGrid { int form, xcd_nt, chunks; };
+
+// gemm_nt_kernel and gemm_nt_split_kernel: XCD-aware ids for 2..16 N tiles over a streamed A (17..32 N tiles measured: 1-5 % slower)
+static NtGrid nt_grid(int mt, int nt) {
+  if (nt >= 2 && nt <= 16 && mt >= 64) return NtGrid{1, nt, 1};
+  return NtGrid{0, 0, 1};
 }
 
-// 128 x 128 unless the narrower tile pads fewer columns or balances the 768 resident workgroups (3 per CU) better
-static int g_split_nj = 0;     // tile override of both split generations (lab hook: tools/hip/gemm_lab.hip assigns it): 1 force 128 x 64, 2 force 128 x 128, 3: 64 / 128 only, >= 16: that width (second generation)
-static void launch_nt_split(const GemmArgs& g, int batch, hipStream_t st) {
+// gemm_nt_split3_kernel: up to 16 N tiles: one chunk; more (N = 2304: 18, N = 3840: 30): chunks of ~6 (measured 227 -> 219 us and
+// 572 -> 545 us; eleven tiles cut into 6 + 5 lost 10 %, so the short lists stay whole)
+static NtGrid nt_split3_grid(int mt, int nt) {
+  if (nt >= 2 && mt >= 64) {
+    const int chunks = nt <= 16 ? 1 : cdiv(nt, g_split3_xcd_chunk);
+    return NtGrid{chunks > 1 ? 2 : 1, cdiv(nt, chunks), chunks};
+  }
+  return NtGrid{0, 0, 1};
+}
+
+// First split generation, tile width: 128 x 128 unless the narrower tile pads fewer columns or balances the 768 resident
+// workgroups (3 per CU) better
+static int nt_split_width(int M, int N, int K, int batch) {
   const int forced = g_split_nj;
   auto score = [&](int bn, double eff) {
-    const long nt = cdiv(g.N, bn), tiles = (long)cdiv(g.M, 128) * nt * batch;
-    const double pad = (double)g.N / (double)(nt * bn);
+    const long nt = cdiv(N, bn), tiles = (long)cdiv(M, 128) * nt * batch;
+    const double pad = (double)N / (double)(nt * bn);
     const double rounds = (double)tiles / 768.0;
     const double balance = rounds / (double)(long)(rounds + 0.999999);
     return eff * pad * balance;
@@ -1216,52 +1228,28 @@ static void launch_nt_split(const GemmArgs& g, int batch, hipStream_t st) {
   // 64-wide tile does 0.87 of the 128-wide tile's work per unit time.  (K = 3840 -> N = 640 took 876 us with the 64-wide tile
   // the first rule picked and 788 us with the 128-wide one.)
   auto cost = [&](int bn, double eff) {
-    const double rounds = (double)cdiv(g.M, 128) * cdiv(g.N, bn) * batch / 768.0;
+    const double rounds = (double)cdiv(M, 128) * cdiv(N, bn) * batch / 768.0;
     const double full = (double)(long)rounds, tail = rounds - full;
     return (full + (tail > 0 ? (tail + 0.12 < 1.0 ? tail + 0.12 : 1.0) : 0.0)) * bn / eff;
   };
   const bool narrow = forced ? forced == 1
-                    : g.K >= 1024 ? cost(64, 0.87) < cost(128, 1.0)
-                                  : score(64, 0.92) > score(128, 1.0) + 1e-9;
-  if (narrow) launch_nt_split_t<1>(g, batch, st);
-  else launch_nt_split_t<2>(g, batch, st);
+                    : K >= 1024 ? cost(64, 0.87) < cost(128, 1.0)
+                                : score(64, 0.92) > score(128, 1.0) + 1e-9;
+  return narrow ? 64 : 128;
 }
 
-// ---- second-generation split kernel: pre-split weight planes (mx_pw_planes_batch) -----------------------------------
-static int g_split3_xcd_chunk = 6;     // N tiles per XCD-local chunk when there are more than 16 (lab hook: tools/hip/gemm_lab.hip chunk)
-template <int TN>
-static void launch_nt_split3_t(const GemmArgs& g, int batch, hipStream_t st) {
-  constexpr int BN = 16 * TN;
-  const int mt = cdiv(g.M, 128), nt = cdiv(g.N, BN);
-  GemmArgs a = g;
-  a.mt = mt;
-  a.xcd_nt = 0;
-  dim3 grid(mt, nt, batch);
-  if (nt >= 2 && mt >= 64) {
-    // up to 16 N tiles: one chunk; more (N = 2304: 18, N = 3840: 30): chunks of ~6 (measured 227 -> 219 us and 572 -> 545 us;
-    // eleven tiles cut into 6 + 5 lost 10 %, so the short lists stay whole)
-    const int chunks = nt <= 16 ? 1 : cdiv(nt, g_split3_xcd_chunk);
-    a.xcd_nt = cdiv(nt, chunks); a.zt = nt;
-    grid = dim3(chunks * 8 * cdiv(mt, 8) * a.xcd_nt, 1, batch);
-  }
-  if (g.a.mode == MX_BNBWD) hipLaunchKernelGGL((gemm_nt_split3_kernel<TN, MX_BNBWD>), grid, dim3(256), 0, st, a);
-  else if (g.a.mode == MX_BNACT) {
-    if constexpr (TN <= 6) hipLaunchKernelGGL((gemm_nt_split3_kernel<TN, MX_BNACT>), grid, dim3(256), 0, st, a);     // (launch_nt_split3 keeps the activated form at <= 96 columns)
-  } else hipLaunchKernelGGL((gemm_nt_split3_kernel<TN, MX_PLAIN>), grid, dim3(256), 0, st, a);
-}
-
-// Tile width: 128 columns, or 112 / 96 / 80 / 64 where that pads less or balances better.  Tiles are dealt over 256 CUs: time ~
-// (tiles per CU + half a tile of tail) x tile width / efficiency of the width (a narrower tile re-loads and re-splits the same
-// activation rows for fewer columns: 0.85 at 64, measured 0.84-0.96 on the M = 25088 layers); a grid of fewer than ~1.2 wide tiles
-// per CU always takes the 64-wide tile (M = 6272: 2304 -> 384 108 -> 91 us, M = 12544: 1152 -> 192 61 -> 51).  The odd widths are
-// only taken where they divide N (N = 160 = 2 x 80, 224 = 2 x 112, 960 = 10 x 96, 2304 = 24 x 96): no padded columns at all
+// Second split generation, tile width: 128 columns, or 112 / 96 / 80 / 64 where that pads less or balances better.  Tiles are dealt
+// over 256 CUs: time ~ (tiles per CU + half a tile of tail) x tile width / efficiency of the width (a narrower tile re-loads and
+// re-splits the same activation rows for fewer columns: 0.85 at 64, measured 0.84-0.96 on the M = 25088 layers); a grid of fewer than
+// ~1.2 wide tiles per CU always takes the 64-wide tile (M = 6272: 2304 -> 384 108 -> 91 us, M = 12544: 1152 -> 192 61 -> 51).  The odd
+// widths are only taken where they divide N (N = 160 = 2 x 80, 224 = 2 x 112, 960 = 10 x 96, 2304 = 24 x 96): no padded columns at all
 // (960 -> 160: 69 us at 64 columns, 55 at 80; 1344 -> 224: 99 at 128, 91 at 112; 480 -> 80 at 100 352 rows: 73 -> 54).
-static void launch_nt_split3(const GemmArgs& g, int batch, hipStream_t st) {
+static int nt_split3_width(int M, int N, int K, int batch, int a_mode) {
   auto cost = [&](int bn, double eff) {
-    const double per_cu = (double)cdiv(g.M, 128) * cdiv(g.N, bn) * batch / 256.0;
+    const double per_cu = (double)cdiv(M, 128) * cdiv(N, bn) * batch / 256.0;
     return (per_cu + 0.5) * bn / eff;
   };
-  const long wide_tiles = (long)cdiv(g.M, 128) * cdiv(g.N, 128) * batch;
+  const long wide_tiles = (long)cdiv(M, 128) * cdiv(N, 128) * batch;
   int bn = 128;
   if (g_split_nj >= 16) bn = g_split_nj;                                   // lab: force this width
   else if (g_split_nj == 1 || (g_split_nj != 2 && wide_tiles <= 300)) bn = 64;
@@ -1269,23 +1257,20 @@ static void launch_nt_split3(const GemmArgs& g, int batch, hipStream_t st) {
     // short reductions (K <= 512: few K steps per tile, so a tile's fill and epilogue weigh more) reward the widths that run four
     // workgroups per CU (96 and 80 columns: 112-128 registers, <= 36 KB of LDS): tools/hip/gemm_lab widths,
     // profiles/r04_gemm_lab_widths.txt - 384 -> 2304: 236 (128) / 216 (96); 224 -> 1344: 97 / 89.5; 160 -> 960: 65 / 57.5
-    const bool shortk = g.K <= 512;
+    const bool shortk = K <= 512;
     const double e64 = shortk ? 0.90 : 0.85, e80 = shortk ? 0.97 : 0.90, e96 = shortk ? 1.03 : 0.94, e112 = 0.97;
     double best = cost(128, 1.0);
     if (cost(64, e64) < best) { best = cost(64, e64); bn = 64; }
     if (g_split_nj != 3) {
-      if (g.N % 112 == 0 && cost(112, e112) < best) { best = cost(112, e112); bn = 112; }
-      if (g.N % 96 == 0 && cost(96, e96) < best) { best = cost(96, e96); bn = 96; }
-      if (g.N % 80 == 0 && cost(80, e80) < best) { best = cost(80, e80); bn = 80; }
+      if (N % 112 == 0 && cost(112, e112) < best) { best = cost(112, e112); bn = 112; }
+      if (N % 96 == 0 && cost(96, e96) < best) { best = cost(96, e96); bn = 96; }
+      if (N % 80 == 0 && cost(80, e80) < best) { best = cost(80, e80); bn = 80; }
     }
   }
-  if (g.a.mode == MX_BNACT && bn > 96) bn = (g.N % 96 == 0) ? 96 : 64;     // (the activated form exists up to 96 columns)
-  switch (bn) {
-    case 64: launch_nt_split3_t<4>(g, batch, st); break;
-    case 80: launch_nt_split3_t<5>(g, batch, st); break;
-    case 96: launch_nt_split3_t<6>(g, batch, st); break;
-    case 112: launch_nt_split3_t<7>(g, batch, st); break;
-    default: launch_nt_split3_t<8>(g, batch, st); break;
+  if (a_mode == MX_BNACT && bn > 96) bn = (N % 96 == 0) ? 96 : 64;         // (the activated form exists up to 96 columns)
+  switch (bn) {                                                            // (the widths that are compiled; any other: 128)
+    case 64: case 80: case 96: case 112: return bn;
+    default: return 128;
   }
 }
 
@@ -1293,23 +1278,6 @@ static void launch_nt_split3(const GemmArgs& g, int batch, hipStream_t st) {
 struct NtCfg { int bm, bn; };
 static const NtCfg kNtCfgs[] = {{128, 128}, {128, 96}, {128, 64}, {128, 48}, {128, 80}, {128, 32}, {128, 160}};
 constexpr int kNumNtCfgs = sizeof(kNtCfgs) / sizeof(kNtCfgs[0]);
-
-template <int WM, int WN, int TM, int TN>
-static void launch_nt(const GemmArgs& g, int batch, hipStream_t st) {
-  constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
-  const int mt = cdiv(g.M, BM), nt = cdiv(g.N, BN);
-  GemmArgs a = g;
-  a.mt = mt;
-  a.xcd_nt = 0;
-  dim3 grid(mt, nt, batch);
-  if (nt >= 2 && nt <= 16 && mt >= 64) { a.xcd_nt = nt; grid = dim3(8 * cdiv(mt, 8) * nt, 1, batch); }
-  switch (g.a.mode) {
-    case MX_PLAIN: hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, TM, TN, MX_PLAIN>), grid, dim3(256), 0, st, a); break;
-    case MX_BNACT: hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, TM, TN, MX_BNACT>), grid, dim3(256), 0, st, a); break;
-    case MX_BNBWD: hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, TM, TN, MX_BNBWD>), grid, dim3(256), 0, st, a); break;
-    default: hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, TM, TN, MX_AFFINE>), grid, dim3(256), 0, st, a); break;
-  }
-}
 
 // Choice among the NT tiles: fewest padded columns first (16-column granularity), then the widest tile whose grid still
 // gives every CU at least ~2 workgroups.
@@ -1330,19 +1298,105 @@ static int pick_nt_cfg(int M, int N) {
   return best;
 }
 
+// What one forward / data-gradient launch runs: family 1 = gemm_nt_kernel, 2 = gemm_nt_split_kernel, 3 = gemm_nt_split3_kernel;
+// bn = the tile width; cfg = the index into kNtCfgs (family 1 only); grid as above.
+struct NtPlan { int family, bn, cfg; NtGrid grid; };
+
+// the gemm_common(L_NT) route (mx_pw_fwd, mx_bgemm layout 0, mx_pw_dgrad_bnbwd)
+static NtPlan plan_nt(int a_mode, int M, int N, int K, int batch) {
+  NtPlan p{};
+  if (a_mode != MX_BNBWD && nt_uses_split(N, K)) {     // MFMA-bound shapes only: K and N large enough, <= 26 % padded columns
+    p.family = 2;
+    p.bn = nt_split_width(M, N, K, batch);
+  } else {
+    p.family = 1;
+    p.cfg = pick_nt_cfg(M, N);
+    p.bn = kNtCfgs[p.cfg].bn;
+  }
+  p.grid = nt_grid(cdiv(M, 128), cdiv(N, p.bn));
+  return p;
+}
+
+// the planes route (mx_pw_fwd_planes, mx_pw_fwd_planes_act, mx_pw_dgrad_bnbwd_planes)
+static NtPlan plan_nt_planes(int a_mode, int M, int N, int K, int batch) {
+  NtPlan p{};
+  p.family = 3;
+  p.bn = nt_split3_width(M, N, K, batch, a_mode);
+  p.grid = nt_split3_grid(cdiv(M, 128), cdiv(N, p.bn));
+  return p;
+}
+
+// grid dimensions and the kernel's grid arguments from a plan (every tile of the family has 128 rows)
+static dim3 nt_apply_grid(GemmArgs& a, const NtPlan& p, int batch) {
+  const int mt = cdiv(a.M, 128), nt = cdiv(a.N, p.bn);
+  a.mt = mt;
+  a.xcd_nt = p.grid.xcd_nt;
+  if (p.grid.form == 0) return dim3(mt, nt, batch);
+  a.zt = nt;                                             // (read by the second-generation split kernel only)
+  return dim3(p.grid.chunks * 8 * cdiv(mt, 8) * p.grid.xcd_nt, 1, batch);
+}
+
+template <int NJ>
+static void launch_nt_split_t(const GemmArgs& g, const NtPlan& p, int batch, hipStream_t st) {
+  GemmArgs a = g;
+  const dim3 grid = nt_apply_grid(a, p, batch);
+  switch (g.a.mode) {
+    case MX_PLAIN: hipLaunchKernelGGL((gemm_nt_split_kernel<MX_PLAIN, NJ>), grid, dim3(256), 0, st, a); break;
+    case MX_BNACT: hipLaunchKernelGGL((gemm_nt_split_kernel<MX_BNACT, NJ>), grid, dim3(256), 0, st, a); break;
+    default: hipLaunchKernelGGL((gemm_nt_split_kernel<MX_AFFINE, NJ>), grid, dim3(256), 0, st, a); break;
+  }
+}
+
+// ---- second-generation split kernel: pre-split weight planes (mx_pw_planes_batch) -----------------------------------
+template <int TN>
+static void launch_nt_split3_t(const GemmArgs& g, const NtPlan& p, int batch, hipStream_t st) {
+  GemmArgs a = g;
+  const dim3 grid = nt_apply_grid(a, p, batch);
+  if (g.a.mode == MX_BNBWD) hipLaunchKernelGGL((gemm_nt_split3_kernel<TN, MX_BNBWD>), grid, dim3(256), 0, st, a);
+  else if (g.a.mode == MX_BNACT) {
+    if constexpr (TN <= 6) hipLaunchKernelGGL((gemm_nt_split3_kernel<TN, MX_BNACT>), grid, dim3(256), 0, st, a);     // (nt_split3_width keeps the activated form at <= 96 columns)
+  } else hipLaunchKernelGGL((gemm_nt_split3_kernel<TN, MX_PLAIN>), grid, dim3(256), 0, st, a);
+}
+
+static void launch_nt_split3(const GemmArgs& g, int batch, hipStream_t st) {
+  const NtPlan p = plan_nt_planes(g.a.mode, g.M, g.N, g.K, batch);
+  switch (p.bn) {
+    case 64: launch_nt_split3_t<4>(g, p, batch, st); break;
+    case 80: launch_nt_split3_t<5>(g, p, batch, st); break;
+    case 96: launch_nt_split3_t<6>(g, p, batch, st); break;
+    case 112: launch_nt_split3_t<7>(g, p, batch, st); break;
+    default: launch_nt_split3_t<8>(g, p, batch, st); break;
+  }
+}
+
+template <int WM, int WN, int TM, int TN>
+static void launch_nt(const GemmArgs& g, const NtPlan& p, int batch, hipStream_t st) {
+  static_assert(WM * TM * 16 == 128, "every NT tile has 128 rows (nt_apply_grid, mx_pw_fwd_parts)");
+  GemmArgs a = g;
+  const dim3 grid = nt_apply_grid(a, p, batch);
+  switch (g.a.mode) {
+    case MX_PLAIN: hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, TM, TN, MX_PLAIN>), grid, dim3(256), 0, st, a); break;
+    case MX_BNACT: hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, TM, TN, MX_BNACT>), grid, dim3(256), 0, st, a); break;
+    case MX_BNBWD: hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, TM, TN, MX_BNBWD>), grid, dim3(256), 0, st, a); break;
+    default: hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, TM, TN, MX_AFFINE>), grid, dim3(256), 0, st, a); break;
+  }
+}
+
 static void dispatch_nt(const GemmArgs& g, int batch, hipStream_t st) {
-  if (g.a.mode != MX_BNBWD && nt_uses_split(g.N, g.K)) {
-    launch_nt_split(g, batch, st);       // MFMA-bound shapes only: K and N large enough, <= 26 % padded columns
+  const NtPlan p = plan_nt(g.a.mode, g.M, g.N, g.K, batch);
+  if (p.family == 2) {
+    if (p.bn == 64) launch_nt_split_t<1>(g, p, batch, st);
+    else launch_nt_split_t<2>(g, p, batch, st);
     return;
   }
-  switch (pick_nt_cfg(g.M, g.N)) {
-    case 0: launch_nt<2, 2, 4, 4>(g, batch, st); break;     // 128 x 128
-    case 1: launch_nt<2, 2, 4, 3>(g, batch, st); break;     // 128 x 96
-    case 2: launch_nt<2, 2, 4, 2>(g, batch, st); break;     // 128 x 64
-    case 3: launch_nt<4, 1, 2, 3>(g, batch, st); break;     // 128 x 48
-    case 4: launch_nt<4, 1, 2, 5>(g, batch, st); break;     // 128 x 80
-    case 5: launch_nt<4, 1, 2, 2>(g, batch, st); break;     // 128 x 32
-    default: launch_nt<2, 2, 4, 5>(g, batch, st); break;    // 128 x 160
+  switch (p.cfg) {
+    case 0: launch_nt<2, 2, 4, 4>(g, p, batch, st); break;     // 128 x 128
+    case 1: launch_nt<2, 2, 4, 3>(g, p, batch, st); break;     // 128 x 96
+    case 2: launch_nt<2, 2, 4, 2>(g, p, batch, st); break;     // 128 x 64
+    case 3: launch_nt<4, 1, 2, 3>(g, p, batch, st); break;     // 128 x 48
+    case 4: launch_nt<4, 1, 2, 5>(g, p, batch, st); break;     // 128 x 80
+    case 5: launch_nt<4, 1, 2, 2>(g, p, batch, st); break;     // 128 x 32
+    default: launch_nt<2, 2, 4, 5>(g, p, batch, st); break;    // 128 x 160
   }
 }
 
@@ -1383,6 +1437,11 @@ static int gemm_common(int layout, GemmArgs& g, int batch, hipStream_t st) {
   if (layout == L_NT) {
     MX_CHECK_ARG(g.K % 4 == 0, "gemm NT: K=%d must be a multiple of 4", g.K);
     MX_CHECK_ARG(g.b.mode == MX_PLAIN, "gemm NT: operand B must be plain (mode %d given): the NT kernels apply a prologue to A only", g.b.mode);
+    // the epilogues store and load C / residual 16 bytes at a time when ldc and N are multiples of 4 (nt_epilogue's `vec`), and every
+    // batch member's operands are read 16 bytes at a time
+    MX_CHECK_ARG(((g.ldc | g.N) & 3) != 0 || ((((uintptr_t)g.c | (uintptr_t)g.residual) & 15) == 0 && g.sc % 4 == 0),
+                 "gemm NT: C and residual must be 16-byte aligned (and the batch stride of C a multiple of 4) when ldc=%d and N=%d are multiples of 4", g.ldc, g.N);
+    MX_CHECK_ARG(g.sa % 4 == 0 && g.sb % 4 == 0, "gemm NT: batch strides of A and B must be multiples of 4 (sa=%ld sb=%ld)", g.sa, g.sb);
     dispatch_nt(g, batch, st);                                   // second-generation NT kernels (profiles/r02_gemm_nt_v2_vs_short.txt)
   } else if (layout == L_NN) {
     MX_CHECK_ARG(g.K % 4 == 0 && g.N % 4 == 0, "gemm NN: K=%d and N=%d must be multiples of 4", g.K, g.N);
@@ -1519,7 +1578,7 @@ int mx_pw_fwd_planes(const float* A, const void* Wplanes, float* C, int M, int K
   MX_CHECK_ARG(A && Wplanes && C, "pw_fwd_planes: null pointer");
   MX_CHECK_ARG(M > 0 && N > 0 && K > 0 && K % 16 == 0, "pw_fwd_planes: bad extents M=%d N=%d K=%d (K must be a multiple of 16)", M, N, K);
   MX_CHECK_ARG(lda % 4 == 0 && lda >= K && ldc >= N, "pw_fwd_planes: bad leading dimensions lda=%d ldc=%d", lda, ldc);
-  MX_CHECK_ARG((((uintptr_t)A | (uintptr_t)Wplanes | (uintptr_t)C) & 15) == 0, "pw_fwd_planes: pointers must be 16-byte aligned");
+  MX_CHECK_ARG((((uintptr_t)A | (uintptr_t)Wplanes | (uintptr_t)C | (uintptr_t)residual) & 15) == 0, "pw_fwd_planes: pointers must be 16-byte aligned");
   GemmArgs g{};
   g.a = MxOperand{A, nullptr, nullptr, nullptr, MX_PLAIN, 1};
   g.b = MxOperand{reinterpret_cast<const float*>(Wplanes), nullptr, nullptr, nullptr, MX_PLAIN, 1};
@@ -1564,7 +1623,8 @@ int mx_pw_dgrad_bnbwd_planes(const float* G, const float* X, const float* coef, 
   MX_CHECK_ARG(G && X && coef && WtPlanes && dX, "pw_dgrad_bnbwd_planes: null pointer");
   MX_CHECK_ARG(M > 0 && N > 0 && K > 0 && K % 32 == 0, "pw_dgrad_bnbwd_planes: bad extents M=%d N=%d K=%d (K must be a multiple of 32)", M, N, K);
   MX_CHECK_ARG(ldg % 4 == 0 && ldg >= K && ldx >= N, "pw_dgrad_bnbwd_planes: bad leading dimensions");
-  MX_CHECK_ARG((((uintptr_t)G | (uintptr_t)X | (uintptr_t)coef | (uintptr_t)WtPlanes | (uintptr_t)dX) & 15) == 0, "pw_dgrad_bnbwd_planes: pointers must be 16-byte aligned");
+  MX_CHECK_ARG((((uintptr_t)G | (uintptr_t)X | (uintptr_t)coef | (uintptr_t)WtPlanes | (uintptr_t)dX | (uintptr_t)residual) & 15) == 0,
+               "pw_dgrad_bnbwd_planes: pointers must be 16-byte aligned");
   GemmArgs g{};
   g.a = MxOperand{G, coef, coef + K, X, MX_BNBWD, 1};
   g.b = MxOperand{reinterpret_cast<const float*>(WtPlanes), nullptr, nullptr, nullptr, MX_PLAIN, 1};
@@ -1591,6 +1651,28 @@ bool mx_wgrad_uses_split(int R, int Co, int Ci);      // wgrad.hip
 int mx_gemm_uses_split(int kind, int M, int N, int K) {
   if (kind == 0) return nt_uses_split(N, K) ? 1 : 0;
   return mx_wgrad_uses_split(K, M, N) ? 1 : 0;
+}
+
+// Which kernel a forward / data-gradient GEMM C[M,N] = A'[M,K] W[N,K]^T would launch in the current arithmetic mode; launches nothing.
+// entry 0: the mx_pw_fwd / mx_bgemm layout 0 / mx_pw_dgrad_bnbwd (a_mode 3) route; entry 1: mx_pw_fwd_planes (a_mode 0),
+// mx_pw_fwd_planes_act (1), mx_pw_dgrad_bnbwd_planes (3).  Answer: family * 10000 + tile width * 10 + grid form (NtPlan, NtGrid);
+// MX_EARG for extents the entry point refuses.  Built from plan_nt / plan_nt_planes, the functions the launchers run.
+int mx_pw_fwd_plan(int entry, int a_mode, int M, int K, int N, int batch) {
+  MX_CHECK_ARG(entry == 0 || entry == 1, "pw_fwd_plan: entry must be 0 (mx_pw_fwd route) or 1 (planes route)");
+  MX_CHECK_ARG(a_mode >= 0 && a_mode <= 3, "pw_fwd_plan: bad a_mode %d", a_mode);
+  MX_CHECK_ARG(M > 0 && N > 0 && K > 0 && batch >= 1, "pw_fwd_plan: bad extents M=%d N=%d K=%d batch=%d", M, N, K, batch);
+  NtPlan p;
+  if (entry == 0) {
+    MX_CHECK_ARG(K % 4 == 0, "pw_fwd_plan: K=%d must be a multiple of 4", K);
+    p = plan_nt(a_mode, M, N, K, batch);
+  } else {
+    MX_CHECK_ARG(a_mode != MX_AFFINE, "pw_fwd_plan: the planes route has no affine-only form");
+    MX_CHECK_ARG(batch == 1, "pw_fwd_plan: the planes route is not batched");
+    MX_CHECK_ARG(K % (a_mode == MX_PLAIN ? 16 : 32) == 0, "pw_fwd_plan: K=%d must be a multiple of %d on the planes route with a_mode %d",
+                 K, a_mode == MX_PLAIN ? 16 : 32, a_mode);
+    p = plan_nt_planes(a_mode, M, N, K, batch);
+  }
+  return p.family * 10000 + p.bn * 10 + p.grid.form;
 }
 
 // number of partial-statistics rows mx_pw_fwd writes for an [M, N] output
