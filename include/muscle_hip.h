@@ -71,7 +71,7 @@ int mx_get_wgrad_kernel(void);
  * C[M,N] = A[M,K] W[N,K]^T; kind 1: weight gradient dW[M=Co,N=Ci] over K=R rows), else 0 - for measurement code. */
 int mx_gemm_uses_split(int kind, int M, int N, int K);
 /* Which kernel a forward / data-gradient GEMM C[M,N] = A'[M,K] W[N,K]^T would launch in the current mode (tests and measurement;
- * launches nothing, touches no device).  entry 0: the route of mx_pw_fwd, mx_bgemm layout 0 and mx_pw_dgrad_bnbwd (a_mode 3);
+ * launches nothing, touches no device).  entry 0: the route of mx_pw_fwd and mx_bgemm layout 0 (a_mode 0..2; 3 is MX_EARG there);
  * entry 1: the planes route, mx_pw_fwd_planes (a_mode 0), mx_pw_fwd_planes_act (a_mode 1), mx_pw_dgrad_bnbwd_planes (a_mode 3).
  * Answer = family * 10000 + tile width * 10 + grid form.  family: 1 gemm_nt_kernel (exact fp32), 2 gemm_nt_split_kernel (first
  * split generation), 3 gemm_nt_split3_kernel (weight planes).  Tile width: the columns of the 128-row tile.  Grid form: 0 = 3-D
@@ -103,12 +103,6 @@ int mx_transpose_batch(const long* table, int n, int total_tiles, void* stream);
 int mx_pw_dgrad(const float* G, const float* W, float* dX, int M, int K, int N, int ldg, int ldx,
                 const float* residual, void* stream);
 
-/* mx_pw_dgrad against Wt = W^T with the BatchNorm backward apply (mx_bn_bwd_apply, plain form) folded into the operand load:
- * dZ = coef[0][k]*G + coef[1][k]*X + coef[2][k] (coef = the [3][K] block mx_bn_bwd_finalize writes), dX = dZ * Wt^T (+ residual);
- * dZ [M, ldg] is also WRITTEN, for the weight gradient.  dZ must not alias G or X. */
-int mx_pw_dgrad_bnbwd(const float* G, const float* X, const float* coef, const float* Wt, float* dX, float* dZ, int M, int K, int N,
-                      int ldg, int ldx, const float* residual, void* stream);
-
 /* The project convolution's forward GEMM (model.py:83-86) with its operand prologue in the second-generation split kernel:
  * C[M,N] = (swish(scale[k]*A[m,k] + shift[k]) * gate[m / rows_per_sample, k]) * W[N,K]^T, W given as its pre-split image; statistics as
  * mx_pw_fwd.  K % 32 == 0.  mx_pw_fwd_act_uses_planes: 1 where the engine should take it (narrow outputs of the HBM-bound stages). */
@@ -117,27 +111,16 @@ int mx_pw_fwd_planes_act(const float* A, const float* scale, const float* shift,
                          const void* Wplanes, float* C, int M, int K, int N, int lda, int ldc, float* stats, void* stream);
 
 /* The BatchNorm-0 backward apply dZ = c1*G + c2*X + c3 (model.py:45 backward; coef = [3][K] as mx_bn_bwd_finalize leaves it) folded into
- * BOTH consumers of dZ in split arithmetic, so that dZ is never written (round 4):
+ * BOTH consumers of dZ, so that dZ is never written, where both are HBM-bound (stages 1-2):
  *   mx_pw_dgrad_bnbwd_planes: dX[M,N] = dZ[M,K] * Wt[N,K]^T (+residual), Wt given as its pre-split image (mx_pw_planes_batch);
- *   mx_pw_wgrad_tile_bnbwd:   dW[Co,Ci] += dZ[R,Co]^T X[R,Ci] (G, G2 = the BatchNorm input, [R, ldg]); scratch = mx_pw_wgrad_tile_ws(R,Co,Ci,0);
- *                             shapes: mx_pw_wgrad_tile_bnbwd_ok (1 = the split-arithmetic tiled kernel takes it in the current mode). */
+ *   mx_pw_wgrad_small_bnbwd:  dW[Co,Ci] += dZ[R,Co]^T X[R,Ci] (G, G2 = the BatchNorm input, [R, ldg]) in the small-output weight-gradient
+ *                             kernel (192 x 32, 288 x 48); scratch = mx_pw_wgrad_small_ws(R,Co,Ci,0); shapes: mx_pw_wgrad_small_bnbwd_ok.
+ * (The same fold into the first-generation data-gradient GEMM and into the tiled split weight gradient was measured slower and removed.) */
 int mx_pw_dgrad_bnbwd_planes(const float* G, const float* X, const float* coef, const void* WtPlanes, float* dX, int M, int K, int N,
                              int ldg, int ldx, const float* residual, void* stream);
-int mx_pw_wgrad_tile_bnbwd_ok(int R, int Co, int Ci);
-/* the same fold in the small-output weight-gradient kernel (stages 1-2: 192 x 32, 288 x 48; HBM-bound, so dropping the pass that
- * wrote dZ is a net saving there); scratch = mx_pw_wgrad_small_ws(R,Co,Ci,0) */
 int mx_pw_wgrad_small_bnbwd_ok(int R, int Co, int Ci);
 int mx_pw_wgrad_small_bnbwd(const float* G, const float* G2, const float* coef, const float* X, float* dW, int R, int Co, int Ci,
                             int ldg, int ldx, void* ws, long ws_bytes, void* stream);
-int mx_pw_wgrad_tile_bnbwd(const float* G, const float* G2, const float* coef, const float* X, float* dW, int R, int Co, int Ci,
-                           int ldg, int ldx, void* ws, long ws_bytes, void* stream);
-/* Round 5: the fold on the weight-gradient side ONLY.  The weight gradient of the expand convolution (backward of model.py:77) runs
- * first; the loader waves of its wave-specialised kernel form dZ = c1*G + c2*G2 + c3 and also STORE it (dz [R, ldg], not aliasing G or
- * G2), and the data gradient then reads that materialised dZ like before: the apply pass mx_bn_bwd_apply (2 reads + 1 write of the
- * Cexp-wide tensors) is not launched, and no matrix wave carries a second operand stream.  _ok: 1 where the kernel takes the shape. */
-int mx_pw_wgrad_tile_bnbwd_dz_ok(int R, int Co, int Ci, int ldg, int ldx);
-int mx_pw_wgrad_tile_bnbwd_dz(const float* G, const float* G2, const float* coef, const float* X, float* dW, float* dz, int R, int Co,
-                              int Ci, int ldg, int ldx, void* ws, long ws_bytes, void* stream);
 
 /* dW[Co,Ci] += G[R,Co]^T * X'[R,Ci]: weight gradient, general kernel (the shapes the two below do not take).  The R pixel
  * rows are split into slices; with more than one slice each adds into its own partial matrix in `ws` (mx_pw_wgrad_ws bytes)

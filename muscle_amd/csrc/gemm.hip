@@ -37,7 +37,7 @@ struct GemmArgs {
   int xcd_nt;               // > 0: 1-D grid, the xcd_nt N tiles of an M tile run back to back on one XCD (see kernel)
   int mt, zt;               // M tiles, reduction slices (for the 1-D grids)
   unsigned long long* stamps;   // diagnostic builds only (tools/hip/gemm_lab.hip); null in the library
-  float* a_out;             // MX_BNBWD: the prologue's result [M, lda] is also written here (by the N tile 0 workgroups)
+  float* a_out;             // gemm_nt_kernel's MX_BNBWD branches only (not instantiated, see there); no launch sets it
   float* ws;                // TN: scratch for the per-slice partial matrices [slices][M][N]
 };
 
@@ -549,6 +549,10 @@ static __device__ __forceinline__ float4 nt_prologue(float4 v, float4 sc, float4
 constexpr int gemm_nt_waves(int acc) { return acc <= 48 ? 4 : acc <= 64 ? 3 : 2; }
 
 // ---- streaming kernel: one tile per workgroup, K in 16-wide slabs, double-buffered -----------------------------------
+// AMODE is MX_PLAIN, MX_BNACT or MX_AFFINE.  The MX_BNBWD form (the BatchNorm backward apply folded into this kernel's operand load, dZ
+// stored through GemmArgs::a_out) was measured slower and is no longer instantiated or reachable; its branches stay in the source because
+// deleting them, dead as they are, exchanges the two factors of one v_pk_fma_f32 in each of the seven <MX_AFFINE> instantiations
+// (profiles/fold_trim_build.txt).  Taking them out belongs to a change that measures those kernels.
 template <int WM, int WN, int TM, int TN, int AMODE>
 __global__ __launch_bounds__(256, gemm_nt_waves(TM * TN * 4 + (AMODE == MX_BNBWD ? 16 : 0))) void gemm_nt_kernel(GemmArgs g) {
   constexpr int BM = WM * TM * 16, BN = WN * TN * 16, LS = 20;
@@ -1302,10 +1306,10 @@ static int pick_nt_cfg(int M, int N) {
 // bn = the tile width; cfg = the index into kNtCfgs (family 1 only); grid as above.
 struct NtPlan { int family, bn, cfg; NtGrid grid; };
 
-// the gemm_common(L_NT) route (mx_pw_fwd, mx_bgemm layout 0, mx_pw_dgrad_bnbwd)
-static NtPlan plan_nt(int a_mode, int M, int N, int K, int batch) {
+// the gemm_common(L_NT) route (mx_pw_fwd, mx_bgemm layout 0); the operand prologue does not change the plan
+static NtPlan plan_nt(int M, int N, int K, int batch) {
   NtPlan p{};
-  if (a_mode != MX_BNBWD && nt_uses_split(N, K)) {     // MFMA-bound shapes only: K and N large enough, <= 26 % padded columns
+  if (nt_uses_split(N, K)) {    // MFMA-bound shapes only: K and N large enough, <= 26 % padded columns
     p.family = 2;
     p.bn = nt_split_width(M, N, K, batch);
   } else {
@@ -1377,13 +1381,12 @@ static void launch_nt(const GemmArgs& g, const NtPlan& p, int batch, hipStream_t
   switch (g.a.mode) {
     case MX_PLAIN: hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, TM, TN, MX_PLAIN>), grid, dim3(256), 0, st, a); break;
     case MX_BNACT: hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, TM, TN, MX_BNACT>), grid, dim3(256), 0, st, a); break;
-    case MX_BNBWD: hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, TM, TN, MX_BNBWD>), grid, dim3(256), 0, st, a); break;
     default: hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, TM, TN, MX_AFFINE>), grid, dim3(256), 0, st, a); break;
   }
 }
 
 static void dispatch_nt(const GemmArgs& g, int batch, hipStream_t st) {
-  const NtPlan p = plan_nt(g.a.mode, g.M, g.N, g.K, batch);
+  const NtPlan p = plan_nt(g.M, g.N, g.K, batch);
   if (p.family == 2) {
     if (p.bn == 64) launch_nt_split_t<1>(g, p, batch, st);
     else launch_nt_split_t<2>(g, p, batch, st);
@@ -1403,7 +1406,7 @@ static void dispatch_nt(const GemmArgs& g, int batch, hipStream_t st) {
 static int check_operand(const MxOperand& o, const char* nm) {
   MX_CHECK_ARG(o.p != nullptr, "gemm: operand %s is null", nm);
   MX_CHECK_ARG(((uintptr_t)o.p & 15) == 0, "gemm: operand %s not 16-byte aligned", nm);
-  MX_CHECK_ARG(o.mode >= 0 && o.mode <= 3, "gemm: operand %s bad mode %d", nm, o.mode);
+  MX_CHECK_ARG(o.mode >= MX_PLAIN && o.mode <= MX_AFFINE, "gemm: operand %s bad mode %d", nm, o.mode);
   if (o.mode != MX_PLAIN) {
     MX_CHECK_ARG(o.c1 && o.c2, "gemm: operand %s needs scale/shift", nm);
     MX_CHECK_ARG(o.rps > 0, "gemm: operand %s rows_per_sample must be > 0", nm);
@@ -1654,17 +1657,17 @@ int mx_gemm_uses_split(int kind, int M, int N, int K) {
 }
 
 // Which kernel a forward / data-gradient GEMM C[M,N] = A'[M,K] W[N,K]^T would launch in the current arithmetic mode; launches nothing.
-// entry 0: the mx_pw_fwd / mx_bgemm layout 0 / mx_pw_dgrad_bnbwd (a_mode 3) route; entry 1: mx_pw_fwd_planes (a_mode 0),
+// entry 0: the mx_pw_fwd / mx_bgemm layout 0 route (a_mode 0..2); entry 1: mx_pw_fwd_planes (a_mode 0),
 // mx_pw_fwd_planes_act (1), mx_pw_dgrad_bnbwd_planes (3).  Answer: family * 10000 + tile width * 10 + grid form (NtPlan, NtGrid);
 // MX_EARG for extents the entry point refuses.  Built from plan_nt / plan_nt_planes, the functions the launchers run.
 int mx_pw_fwd_plan(int entry, int a_mode, int M, int K, int N, int batch) {
   MX_CHECK_ARG(entry == 0 || entry == 1, "pw_fwd_plan: entry must be 0 (mx_pw_fwd route) or 1 (planes route)");
-  MX_CHECK_ARG(a_mode >= 0 && a_mode <= 3, "pw_fwd_plan: bad a_mode %d", a_mode);
+  MX_CHECK_ARG(a_mode >= 0 && a_mode <= (entry == 0 ? MX_AFFINE : MX_BNBWD), "pw_fwd_plan: bad a_mode %d", a_mode);
   MX_CHECK_ARG(M > 0 && N > 0 && K > 0 && batch >= 1, "pw_fwd_plan: bad extents M=%d N=%d K=%d batch=%d", M, N, K, batch);
   NtPlan p;
   if (entry == 0) {
     MX_CHECK_ARG(K % 4 == 0, "pw_fwd_plan: K=%d must be a multiple of 4", K);
-    p = plan_nt(a_mode, M, N, K, batch);
+    p = plan_nt(M, N, K, batch);
   } else {
     MX_CHECK_ARG(a_mode != MX_AFFINE, "pw_fwd_plan: the planes route has no affine-only form");
     MX_CHECK_ARG(batch == 1, "pw_fwd_plan: the planes route is not batched");
@@ -1704,22 +1707,6 @@ int mx_pw_dgrad(const float* G, const float* W, float* dX, int M, int K, int N, 
   g.c = dX; g.M = M; g.N = N; g.K = K; g.lda = ldg; g.ldb = N; g.ldc = ldx;
   g.residual = residual;
   return gemm_common(L_NN, g, 1, (hipStream_t)stream);
-}
-
-// Data gradient with the BatchNorm backward apply folded into its operand load: dZ = c1*G + c2*X + c3 per channel (coef =
-// [3][K]), dX[M,N] = dZ[M,K] * Wt[N,K]^T (+ residual); dZ [M, ldg] is ALSO written (the weight gradient reads it).
-int mx_pw_dgrad_bnbwd(const float* G, const float* X, const float* coef, const float* Wt, float* dX, float* dZ, int M, int K, int N,
-                      int ldg, int ldx, const float* residual, void* stream) {
-  MX_CHECK_ARG(G && X && coef && Wt && dX && dZ, "pw_dgrad_bnbwd: null pointer");
-  MX_CHECK_ARG(dZ != G && dZ != X, "pw_dgrad_bnbwd: dZ must not alias G or X (other N tiles still read them)");
-  MX_CHECK_ARG((((uintptr_t)X | (uintptr_t)dZ | (uintptr_t)coef) & 15) == 0 && K % 4 == 0, "pw_dgrad_bnbwd: alignment");
-  GemmArgs g{};
-  g.a = MxOperand{G, coef, coef + K, X, MX_BNBWD, 1};
-  g.b = MxOperand{Wt, nullptr, nullptr, nullptr, MX_PLAIN, 1};
-  g.c = dX; g.M = M; g.N = N; g.K = K; g.lda = ldg; g.ldb = K; g.ldc = ldx;
-  g.residual = residual;
-  g.a_out = dZ;
-  return gemm_common(L_NT, g, 1, (hipStream_t)stream);
 }
 
 // bytes of scratch mx_pw_wgrad needs for this shape (0: a single reduction slice adds straight into dW)

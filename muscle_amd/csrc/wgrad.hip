@@ -412,9 +412,13 @@ struct WtArgs {
   int accumulate;          // groups == 1: part == dW, add instead of store
   int total;               // number of workgroup ids (8 * ceil(groups / 8) * tiles)
   int order;               // 0: XCD-aware (tiles of a group on one XCD); 1: group-major; 2: tile-major
-  const float* G2;         // wgrad_split_kernel<*, true>: the G operand is c1*G + c2*G2 + c3 per column (BatchNorm backward apply
-  const float* gcoef;      //   folded into the load; gcoef = [3][Co]); G2 shares G's leading dimension
-  float* dz;               // wgrad_split_ws_kernel<true> only: if set, that operand is also WRITTEN here ([R, ldg]; by the ci-tile-0 items)
+  // Not set by any launch since the BatchNorm folds into the tiled kernels were removed.  G2 / gcoef are read only by the GBN branches
+  // of wgrad_split_kernel, which are no longer instantiated (see there); `reserved` stood for the stored dZ.  All three keep
+  // sizeof(WtArgs) at 128 bytes: the implicit kernel arguments follow the struct, and with them 24 bytes lower wgrad_tile_kernel's scalar
+  // argument loads pair up differently and its whole instruction stream is rescheduled (profiles/fold_trim_build.txt).
+  const float* G2;
+  const float* gcoef;
+  void* reserved;
 };
 
 template <int TE, int TF, int XMODE>
@@ -568,9 +572,11 @@ static __device__ __forceinline__ void wsplit3_pair(float x0, float x1, unsigned
   l = __builtin_amdgcn_perm(__float_as_uint(s1), __float_as_uint(s0), 0x07060302u);
 }
 
-// GBN: the G operand is the BatchNorm backward apply c1*G + c2*G2 + c3 (per column), formed from two tensors by the loader threads
-// (their columns are fixed, so the three coefficient vectors are loaded once): the expand convolution's weight gradient reads
-// (G, e_raw) instead of a materialised dZ - see gemm_nt_split3_kernel<*, MX_BNBWD> for the data-gradient half.
+// GBN (the G operand as the BatchNorm backward apply c1*G + c2*G2 + c3, formed by the loader threads) is instantiated as false only: the
+// fold into this kernel was measured slower and its entry points are removed.  The GBN branches stay in the source because deleting them,
+// dead as they are, makes the compiler number the scale / shift registers of the <MX_BNACT> and <MX_AFFINE> instantiations differently,
+// exchange the factors of five v_pk_mul_f32 in the first and reorder v_cndmask_b32 triples in the second (profiles/fold_trim_build.txt);
+// taking them out belongs to a change that measures those two kernels.
 template <int XMODE, bool GBN>
 __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(WtArgs a) {
   constexpr int PLANE = 128 * 64;                           // bytes: [128 columns][32 k] bf16
@@ -753,14 +759,9 @@ __device__ unsigned long long* wpipe_stamps;
 #ifndef WWS_PRIO
 #define WWS_PRIO 1         // s_setprio of the MFMA waves
 #endif
-// GBN: the G operand is the BatchNorm backward apply dZ = c1*G + c2*G2 + c3 (per column), formed by the G loader waves from two tensors
-// (their vector work grows by 2 FMAs per element, their requests double); with a.dz set the items of ci tile 0 also STORE it, so the
-// data gradient that follows reads a materialised dZ and the separate 2R + 1W pass (bn_bwd_apply) is gone - unlike round 4's fold into
-// BOTH consumers, no GEMM kernel carries a second operand stream in its matrix waves.
-template <bool GBN>
 __global__ __launch_bounds__(512, 1) void wgrad_split_ws_kernel(WtArgs a) {
   constexpr int PLANE = 4 * 144 * 16, STAGE = 6 * PLANE;    // the LDS image described above wbuf_rsrc
-  constexpr int PF = WWS_PF;                                // raw row sets (the folded form holds two tensors' rows in each)
+  constexpr int PF = WWS_PF;                                // raw row sets
   extern __shared__ __attribute__((aligned(16))) unsigned char ws_smem[];      // 2 * STAGE
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int tiles = a.tiles_co * a.tiles_ci;
@@ -780,23 +781,10 @@ __global__ __launch_bounds__(512, 1) void wgrad_split_ws_kernel(WtArgs a) {
     const unsigned slab_bytes = (unsigned)(32 * ld * 4), row_bytes = (unsigned)(ld * 4);
     typedef float wf4 __attribute__((ext_vector_type(4)));
     wf4 raw[PF][8];
-    wf4 raw2[GBN ? PF : 1][8];
-    const bool isg = GBN && !isx;                            // (wave-uniform: waves 4-5)
     unsigned char* const wb = ws_smem + (isx ? 3 * PLANE : 0) + (rg * 144 + c) * 16;
 #define WWS_GLOAD(K, S)                                                                                                             \
-    _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_) {                                                                              \
-      raw[K][i_] = __builtin_bit_cast(wf4, __builtin_amdgcn_raw_buffer_load_b128(rs, vbase + (unsigned)i_ * row_bytes, (unsigned)(S) * slab_bytes, 0)); \
-      if (isg) raw2[GBN ? (K) : 0][i_] = __builtin_bit_cast(wf4, __builtin_amdgcn_raw_buffer_load_b128(rs2, vbase + (unsigned)i_ * row_bytes, (unsigned)(S) * slab_bytes, 0)); \
-    }
-    // the folded operand: dZ in place of the raw rows of slab S (rows past the group give c3 - they meet zero rows of X), stored once per G block
-#define WWS_FOLD(K, S)                                                                                                              \
-    if (isg) {                                                                                                                      \
-      _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_) {                                                                            \
-        _Pragma("unroll") for (int e_ = 0; e_ < 4; ++e_)                                                                            \
-          raw[K][i_][e_] = __builtin_fmaf(gc1[e_], raw[K][i_][e_], __builtin_fmaf(gc2[e_], raw2[GBN ? (K) : 0][i_][e_], gc3[e_])); \
-        if (wr_dz) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(wu4, raw[K][i_]), rdz, vbase + (unsigned)i_ * row_bytes, (unsigned)(S) * slab_bytes, 0); \
-      }                                                                                                                             \
-    }
+    _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_)                                                                                \
+      raw[K][i_] = __builtin_bit_cast(wf4, __builtin_amdgcn_raw_buffer_load_b128(rs, vbase + (unsigned)i_ * row_bytes, (unsigned)(S) * slab_bytes, 0));
 // (lab, round 5: the two residual subtractions of adjacent columns as ONE v_pk_add_f32 - 144 instead of 176 vector instructions per
 // slab - took the MFMA waves from 39.8 to 62.6 cycles per MFMA: packed f32 arithmetic on the partner wave stalls the matrix pipe)
 #define WWS_SPLIT(RV, STG)                                                                                                          \
@@ -813,7 +801,6 @@ __global__ __launch_bounds__(512, 1) void wgrad_split_ws_kernel(WtArgs a) {
 #define WWS_LBODY(S, RB)                                                                                                            \
     {                                                                                                                               \
       WWS_GLOAD(((RB) + PF - 1) % PF, (S) + PF)                                                                                     \
-      WWS_FOLD(RB, (S) + 1)                                                                                                         \
       WWS_SPLIT(raw[RB], ((S) + 1) & 1)                                                                                             \
       __builtin_amdgcn_s_waitcnt(0xc07f);                                                                                           \
       __builtin_amdgcn_s_barrier();                                                                                                 \
@@ -832,20 +819,10 @@ __global__ __launch_bounds__(512, 1) void wgrad_split_ws_kernel(WtArgs a) {
       // the descriptor covers exactly the group's rows: rows past its end and columns past the matrix read as zeros by the range check
       const __amdgpu_buffer_rsrc_t rs = wbuf_rsrc((isx ? a.X.p : a.G) + r_beg * ld, (long)rows * ld * 4);
       const unsigned vbase = colok ? (unsigned)((8 * rg * ld + col0) * 4) : 0x7f000000u;
-      const __amdgpu_buffer_rsrc_t rs2 = isg ? wbuf_rsrc(a.G2 + r_beg * ld, (long)rows * ld * 4) : rs;
-      const bool wr_dz = isg && a.dz != nullptr && tile % a.tiles_ci == 0;
-      const __amdgpu_buffer_rsrc_t rdz = wr_dz ? wbuf_rsrc(a.dz + r_beg * ld, (long)rows * ld * 4) : rs;
-      typedef unsigned wu4 __attribute__((ext_vector_type(4)));
-      wf4 gc1 = {1.f, 1.f, 1.f, 1.f}, gc2 = {0.f, 0.f, 0.f, 0.f}, gc3 = gc2;
-      if (isg && colok) {
-        gc1 = *reinterpret_cast<const wf4*>(a.gcoef + col0); gc2 = *reinterpret_cast<const wf4*>(a.gcoef + a.Co + col0);
-        gc3 = *reinterpret_cast<const wf4*>(a.gcoef + 2 * a.Co + col0);
-      }
       WWS_GLOAD(0, 0)
       WWS_GLOAD(1, 1)
       if (PF >= 3) { WWS_GLOAD(PF >= 3 ? 2 : 0, 2) }
       if (PF >= 4) { WWS_GLOAD(PF >= 4 ? 3 : 0, 3) }
-      WWS_FOLD(0, 0)
       WWS_SPLIT(raw[0], 0)
       __builtin_amdgcn_s_waitcnt(0xc07f);
       __builtin_amdgcn_s_barrier();
@@ -858,7 +835,6 @@ __global__ __launch_bounds__(512, 1) void wgrad_split_ws_kernel(WtArgs a) {
       }
     }
 #undef WWS_LBODY
-#undef WWS_FOLD
 #undef WWS_SPLIT
 #undef WWS_GLOAD
     return;
@@ -1163,9 +1139,8 @@ __global__ __launch_bounds__(512, 1) void wgrad_f32_ws_kernel(WtArgs a) {
 // ONE plan per launch: which kernel runs and over which tiles and row groups.  Every entry point and every query below asks it.
 enum WtKernel {
   WT_TILE_F32,       // wgrad_tile_kernel: exact fp32, any prologue, 128 / 64-wide tiles
-  WT_SPLIT,          // wgrad_split_kernel: split arithmetic, any prologue, with or without the BatchNorm fold on G
-  WT_SPLIT_WS,       // wgrad_split_ws_kernel<false>: split arithmetic, plain operands, persistent wave-specialised workgroups
-  WT_SPLIT_WS_BN,    // wgrad_split_ws_kernel<true>: the same with the BatchNorm fold on G (and, optionally, dZ written)
+  WT_SPLIT,          // wgrad_split_kernel: split arithmetic, any prologue
+  WT_SPLIT_WS,       // wgrad_split_ws_kernel: split arithmetic, plain operands, persistent wave-specialised workgroups
   WT_F32_WS,         // wgrad_f32_ws_kernel: exact fp32, plain operands, persistent wave-specialised workgroups
 };
 struct WtPlan { WtKernel kernel; int te, tf, tiles_co, tiles_ci, groups, rows_per_group; };
@@ -1219,9 +1194,9 @@ static void wt_set_groups(WtPlan* p, int R, int groups, int row_multiple) {
   p->groups = cdiv(R, p->rows_per_group);
 }
 
-// bn_fold: the G operand is c1*G + c2*G2 + c3 (mx_pw_wgrad_tile_bnbwd*).  ldg / ldx only decide whether a wave-specialised kernel can
-// address the operands; where it cannot, the launch gets the kernel and the groups of the rule below it.
-static bool wt_plan(int R, int Co, int Ci, int x_mode, bool bn_fold, int ldg, int ldx, WtPlan* p) {
+// ldg / ldx only decide whether a wave-specialised kernel can address the operands; where it cannot, the launch gets the kernel and
+// the groups of the rule below it.  The queries that take no leading dimensions ask for a contiguous launch (ldg = Co, ldx = Ci).
+static bool wt_plan(int R, int Co, int Ci, int x_mode, int ldg, int ldx, WtPlan* p) {
   if (Co % 4 || Ci % 4 || R < 1024 || (long)Co * Ci < 16384) return false;
   const bool forced = g_wgrad_groups > 0 && x_mode == MX_PLAIN;
   if (wt_use_split(Co, Ci)) {
@@ -1233,7 +1208,7 @@ static bool wt_plan(int R, int Co, int Ci, int x_mode, bool bn_fold, int ldg, in
       // (1.09 us per 32-row slab: wgrad_split_ws_kernel's own stamps)
       wt_set_groups(p, R, forced ? (g_wgrad_groups < maxg ? g_wgrad_groups : maxg) : wt_ws_groups(R, tiles, 1.09, Co, Ci), 32);
       if (wt_ws_offsets_fit(p->rows_per_group, Co, Ci, ldg, ldx)) {
-        p->kernel = bn_fold ? WT_SPLIT_WS_BN : WT_SPLIT_WS;
+        p->kernel = WT_SPLIT_WS;
         return true;
       }
     }
@@ -1314,9 +1289,6 @@ static bool wt_plan(int R, int Co, int Ci, int x_mode, bool bn_fold, int ldg, in
   return true;
 }
 
-// the plan of a contiguous launch (ldg = Co, ldx = Ci): what the queries that take no leading dimensions ask
-static bool wt_plan(int R, int Co, int Ci, int x_mode, WtPlan* p) { return wt_plan(R, Co, Ci, x_mode, false, Co, Ci, p); }
-
 template <int TE, int TF>
 static void wt_launch(const WtArgs& a, hipStream_t st) {
   const dim3 grid(a.total);
@@ -1335,18 +1307,16 @@ static int wt_launch_ws(K kernel, int lds, const WtArgs& a, hipStream_t st) {
   return MX_OK;
 }
 
-// dW[Co,Ci] += G'[R,Co]^T X'[R,Ci] by the kernel and the groups of wt_plan (G2 / gcoef: the BatchNorm fold on G; dz: that operand stored)
-static int wgrad_tile_impl(const float* G, const float* G2, const float* gcoef, const float* X, int x_mode, const float* x_scale,
-                           const float* x_shift, const float* x_gate, int rows_per_sample, float* dW, int R, int Co, int Ci, int ldg,
-                           int ldx, void* ws, long ws_bytes, void* stream, float* dz = nullptr) {
+// dW[Co,Ci] += G[R,Co]^T X'[R,Ci] by the kernel and the groups of wt_plan
+static int wgrad_tile_impl(const float* G, const float* X, int x_mode, const float* x_scale, const float* x_shift, const float* x_gate,
+                           int rows_per_sample, float* dW, int R, int Co, int Ci, int ldg, int ldx, void* ws, long ws_bytes, void* stream) {
   MX_CHECK_ARG(G && X && dW && ws, "wgrad_tile: null pointer");
   MX_CHECK_ARG(((uintptr_t)dW & 15) == 0 && ((uintptr_t)ws & 15) == 0 && ((uintptr_t)G & 15) == 0 && ((uintptr_t)X & 15) == 0,
                "wgrad_tile: pointers must be 16-byte aligned");
   MX_CHECK_ARG(ldg % 4 == 0 && ldx % 4 == 0, "wgrad_tile: leading dimensions must be multiples of 4");
   MX_CHECK_ARG(x_mode == MX_PLAIN || (x_scale && x_shift && rows_per_sample > 0), "wgrad_tile: prologue needs scale/shift");
   WtPlan p;
-  MX_CHECK_ARG(wt_plan(R, Co, Ci, x_mode, G2 != nullptr, ldg, ldx, &p), "wgrad_tile: shape R=%d Co=%d Ci=%d not supported", R, Co, Ci);
-  MX_CHECK_ARG(!dz || p.kernel == WT_SPLIT_WS_BN, "wgrad_tile_bnbwd_dz: shape R=%d Co=%d Ci=%d not taken (mx_pw_wgrad_tile_bnbwd_dz_ok)", R, Co, Ci);
+  MX_CHECK_ARG(wt_plan(R, Co, Ci, x_mode, ldg, ldx, &p), "wgrad_tile: shape R=%d Co=%d Ci=%d not supported", R, Co, Ci);
   MX_CHECK_ARG(p.groups == 1 || ws_bytes >= (long)p.groups * Co * Ci * 4, "wgrad_tile: workspace too small");
   WtArgs a{};
   a.G = G; a.X = MxOperand{X, x_scale, x_shift, x_gate, x_mode, rows_per_sample};
@@ -1354,18 +1324,15 @@ static int wgrad_tile_impl(const float* G, const float* G2, const float* gcoef, 
   a.rows_per_group = p.rows_per_group; a.groups = p.groups; a.tiles_co = p.tiles_co; a.tiles_ci = p.tiles_ci;
   a.accumulate = p.groups == 1;
   a.total = 8 * cdiv(a.groups, 8) * a.tiles_co * a.tiles_ci;  // XCD-aware workgroup ids (a.order == 0)
-  a.G2 = G2; a.gcoef = gcoef; a.dz = dz;
   a.part = a.accumulate ? dW : (float*)ws;
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid(a.total);
   constexpr int split_ws_lds = 12 * 4 * 144 * 16, f32_ws_lds = WF32_NST * 2 * 32 * 512;
   int rc = MX_OK;
   switch (p.kernel) {
-    case WT_SPLIT_WS_BN: rc = wt_launch_ws(&wgrad_split_ws_kernel<true>, split_ws_lds, a, st); break;
-    case WT_SPLIT_WS: rc = wt_launch_ws(&wgrad_split_ws_kernel<false>, split_ws_lds, a, st); break;
+    case WT_SPLIT_WS: rc = wt_launch_ws(&wgrad_split_ws_kernel, split_ws_lds, a, st); break;
     case WT_SPLIT:
-      if (a.G2) hipLaunchKernelGGL((wgrad_split_kernel<MX_PLAIN, true>), grid, dim3(256), 0, st, a);
-      else if (x_mode == MX_PLAIN) hipLaunchKernelGGL((wgrad_split_kernel<MX_PLAIN, false>), grid, dim3(256), 0, st, a);
+      if (x_mode == MX_PLAIN) hipLaunchKernelGGL((wgrad_split_kernel<MX_PLAIN, false>), grid, dim3(256), 0, st, a);
       else if (x_mode == MX_BNACT) hipLaunchKernelGGL((wgrad_split_kernel<MX_BNACT, false>), grid, dim3(256), 0, st, a);
       else hipLaunchKernelGGL((wgrad_split_kernel<MX_AFFINE, false>), grid, dim3(256), 0, st, a);
       break;
@@ -1514,7 +1481,7 @@ bool mx_wgrad_uses_split(int R, int Co, int Ci) {
   // 480 x 80 has a plan but no kernel, and goes to the tiled kernels
   if (mx_pw_wgrad_small_ws(R, Co, Ci, MX_PLAIN) > 0 || mx_pw_wgrad_small_ws(R, Co, Ci, MX_BNACT) > 0) return false;
   WtPlan p;
-  return wt_plan(R, Co, Ci, MX_PLAIN, &p) && p.kernel != WT_TILE_F32 && p.kernel != WT_F32_WS;
+  return wt_plan(R, Co, Ci, MX_PLAIN, Co, Ci, &p) && p.kernel != WT_TILE_F32 && p.kernel != WT_F32_WS;
 }
 
 // bytes of scratch mx_pw_wgrad_tile needs for contiguous operands (0 = shape not taken; a single row group accumulates straight into
@@ -1522,7 +1489,7 @@ bool mx_wgrad_uses_split(int R, int Co, int Ci) {
 // launch then reports the workspace as too small.
 long mx_pw_wgrad_tile_ws(int R, int Co, int Ci, int x_mode) {
   WtPlan p;
-  if (!wt_plan(R, Co, Ci, x_mode, &p)) return 0;
+  if (!wt_plan(R, Co, Ci, x_mode, Co, Ci, &p)) return 0;
   return p.groups > 1 ? (long)p.groups * Co * Ci * 4 : 16;
 }
 
@@ -1530,39 +1497,7 @@ long mx_pw_wgrad_tile_ws(int R, int Co, int Ci, int x_mode) {
 int mx_pw_wgrad_tile(const float* G, const float* X, int x_mode, const float* x_scale, const float* x_shift,
                      const float* x_gate, int rows_per_sample, float* dW, int R, int Co, int Ci, int ldg, int ldx,
                      void* ws, long ws_bytes, void* stream) {
-  return wgrad_tile_impl(G, nullptr, nullptr, X, x_mode, x_scale, x_shift, x_gate, rows_per_sample, dW, R, Co, Ci, ldg, ldx, ws, ws_bytes, stream);
-}
-
-// 1 when mx_pw_wgrad_tile_bnbwd takes this shape in the current mode (a split-arithmetic tiled kernel), else 0
-int mx_pw_wgrad_tile_bnbwd_ok(int R, int Co, int Ci) { return mx_wgrad_uses_split(R, Co, Ci) ? 1 : 0; }
-
-// dW[Co,Ci] += dZ[R,Co]^T X[R,Ci] with dZ = c1*G + c2*G2 + c3 per column (coef = [3][Co], as mx_bn_bwd_finalize leaves it) formed in
-// the operand load: the weight-gradient half of the BatchNorm-backward fold (mx_pw_dgrad_bnbwd_planes is the other).  Shapes:
-// mx_pw_wgrad_tile_bnbwd_ok; scratch: mx_pw_wgrad_tile_ws(R, Co, Ci, 0).
-int mx_pw_wgrad_tile_bnbwd(const float* G, const float* G2, const float* coef, const float* X, float* dW, int R, int Co, int Ci,
-                           int ldg, int ldx, void* ws, long ws_bytes, void* stream) {
-  MX_CHECK_ARG(G2 && coef, "wgrad_tile_bnbwd: null pointer");
-  MX_CHECK_ARG((((uintptr_t)G2 | (uintptr_t)coef) & 15) == 0, "wgrad_tile_bnbwd: pointers must be 16-byte aligned");
-  MX_CHECK_ARG(mx_wgrad_uses_split(R, Co, Ci), "wgrad_tile_bnbwd: shape R=%d Co=%d Ci=%d is not one the split kernels take (mx_pw_wgrad_tile_bnbwd_ok)", R, Co, Ci);
-  return wgrad_tile_impl(G, G2, coef, X, MX_PLAIN, nullptr, nullptr, nullptr, 1, dW, R, Co, Ci, ldg, ldx, ws, ws_bytes, stream);
-}
-
-// 1 when mx_pw_wgrad_tile_bnbwd_dz can leave dZ for this shape (the wave-specialised kernel takes it), else 0
-int mx_pw_wgrad_tile_bnbwd_dz_ok(int R, int Co, int Ci, int ldg, int ldx) {
-  WtPlan p;
-  return mx_wgrad_uses_split(R, Co, Ci) && wt_plan(R, Co, Ci, MX_PLAIN, true, ldg, ldx, &p) && p.kernel == WT_SPLIT_WS_BN ? 1 : 0;
-}
-
-// The same, and dZ[R, ldg] = c1*G + c2*G2 + c3 is also WRITTEN (round 5): the weight gradient runs FIRST and its loader waves leave the
-// materialised operand for the data gradient (mx_pw_fwd_planes / mx_pw_dgrad on dZ), so the separate apply pass (mx_bn_bwd_apply:
-// 2 reads + 1 write of the Cexp-wide tensors) is not launched at all.  dz must not alias G or G2.  Shapes: mx_pw_wgrad_tile_bnbwd_dz_ok.
-int mx_pw_wgrad_tile_bnbwd_dz(const float* G, const float* G2, const float* coef, const float* X, float* dW, float* dz, int R, int Co,
-                              int Ci, int ldg, int ldx, void* ws, long ws_bytes, void* stream) {
-  MX_CHECK_ARG(G2 && coef && dz, "wgrad_tile_bnbwd_dz: null pointer");
-  MX_CHECK_ARG((((uintptr_t)G2 | (uintptr_t)coef | (uintptr_t)dz) & 15) == 0, "wgrad_tile_bnbwd_dz: pointers must be 16-byte aligned");
-  MX_CHECK_ARG(dz != G && dz != G2, "wgrad_tile_bnbwd_dz: dz aliases an input (other workgroups still read it)");
-  MX_CHECK_ARG(mx_pw_wgrad_tile_bnbwd_dz_ok(R, Co, Ci, ldg, ldx), "wgrad_tile_bnbwd_dz: shape R=%d Co=%d Ci=%d not taken (mx_pw_wgrad_tile_bnbwd_dz_ok)", R, Co, Ci);
-  return wgrad_tile_impl(G, G2, coef, X, MX_PLAIN, nullptr, nullptr, nullptr, 1, dW, R, Co, Ci, ldg, ldx, ws, ws_bytes, stream, dz);
+  return wgrad_tile_impl(G, X, x_mode, x_scale, x_shift, x_gate, rows_per_sample, dW, R, Co, Ci, ldg, ldx, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -258,18 +258,6 @@ def pw_dgrad(G, W, N_in, *, residual=None, out=None, wt=None, planes=None):
     return out
 
 
-def pw_dgrad_bnbwd(G, X, coef, W, N_in, *, residual=None, wt=None):
-    """The BatchNorm backward apply dZ = c1*G + c2*X + c3 (coef [3, K], as bn_bwd_coeffs returns it) folded into the data
-    gradient dX = dZ W: returns (dX [M, N_in], dZ [M, K]) - dZ is materialised by the GEMM for the weight gradient.
-    Lab kernel: not on the engine's path."""
-    M, K = G.shape
-    out = _f32(M, N_in, device=G.device)
-    dz = torch.empty_like(G)
-    call("mx_pw_dgrad_bnbwd", ptr(G), ptr(X), ptr(coef), ptr(wt if wt is not None else transpose(W)), ptr(out), ptr(dz), M, K, N_in,
-         G.stride(0), N_in, ptr(residual), stream())
-    return out, dz
-
-
 def pw_dgrad_bnbwd_planes(G, X, coef, planes, N_in, *, residual=None):
     """dX = dZ W with dZ = c1*G + c2*X + c3 formed in the GEMM's operand load (second-generation split kernel, W^T given as its
     pre-split image); dZ is not materialised - the weight gradient folds the same expression (pw_wgrad_bnbwd)."""
@@ -282,8 +270,8 @@ def pw_dgrad_bnbwd_planes(G, X, coef, planes, N_in, *, residual=None):
 def bnbwd_fold_takes(M, K, N):
     """Which kernel can fold the BatchNorm backward apply for dZ [M, K] (data gradient against W^T [N, K], weight gradient
     dW [K, N]) in the current arithmetic: "fused" (pw_bwd_fused: both gradients from one pass, exact fp32 in every arithmetic), or,
-    given that the data gradient takes the planes kernel, "small" (the HBM-bound small-output weight-gradient kernel of stages 1-2)
-    or "tile" (the split-arithmetic tiled kernel), or None."""
+    given that the data gradient takes the planes kernel, "small" (the HBM-bound small-output weight-gradient kernel of stages 1-2),
+    or None."""
     if lib().mx_pw_bwd_small_fused_ok(M, K, N):
         return "fused"
     return bnbwd_fold_takes_split(M, K, N)
@@ -291,28 +279,21 @@ def bnbwd_fold_takes(M, K, N):
 
 @_per_mode
 def bnbwd_fold_takes_split(M, K, N):
-    """bnbwd_fold_takes without the fused kernel: "small", "tile" or None (the answer where pw_bwd_fused is switched off)."""
-    if not _planes_take(M, K, N):
-        return None
-    if lib().mx_pw_wgrad_small_bnbwd_ok(M, K, N):
+    """bnbwd_fold_takes without the fused kernel: "small" or None (the answer where pw_bwd_fused is switched off)."""
+    if _planes_take(M, K, N) and lib().mx_pw_wgrad_small_bnbwd_ok(M, K, N):
         return "small"
-    if lib().mx_pw_wgrad_small_ws(M, K, N, PLAIN) <= 0 and lib().mx_pw_wgrad_tile_bnbwd_ok(M, K, N):
-        return "tile"
     return None
 
 
 def pw_wgrad_bnbwd(G, G2, coef, X, dW):
-    """dW[Co, Ci] += (c1*G + c2*G2 + c3)[R, Co]^T X[R, Ci] through the kernel bnbwd_fold_takes names."""
+    """dW[Co, Ci] += (c1*G + c2*G2 + c3)[R, Co]^T X[R, Ci] in the small-output weight-gradient kernel (bnbwd_fold_takes == "small")."""
     R, Co = G.shape
     Ci = X.shape[1]
-    if lib().mx_pw_wgrad_small_bnbwd_ok(R, Co, Ci):
-        need = lib().mx_pw_wgrad_small_ws(R, Co, Ci, PLAIN)
-        ws = _wgrad_workspace(G.device, max(need, 16))
-        call("mx_pw_wgrad_small_bnbwd", ptr(G), ptr(G2), ptr(coef), ptr(X), ptr(dW), R, Co, Ci, G.stride(0), X.stride(0), ws.data_ptr(), ws.numel(), stream())
-        return
-    need = lib().mx_pw_wgrad_tile_ws(R, Co, Ci, PLAIN)
+    if not lib().mx_pw_wgrad_small_bnbwd_ok(R, Co, Ci):
+        raise ValueError(f"pw_wgrad_bnbwd: R={R} Co={Co} Ci={Ci} not taken (mx_pw_wgrad_small_bnbwd_ok)")
+    need = lib().mx_pw_wgrad_small_ws(R, Co, Ci, PLAIN)
     ws = _wgrad_workspace(G.device, max(need, 16))
-    call("mx_pw_wgrad_tile_bnbwd", ptr(G), ptr(G2), ptr(coef), ptr(X), ptr(dW), R, Co, Ci, G.stride(0), X.stride(0), ws.data_ptr(), ws.numel(), stream())
+    call("mx_pw_wgrad_small_bnbwd", ptr(G), ptr(G2), ptr(coef), ptr(X), ptr(dW), R, Co, Ci, G.stride(0), X.stride(0), ws.data_ptr(), ws.numel(), stream())
 
 
 def _rows_ptr(t, what):
@@ -393,26 +374,6 @@ def pw_proj_bwd_fused(dp, d_raw2d, st1: "BNState", gate, rows_per_sample, Wp, dW
     if defer is not None:
         defer(ws[:n_part].view(groups, Cout * Cexp), dW)
     return dA, pooled5
-
-
-def wgrad_bnbwd_dz_takes(R, Co, Ci) -> bool:
-    """True where `pw_wgrad_bnbwd_dz` exists: the wave-specialised split weight-gradient kernel takes dW [Co, Ci] over R rows.
-    Lab kernel: not on the engine's path."""
-    return bool(lib().mx_pw_wgrad_tile_bnbwd_dz_ok(R, Co, Ci, Co, Ci))
-
-
-def pw_wgrad_bnbwd_dz(G, G2, coef, X, dW, dz=None):
-    """dW[Co, Ci] += dZ^T X with dZ = c1*G + c2*G2 + c3 formed AND stored by the weight-gradient kernel's loader waves (round 5):
-    returns dZ [R, Co] for the data gradient that follows; mx_bn_bwd_apply is not launched.  Lab kernel: not on the engine's path."""
-    R, Co = G.shape
-    Ci = X.shape[1]
-    if dz is None:
-        dz = torch.empty_like(G)
-    need = lib().mx_pw_wgrad_tile_ws(R, Co, Ci, PLAIN)
-    ws = _wgrad_workspace(G.device, max(need, 16))
-    call("mx_pw_wgrad_tile_bnbwd_dz", ptr(G), ptr(G2), ptr(coef), ptr(X), ptr(dW), ptr(dz), R, Co, Ci, G.stride(0), X.stride(0),
-         ws.data_ptr(), ws.numel(), stream())
-    return dz
 
 
 WGRAD_TILE = os.environ.get("MUSCLE_WGRAD_TILE", "1") == "1"   # large outputs: tiled deterministic kernel (wgrad.hip) instead of the atomic TN GEMM

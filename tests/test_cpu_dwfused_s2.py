@@ -69,7 +69,7 @@ def _describe(v):
 
 class RecordingOps:
     """Every ops.* call logged with the shapes of its tensor arguments and its keyword arguments; results are empty CPU tensors of
-    the shapes the real calls return.  bnbwd_fold_takes answers "small" from 512 rows, "tile" from 128, else None."""
+    the shapes the real calls return.  bnbwd_fold_takes answers "small" from 512 rows, else None."""
     PLAIN, BNACT, AFFINE = 0, 1, 2
 
     def __init__(self):
@@ -140,7 +140,7 @@ class RecordingOps:
         return out
 
     def _r_bnbwd_fold_takes(self, M, K, N):
-        return "small" if M >= 512 else "tile" if M >= 128 else None
+        return "small" if M >= 512 else None
 
 
 def _b0_tape(N=2, S=32):

@@ -55,6 +55,24 @@ def test_the_pipelined_wgrad_kernel_is_gone(restore_settings):
         assert L.mx_set_wgrad_kernel(kern, 0) == 0 and L.mx_get_wgrad_kernel() == kern
 
 
+def test_the_lab_only_batchnorm_folds_are_gone():
+    """The BatchNorm-0 backward folds into the first-generation data-gradient GEMM and into the tiled split weight gradient (with and
+    without the stored dZ) were measured slower and removed: no entry point, no kernel.  Read from the host stubs' mangled names."""
+    import re
+    from muscle_amd import _build
+    L = _lib.lib()
+    for name in ("mx_pw_dgrad_bnbwd", "mx_pw_wgrad_tile_bnbwd", "mx_pw_wgrad_tile_bnbwd_ok", "mx_pw_wgrad_tile_bnbwd_dz",
+                 "mx_pw_wgrad_tile_bnbwd_dz_ok"):
+        assert not hasattr(L, name), name
+    for name in ("mx_pw_dgrad_bnbwd_planes", "mx_pw_wgrad_small_bnbwd", "mx_pw_wgrad_small_bnbwd_ok"):      # the live folds
+        assert hasattr(L, name), name
+    blob = open(_build.LIB, "rb").read()
+    assert b"wgrad_split_ws_kernelILb1E" not in blob and b"wgrad_split_ws_kernel" in blob
+    assert not re.search(rb"wgrad_split_kernelILi\d+ELb1EE", blob) and re.search(rb"wgrad_split_kernelILi0E", blob)
+    nt = re.findall(rb"__device_stub__gemm_nt_kernelILi\d+ELi\d+ELi\d+ELi\d+ELi(\d+)EE", blob)
+    assert nt and b"3" not in set(nt), sorted(set(nt))
+
+
 def test_only_the_gemm_kernels_a_planner_can_select_are_compiled():
     """The built library holds the first-generation gemm_kernel for exactly the (layout, tile) pairs its dispatch can reach,
     no 128 x 256 split tile, and reads no tile override from the environment.  Read from the host stubs' mangled names."""

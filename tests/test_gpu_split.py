@@ -157,12 +157,16 @@ def test_planes_gemm_with_activated_input_matches_fp64(M, K, N, rps):
     assert errs[1] <= 1.5 * errs[0] + 2e-7 * scale_, errs        # the planes kernel is as close to fp64
 
 
-@pytest.mark.parametrize("M,K,N,res", [(25088, 960, 160, True), (6272, 2304, 384, False), (3001, 384, 130, True), (700, 1344, 224, False),
-                                       (401408, 288, 48, True), (200704, 192, 32, False), (100352 + 37, 288, 48, False)])   # stages 1-2: small-output kernel
+BNBWD_FOLD_SHAPES = [(25088, 960, 160, True), (6272, 2304, 384, False), (3001, 384, 130, True), (700, 1344, 224, False),
+                     (401408, 288, 48, True), (200704, 192, 32, False), (100352 + 37, 288, 48, False)]   # stages 1-2: small-output kernel
+
+
+@pytest.mark.parametrize("M,K,N,res", BNBWD_FOLD_SHAPES)
 def test_bnbwd_fold_in_both_consumers_matches_fp64(M, K, N, res):
-    """The BatchNorm backward apply dZ = c1*G + c2*X + c3 folded into BOTH consumers of dZ (mx_pw_dgrad_bnbwd_planes: the data gradient's
-    operand load; mx_pw_wgrad_tile_bnbwd: the weight gradient's G operand) against float64, beside the unfused pair (bn_bwd_apply, then
-    the same two GEMMs on the materialised dZ); bit-identical from run to run."""
+    """The BatchNorm backward apply dZ = c1*G + c2*X + c3 folded into the consumers of dZ against float64, beside the unfused pair
+    (bn_bwd_apply, then the same GEMM on the materialised dZ); bit-identical from run to run.  The data gradient's operand load
+    (mx_pw_dgrad_bnbwd_planes) is held to it at every shape; the weight gradient's G operand (mx_pw_wgrad_small_bnbwd) where
+    mx_pw_wgrad_small_bnbwd_ok takes the shape - at least three of the shapes, so that half cannot silently vanish."""
     import muscle_amd
     from muscle_amd import ops
     g = torch.Generator(device=DEV).manual_seed(M + K)
@@ -180,22 +184,25 @@ def test_bnbwd_fold_in_both_consumers_matches_fp64(M, K, N, res):
     (image,) = plan.run()
     muscle_amd.set_gemm_mode(1)
     try:
-        if ops.bnbwd_fold_takes(M, K, N) is None:
-            pytest.skip("shape not folded in mode 1")
+        assert sum(bool(ops.lib().mx_pw_wgrad_small_bnbwd_ok(m, k, n)) for m, k, n, _ in BNBWD_FOLD_SHAPES) >= 3
+        wgrad_half = bool(ops.lib().mx_pw_wgrad_small_bnbwd_ok(M, K, N))
         dz = ops.bn_bwd_apply_plain(G, X, coef, torch.empty_like(G))
         dx_ref = ops.pw_dgrad(dz, None, N, wt=Wt, planes=image, residual=R)
         dw_ref = torch.zeros(K, N, device=DEV)
-        ops.pw_wgrad(dz, Xin, dw_ref)
+        if wgrad_half:
+            ops.pw_wgrad(dz, Xin, dw_ref)
         outs = []
         for _ in range(2):
             dx = ops.pw_dgrad_bnbwd_planes(G, X, coef, image, N, residual=R)
             dw = torch.zeros(K, N, device=DEV)
-            ops.pw_wgrad_bnbwd(G, X, coef, Xin, dw)
+            if wgrad_half:
+                ops.pw_wgrad_bnbwd(G, X, coef, Xin, dw)
             outs.append((dx, dw))
     finally:
         muscle_amd.set_gemm_mode(0)
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
-    for got, ref, want in ((outs[0][0], dx_ref, want_dx), (outs[0][1], dw_ref, want_dw)):
+    halves = [(outs[0][0], dx_ref, want_dx)] + ([(outs[0][1], dw_ref, want_dw)] if wgrad_half else [])
+    for got, ref, want in halves:
         scale = float(want.abs().max())
         e_got, e_ref = float((got.double() - want).abs().max()), float((ref.double() - want).abs().max())
         assert e_got <= 1.5 * e_ref + 3e-7 * scale, (e_got, e_ref, scale)
@@ -324,45 +331,3 @@ def test_wgrad_kernels_of_round_5_equal_the_first_split_kernel_bit_for_bit(R, Co
     assert torch.equal(outs[0], outs[1])
     ref = base.double() + G.double().t() @ X.double()
     assert (outs[1].double() - ref).abs().max().item() <= 3e-5 * ref.abs().max().item()
-
-
-@pytest.mark.parametrize("M,K,N", [(25088, 960, 160), (12544 + 5, 2304, 384), (6272, 1344, 224), (3136 * 3, 3840, 640)])
-def test_wgrad_side_fold_leaves_dz_for_the_data_gradient(M, K, N):
-    """Round 5's form of the BatchNorm-backward fold: mx_pw_wgrad_tile_bnbwd_dz forms dZ = c1*G + c2*X + c3 in the loader waves of the
-    weight-gradient kernel, uses it and STORES it; the data gradient then reads the stored dZ.  Held to the unfused pair (bn_bwd_apply,
-    then the plain weight gradient) and to float64: dZ itself to one rounding of its three terms, dW like the unfused kernel; the rows
-    past a ragged end and the padded tile columns leave nothing behind; bit-identical from run to run."""
-    import muscle_amd
-    from muscle_amd import ops
-    g = torch.Generator(device=DEV).manual_seed(M + N)
-    G = torch.randn(M, K, device=DEV, generator=g)
-    X = torch.randn(M, K, device=DEV, generator=g)
-    coef = torch.stack([torch.rand(K, device=DEV, generator=g) + 0.5, torch.randn(K, device=DEV, generator=g) * 0.3,
-                        torch.randn(K, device=DEV, generator=g) * 0.1]).contiguous()
-    Xin = torch.randn(M, N, device=DEV, generator=g)
-    dz64 = coef[0].double() * G.double() + coef[1].double() * X.double() + coef[2].double()
-    want_dw = dz64.t() @ Xin.double()
-    muscle_amd.set_gemm_mode(1)
-    try:
-        if not ops.wgrad_bnbwd_dz_takes(M, K, N):
-            pytest.skip("shape not taken by the wave-specialised kernel in mode 1")
-        dz_ref = ops.bn_bwd_apply_plain(G, X, coef, torch.empty_like(G))
-        dw_ref = torch.zeros(K, N, device=DEV)
-        ops.pw_wgrad(dz_ref, Xin, dw_ref)
-        outs = []
-        for _ in range(2):
-            dw = torch.zeros(K, N, device=DEV)
-            dz = torch.full_like(G, float("nan"))                      # every element must be written
-            ops.pw_wgrad_bnbwd_dz(G, X, coef, Xin, dw, dz)
-            outs.append((dz, dw))
-    finally:
-        muscle_amd.set_gemm_mode(0)
-    assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
-    dz, dw = outs[0]
-    assert torch.isfinite(dz).all()
-    mag = (coef[0].abs() * G.abs() + coef[1].abs() * X.abs() + coef[2].abs()).double()
-    assert float(((dz.double() - dz64).abs() / mag).max()) <= 2.0 * 2 ** -24            # two fused roundings at most
-    assert float((dz - dz_ref).abs().max()) <= 4e-7 * float(dz64.abs().max())
-    scale = float(want_dw.abs().max())
-    e_got, e_ref = float((dw.double() - want_dw).abs().max()), float((dw_ref.double() - want_dw).abs().max())
-    assert e_got <= 1.5 * e_ref + 3e-7 * scale, (e_got, e_ref, scale)

@@ -40,8 +40,6 @@ QUERIES = {
     "mx_pw_wgrad_tile_ws": lambda r, a, b, x: (r, b, a, x),
     "mx_wgrad_uses_split": lambda r, a, b, x: (r, b, a),
     "mx_pw_wgrad_small_bnbwd_ok": lambda r, a, b, x: (r, b, a),
-    "mx_pw_wgrad_tile_bnbwd_ok": lambda r, a, b, x: (r, b, a),
-    "mx_pw_wgrad_tile_bnbwd_dz_ok": lambda r, a, b, x: (r, b, a, b, a),
 }
 WITH_X_MODE = ("mx_pw_wgrad_small_ws", "mx_pw_wgrad_tile_ws")          # the only queries that take x_mode
 
