@@ -497,6 +497,27 @@ int mx_irn_walk_weights(const float* edge, int h, int w, int radius, const int* 
 long mx_irn_walk_ws(int C, int n);                                       /* < 0: bad arguments */
 int mx_irn_walk(const float* x, const float* edge, const float* W, const double* cs, int h, int w, int radius, const int* pcoord,
                 const int* poff, const int* plen, int nd, int C, int steps, double* state_a, double* state_b, float* rw, void* stream);
+/* mx_irn_walk that also hands out the states it passes through (src/indexing.py:116-147 for several exp_times at the cost of
+ * the largest): snap[ns] int32 in HOST memory (read before return), 1 <= snap[0], strictly ascending, snap[ns-1] <= 4096,
+ * ns <= 13; snap[ns-1] steps are run and at step snap[i] the fp64 state is written together with its fp32 rounding,
+ * rw[i][C][n].  Snapshot i equals mx_irn_walk(..., steps = snap[i]) bit for bit: the same per-pixel arithmetic (one device
+ * function), the fp64 quotient rounded once.  Everything else as mx_irn_walk. */
+int mx_irn_walk_snap(const float* x, const float* edge, const float* W, const double* cs, int h, int w, int radius, const int* pcoord,
+                     const int* poff, const int* plen, int nd, int C, const int* snap, int ns, double* state_a, double* state_b,
+                     float* rw, void* stream);
+/* The label step of infer_irn.py:76-92 for E walk results and ALL thresholds at once, counted as src/evaluation.py:36-50
+ * (input_type='png') counts: counts[e][t][k][0..2] += the (TP, P, T) mx_seg_confusion gives for the label map that
+ * mx_irn_finish(rw[e], ..., bg_thres = thresholds[t]) writes, integer for integer; no label map is written.
+ * rw fp32 [E][Kp][h][w]: the maps of the Kp channels present, channel keys[j] + 1 of the label (every other channel is exactly
+ * 0 and never beats a threshold >= 0); keys int32 [Kp] ascending in 0..K-2; Kp = 0 (rw, keys may be NULL): background
+ * everywhere.  gt uint8 [H,W] (255 = ignore, K..254 count towards P only, as mx_seg_confusion); thresholds fp32 [nt] ascending
+ * and >= 0, nt <= 64; 2 <= K <= 24; E <= 13; H <= 4h, W <= 4w.  vmax uint32 [E]: the bits of the maximum each rw[e] is divided
+ * by - the max_scratch word of mx_irn_up_max / mx_irn_finish run on the full [K-1][h][w] stack (that kernel's rounding depends
+ * on its launch geometry, so the word is taken from it, not recomputed), or a stored CompactSoft vmax; 0 gives NaN values:
+ * background at every threshold.  A tie value == threshold is background.  One launch, snapshot = blockIdx.y; per pixel at
+ * most three LDS integer atomics whatever nt (the bin #{t < best value}, as mx_camdict_confusion); no floating-point atomics. */
+int mx_irn_sweep_confusion(const float* rw, int E, int Kp, const int* keys, int h, int w, const unsigned char* gt, int H, int W,
+                           const float* thresholds, int nt, int K, const unsigned* vmax, long long* counts, void* stream);
 
 /* ---- per-epoch rapid evaluation (train_mcl.py:286-318 + src/evaluation.py:19-52), one image:
  * for each threshold t: predict = argmax_k [t, half(pred_k*label_k)] (first maximum wins); over pixels with gt < 255:

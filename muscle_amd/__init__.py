@@ -32,6 +32,8 @@ from .ins_seg import (InstanceLabels, cluster_centroids, connected_components, f
 
 _INS_EVAL = ("InsSegEval", "voc_instances", "pair_table", "mask_iou", "label_pair_counts", "mask_pair_counts")
 
+_IRN_SWEEP = ("IrnSweep",)
+
 
 def __getattr__(name):
     # instance-segmentation evaluation (script: muscle_amd.ins_eval).  Resolved on first use, so that `python -m muscle_amd.ins_eval`
@@ -39,4 +41,7 @@ def __getattr__(name):
     if name in _INS_EVAL:
         from . import ins_eval
         return getattr(ins_eval, name)
+    if name in _IRN_SWEEP:                       # the infer_irn grid sweep (script: muscle_amd.irn_sweep), resolved the same way
+        from . import irn_sweep
+        return getattr(irn_sweep, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -7,6 +7,8 @@
 // entries); the column sums, the state and every per-pixel sum are fp64: with fp32 state the 2^exp_times renormalised
 // steps accumulate more error than the dense path's exp_times squarings do ("IRN random-walk propagation").
 // Every sum runs in one fixed order, contraction off, no atomics: tests/irn_walk_ref.py restates it operation for operation.
+// mx_irn_walk_snap is the same walk that also writes the states at listed step counts (muscle_amd/irn_sweep.py): one device
+// function holds the per-pixel arithmetic, so a snapshot has the bits of a separate walk of as many steps.
 #include "common.h"
 
 #define IRN_WALK_MAX_ND 1024      // directions whose (dy, dx) a step keeps in LDS: radius 5 has 34, radius 16 has 394
@@ -68,20 +70,14 @@ __global__ __launch_bounds__(256) void irn_walk_init_kernel(const float* __restr
   v[(long)c * n + j] = (double)(x[(long)c * n + j] * (1.0f - edge[j]));
 }
 
-// one step for one (pixel, channel); `out32` != null on the last step.  The (dy, dx) of every direction go to LDS first.
-__global__ __launch_bounds__(256) void irn_walk_step_kernel(const double* __restrict__ v, const float* __restrict__ W,
-                                                            const double* __restrict__ cs, int h, int w,
-                                                            const int* __restrict__ pcoord, const int* __restrict__ poff, int nd,
-                                                            double* __restrict__ out, float* __restrict__ out32) {
+// One step's value for pixel j of one channel (vc = that channel's state): the per-pixel arithmetic, shared by the two step
+// kernels so that a snapshot and a separate walk of as many steps cannot drift apart.  sdy / sdx: the (dy, dx) of every direction.
+__device__ __forceinline__ double irn_walk_step_value(const double* __restrict__ vc, const float* __restrict__ W,
+                                                      const double* __restrict__ cs, int h, int w, int j, const int* sdy,
+                                                      const int* sdx, int nd) {
 #pragma clang fp contract(off)
-  __shared__ int sdy[IRN_WALK_MAX_ND], sdx[IRN_WALK_MAX_ND];
-  for (int d = threadIdx.x; d < nd; d += 256) { sdy[d] = pcoord[2 * poff[d]]; sdx[d] = pcoord[2 * poff[d] + 1]; }
-  __syncthreads();
   const int n = h * w;
-  const int j = blockIdx.x * 256 + threadIdx.x;
-  if (j >= n) return;
   const int y = j / w, x = j - y * w;
-  const double* vc = v + (long)blockIdx.y * n;
   double s = vc[j];
   // A tap outside the image reads pixel j instead and is dropped by the select: no branch, so the loads of several directions
   // are in flight together; the additions stay in the one order.
@@ -98,9 +94,40 @@ __global__ __launch_bounds__(256) void irn_walk_step_kernel(const double* __rest
     const double sb = s + vb * wb;
     s = bok ? sb : s;
   }
-  s = s / cs[j];
+  return s / cs[j];
+}
+
+// one step for one (pixel, channel); `out32` != null on the last step.  The (dy, dx) of every direction go to LDS first.
+__global__ __launch_bounds__(256) void irn_walk_step_kernel(const double* __restrict__ v, const float* __restrict__ W,
+                                                            const double* __restrict__ cs, int h, int w,
+                                                            const int* __restrict__ pcoord, const int* __restrict__ poff, int nd,
+                                                            double* __restrict__ out, float* __restrict__ out32) {
+  __shared__ int sdy[IRN_WALK_MAX_ND], sdx[IRN_WALK_MAX_ND];
+  for (int d = threadIdx.x; d < nd; d += 256) { sdy[d] = pcoord[2 * poff[d]]; sdx[d] = pcoord[2 * poff[d] + 1]; }
+  __syncthreads();
+  const int n = h * w;
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  const double s = irn_walk_step_value(v + (long)blockIdx.y * n, W, cs, h, w, j, sdy, sdx, nd);
   if (out32) out32[(long)blockIdx.y * n + j] = (float)s;
   else out[(long)blockIdx.y * n + j] = s;
+}
+
+// a snapshot step: the fp64 state the walk goes on from AND the fp32 rounding of that same value, which is what
+// irn_walk_step_kernel would have written had the walk ended here
+__global__ __launch_bounds__(256) void irn_walk_snap_kernel(const double* __restrict__ v, const float* __restrict__ W,
+                                                            const double* __restrict__ cs, int h, int w,
+                                                            const int* __restrict__ pcoord, const int* __restrict__ poff, int nd,
+                                                            double* __restrict__ out, float* __restrict__ out32) {
+  __shared__ int sdy[IRN_WALK_MAX_ND], sdx[IRN_WALK_MAX_ND];
+  for (int d = threadIdx.x; d < nd; d += 256) { sdy[d] = pcoord[2 * poff[d]]; sdx[d] = pcoord[2 * poff[d] + 1]; }
+  __syncthreads();
+  const int n = h * w;
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  const double s = irn_walk_step_value(v + (long)blockIdx.y * n, W, cs, h, w, j, sdy, sdx, nd);
+  out[(long)blockIdx.y * n + j] = s;
+  out32[(long)blockIdx.y * n + j] = (float)s;
 }
 
 extern "C" {
@@ -139,6 +166,44 @@ int mx_irn_walk(const float* x, const float* edge, const float* W, const double*
   for (int s = 0; s < steps; ++s) {
     hipLaunchKernelGGL(irn_walk_step_kernel, grid, dim3(256), 0, st, (const double*)src, W, cs, h, w, pcoord, poff, nd, dst,
                        s == steps - 1 ? rw : (float*)nullptr);
+    double* t = src; src = dst; dst = t;
+  }
+  MX_LAUNCH_CHECK();
+  return MX_OK;
+}
+
+#define IRN_WALK_MAX_SNAP 13      // exp_times 0..12
+
+// mx_irn_walk that also hands out the states it passes through: snap[ns] (host memory, read before return) ascending step counts,
+// rw [ns][C][n].  Snapshot i has the bits of mx_irn_walk(..., steps = snap[i]): the same fp64 value, rounded once.
+int mx_irn_walk_snap(const float* x, const float* edge, const float* W, const double* cs, int h, int w, int radius, const int* pcoord,
+                     const int* poff, const int* plen, int nd, int C, const int* snap, int ns, double* state_a, double* state_b,
+                     float* rw, void* stream) {
+  MX_CHECK_ARG(x && edge && W && cs && pcoord && poff && plen && snap && state_a && state_b && rw, "irn_walk_snap: null pointer");
+  MX_CHECK_ARG(ns >= 1 && ns <= IRN_WALK_MAX_SNAP, "irn_walk_snap: ns must be 1..%d (got %d)", IRN_WALK_MAX_SNAP, ns);
+  MX_CHECK_ARG(snap[0] >= 1 && snap[ns - 1] <= 4096, "irn_walk_snap: snap must lie in 1..4096 (got %d..%d)", snap[0], snap[ns - 1]);
+  for (int i = 1; i < ns; ++i)
+    MX_CHECK_ARG(snap[i] > snap[i - 1], "irn_walk_snap: snap must be strictly ascending (snap[%d]=%d after %d)", i, snap[i], snap[i - 1]);
+  MX_CHECK_ARG(radius >= 1, "irn_walk_snap: radius must be >= 1 (got %d)", radius);
+  MX_CHECK_ARG(h > 0 && w > 0 && nd > 0 && nd <= IRN_WALK_MAX_ND && C > 0 && C <= 65535 && (long)h * w * nd < (1L << 31) &&
+                   (long)h * w * C * ns < (1L << 31),
+               "irn_walk_snap: bad geometry (h=%d w=%d nd=%d C=%d ns=%d)", h, w, nd, C, ns);
+  MX_CHECK_ARG(state_a != state_b, "irn_walk_snap: the two state buffers must differ");
+  hipStream_t st = (hipStream_t)stream;
+  const int n = h * w;
+  const dim3 grid(cdiv(n, 256), C);
+  hipLaunchKernelGGL(irn_walk_init_kernel, grid, dim3(256), 0, st, x, edge, n, state_a);
+  double *src = state_a, *dst = state_b;
+  int i = 0;
+  for (int s = 1; s <= snap[ns - 1]; ++s) {
+    if (s == snap[i]) {
+      hipLaunchKernelGGL(irn_walk_snap_kernel, grid, dim3(256), 0, st, (const double*)src, W, cs, h, w, pcoord, poff, nd, dst,
+                         rw + (long)i * C * n);
+      ++i;
+    } else {
+      hipLaunchKernelGGL(irn_walk_step_kernel, grid, dim3(256), 0, st, (const double*)src, W, cs, h, w, pcoord, poff, nd, dst,
+                         (float*)nullptr);
+    }
     double* t = src; src = dst; dst = t;
   }
   MX_LAUNCH_CHECK();

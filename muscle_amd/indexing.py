@@ -11,6 +11,9 @@ propagated with one more GEMM.  For a VOC image at the IRN's 1/4 resolution (≈
 `method="stencil"` computes the same x . T^(2^exp_times) without the matrix: T has at most 2 nd + 1 non-zeros per column
 (nd = 34 one-sided search directions at radius 5), so it is applied 2^exp_times times as a stencil on an fp64 state
 (`mx_irn_walk_weights`, `mx_irn_walk`; DESIGN.md, "IRN random-walk propagation").  The dense path stays the default.
+
+`propagate_to_edge_multi` is the stencil walk for several exp_times at the cost of the largest: the states at the smaller powers
+of two are written on the way (`mx_irn_walk_snap`), each bit for bit what its own walk gives.  muscle_amd/irn_sweep.py builds on it.
 """
 from __future__ import annotations
 
@@ -99,6 +102,35 @@ def propagate_to_edge(x: torch.Tensor, edge: torch.Tensor, radius: int = 5, beta
     rw = torch.empty(C4, n4, dtype=torch.float32, device=dev)
     ops.bgemm(1, xp.view(1, C4, n4), A.view(1, n4, n4), rw.view(1, C4, n4), C4, n4, n4)
     return rw[:C, :n].reshape(C, 1, h, w)
+
+
+def check_exp_times_list(exp_times_list) -> Tuple[int, ...]:
+    """The exp_times of one multi-snapshot walk: integers in 0..12, strictly ascending (so no duplicates), at least one."""
+    ets = tuple(exp_times_list)
+    if not ets:
+        raise ValueError("exp_times_list is empty")
+    if any(isinstance(e, bool) or int(e) != e or not 0 <= e <= 12 for e in ets):
+        raise ValueError(f"exp_times_list: the stencil walk takes integer exp_times 0..12, 2^exp_times steps (got {list(ets)})")
+    if any(b <= a for a, b in zip(ets, ets[1:])):
+        raise ValueError(f"exp_times_list must be strictly ascending, without duplicates (got {list(ets)})")
+    return tuple(int(e) for e in ets)
+
+
+def propagate_to_edge_multi(x: torch.Tensor, edge: torch.Tensor, radius: int = 5, beta: float = 10,
+                            exp_times_list=(8,)) -> torch.Tensor:
+    """propagate_to_edge(method="stencil") for several exp_times from ONE walk to the largest: the walk reaches 2^e steps
+    through every smaller power of two, so the states of the smaller exp_times are snapshots on the way (mx_irn_walk_snap).
+    Returns [E,C,1,h,w]; slice i equals propagate_to_edge(x, edge, radius, beta, exp_times_list[i], method="stencil") bit for
+    bit.  Stencil only; exp_times_list: integers in 0..12, ascending, no duplicates (ValueError otherwise)."""
+    ets = check_exp_times_list(exp_times_list)
+    if not x.is_cuda or not edge.is_cuda:
+        raise MuscleHipError("propagate_to_edge_multi runs on the HIP kernels only")
+    h, w = x.shape[-2:]
+    e = edge.reshape(h, w).contiguous().float()
+    table = _path_table(radius, x.device)
+    W, cs = ops.irn_walk_weights(e, table, radius, beta)
+    rw = ops.irn_walk_snap(x.reshape(-1, h, w).contiguous().float(), e, W, cs, table, radius, [2 ** t for t in ets])
+    return rw.reshape(len(ets), -1, 1, h, w)
 
 
 def finish_semseg(rw: torch.Tensor, H: int, W: int, bg_thres: float, soft_output=False):

@@ -861,6 +861,24 @@ def irn_walk(x, edge, W, cs, table, radius, steps):
     return rw
 
 
+def irn_walk_snap(x, edge, W, cs, table, radius, snap):
+    """`irn_walk` to snap[-1] steps that also returns the states at the step counts `snap` (ascending, 1..4096, at most 13):
+    rw fp32 [len(snap),C,h,w], snapshot i bit for bit `irn_walk(..., steps=snap[i])`.  One call enqueues every launch."""
+    import ctypes
+    C, h, w = x.shape
+    pc, off, ln, nd = table
+    snap = [int(s) for s in snap]
+    nbytes = int(lib().mx_irn_walk_ws(C, h * w))
+    if nbytes < 0 or not snap:
+        raise ValueError(f"irn_walk_snap: geometry C={C} h={h} w={w} snap={snap}")
+    state = torch.empty(2, nbytes // 8, dtype=torch.float64, device=x.device)
+    rw = _f32(len(snap), C, h, w, device=x.device)
+    steps = (ctypes.c_int * len(snap))(*snap)                     # host memory: the entry reads it before it returns
+    call("mx_irn_walk_snap", ptr(x), ptr(edge), ptr(W), ptr(cs), h, w, radius, ptr(pc), ptr(off), ptr(ln), nd, C, steps, len(snap),
+         ptr(state[0]), ptr(state[1]), ptr(rw), stream())
+    return rw
+
+
 # ---- training the IRN heads (csrc/irn_train.hip) ---------------------------------------------------------------
 def irn_loss_fwd(E, D, label, table, radius):
     """E [N,H,W,lde] (column 0 = the edge logit), D [N,H,W,ldd] (columns 0,1 = the displacement), label uint8 [N,H,W], table = the
