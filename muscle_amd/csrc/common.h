@@ -86,6 +86,40 @@ __device__ __forceinline__ float wave_min(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
   return v;
 }
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// sum over the 16 lanes of a DPP row (every lane gets it): rotate-and-add, no LDS
+__device__ __forceinline__ float row16_sum(float v) {
+  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xf, 0xf, false));   // row_ror:8
+  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x124, 0xf, 0xf, false));   // row_ror:4
+  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x122, 0xf, 0xf, false));   // row_ror:2
+  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x121, 0xf, 0xf, false));   // row_ror:1
+  return v;
+}
+
+// two fp32 values -> three words of packed bf16 pairs {x1, x0}: high, middle and low 8 significand bits (the split GEMMs of gemm.hip
+// and wgrad.hip; the arithmetic is described above gemm_nt_split_kernel)
+__device__ __forceinline__ void split3_pair(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
+  const unsigned u0 = __float_as_uint(x0) & 0xffff0000u, u1 = __float_as_uint(x1) & 0xffff0000u;
+  const float r0 = x0 - __uint_as_float(u0), r1 = x1 - __uint_as_float(u1);                // exact
+  const unsigned v0 = __float_as_uint(r0) & 0xffff0000u, v1 = __float_as_uint(r1) & 0xffff0000u;
+  const float s0 = r0 - __uint_as_float(v0), s1 = r1 - __uint_as_float(v1);                // exact, <= 8 significant bits
+  h = __builtin_amdgcn_perm(u1, u0, 0x07060302u);     // {bf16(x1), bf16(x0)}: the top halves of both words
+  m = __builtin_amdgcn_perm(v1, v0, 0x07060302u);
+  l = __builtin_amdgcn_perm(__float_as_uint(s1), __float_as_uint(s0), 0x07060302u);
+}
+
+// buffer descriptor over `bytes` bytes at `base` (the weight-gradient kernels): loads past the range read as zeros
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t wbuf_rsrc(const float* base, long bytes) {
+  // wave-uniform by construction (blockIdx / wave-id only): the readfirstlanes make that provable, no waterfall loops
+  const unsigned long long p = (unsigned long long)base;
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)p), hi = __builtin_amdgcn_readfirstlane((unsigned)(p >> 32));
+  const unsigned n = __builtin_amdgcn_readfirstlane((unsigned)bytes);
+  return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)hi << 32) | lo), 0, n, 0x00020000);
+}
 
 // ---------------------------------------------------------------------------
 // Ordered cross-workgroup reductions without a second launch ("last arriver finishes").
@@ -127,8 +161,8 @@ __device__ __forceinline__ bool mx_last_arriver(unsigned* counter, unsigned tota
   return *lds_flag != 0u;
 }
 
-// BatchNorm backward finalisation of one channel from its two sums (shared by bn.hip and by the producers that finish their own
-// statistics, dwconv.hip): dgamma / dbeta (+=) and the coefficients of dX = c1*g + c2*X + c3.
+// BatchNorm backward finalisation of one channel from its two sums (bn.hip; here so that a producer kernel
+// can finish its own statistics through the same code): dgamma / dbeta (+=) and the coefficients of dX = c1*g + c2*X + c3.
 struct BnBwdFin {
   double count; const float* gamma; const float* mean; const float* rstd; int training;
   float* dgamma; float* dbeta; float* c1; float* c2; float* c3;
@@ -247,6 +281,37 @@ __device__ __forceinline__ void bil_coord_rn(int d, int in, int out, int& i0, in
   if (i0 > in - 1) i0 = in - 1;
   i1 = i0 + ((i0 < in - 1) ? 1 : 0);
   w1 = s - (float)i0;
+}
+// Source taps of the bilinear resizes.  One copy each, because a kernel and its adjoint (or a forward and the kernel that recomputes its
+// pixels) must name the same taps with the same weights:
+//   bil_coord      align_corners=True (torch upsample_bilinear2d: src = dst * (in-1)/(out-1)), contraction left to the compiler: every
+//                  caller gets w1 = fma(scale, d, -i0) with i0 from the rounded product - head.hip, dec.hip and phase2.hip agree on that
+//                  by using THIS function, not by a pragma;
+//   bil_coord_rn   (above) align_corners=True with every rounding spelt out: w1 = rn(scale*d) - i0;
+//   bil_adj_range  the destination indices whose bil_coord can name a given source index (the gather-form adjoints);
+//   halfpixel_tap  align_corners=False (half-pixel centres), rs = source pixels per destination pixel.
+// (hp_coord, hp_coord_x and bil_coord_x of head.hip differ from these on purpose; see there.)
+__device__ __forceinline__ void bil_coord(int d, int in, int out, int& i0, int& i1, float& w1) {
+  float scale = (out > 1) ? (float)(in - 1) / (float)(out - 1) : 0.f;
+  float s = scale * d;
+  i0 = (int)s;
+  if (i0 > in - 1) i0 = in - 1;
+  i1 = i0 + ((i0 < in - 1) ? 1 : 0);
+  w1 = s - i0;
+}
+__device__ __forceinline__ void bil_adj_range(int si, int in, int out, int& lo, int& hi) {
+  // scale*d in (si - 1, si + 1); one index of margin each side
+  if (out <= 1 || in <= 1) { lo = 0; hi = out - 1; return; }
+  const float inv = (float)(out - 1) / (float)(in - 1);
+  lo = max(0, (int)floorf((float)(si - 1) * inv) - 1);
+  hi = min(out - 1, (int)ceilf((float)(si + 1) * inv) + 1);
+}
+__device__ __forceinline__ void halfpixel_tap(int d, float rs, int n_src, int& i0, int& i1, float& l1) {
+  float s = rs * ((float)d + 0.5f) - 0.5f;
+  s = s < 0.f ? 0.f : s;
+  i0 = min((int)s, n_src - 1);
+  i1 = min(i0 + 1, n_src - 1);
+  l1 = s - (float)i0;
 }
 __device__ __forceinline__ float upsample_ac_value(float a00, float a01, float a10, float a11, float wy, float wx) {
   return blend_rows(lerp_a(a00, a01, wx), lerp_b(a10, a11, wx), wy);

@@ -52,23 +52,6 @@ __global__ __launch_bounds__(256) void avgpool3s2_kernel(const float* x, float* 
   }
 }
 
-__device__ __forceinline__ void bc(int d, int in, int out, int& i0, int& i1, float& w1) {
-  float scale = (out > 1) ? (float)(in - 1) / (float)(out - 1) : 0.f;
-  float s = scale * d;
-  i0 = (int)s;
-  if (i0 > in - 1) i0 = in - 1;
-  i1 = i0 + ((i0 < in - 1) ? 1 : 0);
-  w1 = s - i0;
-}
-
-// destination indices whose bilinear footprint (bc) can name source index si: scale*d in (si - 1, si + 1), one index of margin
-__device__ __forceinline__ void adj_rng(int si, int in, int out, int& lo, int& hi) {
-  if (out <= 1 || in <= 1) { lo = 0; hi = out - 1; return; }
-  const float inv = (float)(out - 1) / (float)(in - 1);
-  lo = max(0, (int)floorf((float)(si - 1) * inv) - 1);
-  hi = min(out - 1, (int)ceilf((float)(si + 1) * inv) + 1);
-}
-
 // adjoint of mx_resize_nhwc (no relu): gsrc[N,Hs,Ws,C] += W^T gdst[N,Hd,Wd,C].  Gather form: a thread owns four channels of one
 // SOURCE pixel and adds weight x gradient over the destination pixels that name it, rows then columns ascending - one adder per
 // element, same bits every run (the scatter form needed float atomics).
@@ -81,17 +64,17 @@ __global__ __launch_bounds__(256) void resize_nhwc_bwd_kernel(const float* gdst,
     const int sx = (int)(p % Ws); long q = p / Ws;
     const int sy = (int)(q % Hs), n = (int)(q / Hs);
     int ylo, yhi, xlo, xhi;
-    adj_rng(sy, Hs, Hd, ylo, yhi);
-    adj_rng(sx, Ws, Wd, xlo, xhi);
+    bil_adj_range(sy, Hs, Hd, ylo, yhi);
+    bil_adj_range(sx, Ws, Wd, xlo, xhi);
     float4 acc = make_float4(0, 0, 0, 0);
     for (int y = ylo; y <= yhi; ++y) {
       int y0, y1; float wy;
-      bc(y, Hs, Hd, y0, y1, wy);
+      bil_coord(y, Hs, Hd, y0, y1, wy);
       const float wyy = (y0 == sy ? 1.f - wy : 0.f) + ((y1 == sy && y1 != y0) ? wy : 0.f);
       if (wyy == 0.f) continue;
       for (int x = xlo; x <= xhi; ++x) {
         int x0, x1; float wx;
-        bc(x, Ws, Wd, x0, x1, wx);
+        bil_coord(x, Ws, Wd, x0, x1, wx);
         const float wxx = (x0 == sx ? 1.f - wx : 0.f) + ((x1 == sx && x1 != x0) ? wx : 0.f);
         if (wxx == 0.f) continue;
         const float4 g = ld4(gdst + (((long)n * Hd + y) * Wd + x) * C + c);
@@ -421,7 +404,7 @@ __global__ __launch_bounds__(256) void field_gather_kernel(const float* dense, i
     const int n = pts[2 * q], p = pts[2 * q + 1];
     const int y = p / W, x = p % W;
     int y0 = 0, y1 = 0, x0 = 0, x1 = 0; float wy = 0.f, wx = 0.f;
-    if (mode == 1) { bc(y, h, H, y0, y1, wy); bc(x, w, W, x0, x1, wx); }
+    if (mode == 1) { bil_coord(y, h, H, y0, y1, wy); bil_coord(x, w, W, x0, x1, wx); }
     float v[16];   // CH <= 1024
     float mxv = -INFINITY;
     int cnt = 0;
@@ -549,7 +532,7 @@ __global__ __launch_bounds__(256) void field_tile_gather_kernel(const float* gpt
     if (pts[2 * q] != n) continue;                 // (uniform: every thread reads the same words)
     const int p = pts[2 * q + 1];
     int y0, y1, x0, x1; float wy, wx;
-    bc(p / W, h, H, y0, y1, wy); bc(p % W, w, W, x0, x1, wx);
+    bil_coord(p / W, h, H, y0, y1, wy); bil_coord(p % W, w, W, x0, x1, wx);
     if (y1 < ty0 || y0 >= ty0 + FT || x1 < tx0 || x0 >= tx0 + FT) continue;
     any = true;
     const float w00 = (1.f - wy) * (1.f - wx), w01 = (x1 != x0) ? (1.f - wy) * wx : 0.f;

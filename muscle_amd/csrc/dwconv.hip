@@ -116,12 +116,9 @@ __device__ __forceinline__ void dw_stage_input(const DwArgs& a, float4* tile, in
 //   gpp == 0 (training): group g covers tiles [g tpb, (g+1) tpb) of the (sample, tile) sequence, statistics row g;
 //   gpp  > 0 (inference squeeze): a sample's tiles are cut into gpp groups that do not straddle samples; group (n, gi) parks its
 //            partial squeeze row and the last of the gpp groups to arrive adds them in group order (mx_last_arriver).
-// Software pipelining of the tile loop (tile t + 1's global loads in flight while tile t is computed; -DDW_FWD_PREFETCH=1): measured
-// in round 3 and OFF - the 40 staging registers it keeps live cost a wave per SIMD (4 -> 3), 3x3 loses 10-20 %, 5x5 gains 5-12 % on the
-// widest layers only and loses on the rest; whole step 109.0 -> 110.6 ms.  Occupancy, not intra-workgroup overlap, feeds these kernels.
-#ifndef DW_FWD_PREFETCH
-#define DW_FWD_PREFETCH 0
-#endif
+// (Software pipelining of the tile loop - tile t + 1's global loads in flight while tile t is computed - was measured in round 3 and
+// lost: the 40 staging registers it keeps live cost a wave per SIMD (4 -> 3), 3x3 loses 10-20 %, 5x5 gains 5-12 % on the widest layers
+// only and loses on the rest; whole step 109.0 -> 110.6 ms.  Occupancy, not intra-workgroup overlap, feeds these kernels.)
 // ROWS (28-wide stride-1 tiles, round 4): as in dw_bwd_fused_kernel the staged rows are pitched at 32 pixels, so one staging pass of
 // the 256 threads is one tile row - the row's address, clamp and bounds are scalar, the thread's column is fixed for the tile - and a
 // thread computes 7 pixels x 4 channels (11 tile reads per kernel row for 70 packed FMAs; 8 for 40 at 4 pixels).  The 16-wide form
@@ -157,12 +154,7 @@ __global__ __launch_bounds__(256, (TW == 28) ? 3 : 1) void dw_fwd_kernel(DwArgs 
   float4 s = make_float4(0, 0, 0, 0), sq = make_float4(0, 0, 0, 0), p = make_float4(0, 0, 0, 0);
   float4 psc = make_float4(0, 0, 0, 0), psh = psc;
   if (a.pooled && c < a.C) { psc = ld4(a.ps + c); psh = ld4(a.pb + c); }
-  // software pipeline over the tiles: tile t + 1's global loads are in flight while tile t is computed from LDS
   DwTile<K, S, TH, TW> stg;
-  if (DW_FWD_PREFETCH && t_beg < t_end) {
-    const int rem0 = (int)(t_beg % ntile);
-    stg.load(a, (int)(t_beg / ntile), (rem0 / a.tiles_x) * TH, (rem0 % a.tiles_x) * TW, c0, tid);
-  }
   for (long t = t_beg; t < t_end; ++t) {
     const int n = (int)(t / ntile), rem = (int)(t % ntile);
     const int oy0 = (rem / a.tiles_x) * TH, ox0 = (rem % a.tiles_x) * TW;
@@ -192,14 +184,10 @@ __global__ __launch_bounds__(256, (TW == 28) ? 3 : 1) void dw_fwd_kernel(DwArgs 
       }
       __syncthreads();
     } else {
-    if (!DW_FWD_PREFETCH) stg.load(a, n, oy0, ox0, c0, tid);
-    __syncthreads();                               // the previous tile's readers are done (first pass: the weights are staged)
-    stg.store(a, tile, c0, tid);
-    __syncthreads();
-    }
-    if (DW_FWD_PREFETCH && t + 1 < t_end) {
-      const int rem1 = (int)((t + 1) % ntile);
-      stg.load(a, (int)((t + 1) / ntile), (rem1 / a.tiles_x) * TH, (rem1 % a.tiles_x) * TW, c0, tid);
+      stg.load(a, n, oy0, ox0, c0, tid);
+      __syncthreads();                             // the previous tile's readers are done (first pass: the weights are staged)
+      stg.store(a, tile, c0, tid);
+      __syncthreads();
     }
     float4 acc[OX];
 #pragma unroll
@@ -457,8 +445,6 @@ struct DwFusedArgs {
   float* gx; float* dwpart; float* part;              // outputs: gX (or g*swish'), dW partial rows [groups][C*K*K], BN0 partial sums [groups][2][C]
   int N, H, W, C, pad, tiles_x, tiles_y, tiles_per_block;
   int xcd, gpp, chunks;    // xcd = 1: 1-D grid, the gpp tile groups of one (sample, channel chunk) plane run on ONE XCD (dw_fwd_kernel)
-  unsigned* fin_counters;  // non-null: the last workgroup of a channel chunk to arrive finishes the BatchNorm-0 backward statistics itself
-  BnBwdFin fin;            //   (dgamma / dbeta +=, c1 c2 c3) from the partial rows - the separate bn_reduce_finalize launch is gone
 };
 
 // Tile shapes (TH x TW output pixels per staged tile, PX consecutive pixels per thread "group", 16 groups per pass):
@@ -486,13 +472,14 @@ extern "C" int mx_dw_stamps_read(unsigned long long* host) {
 #define DW_STAMP(k) do {} while (0)
 #endif
 
-#ifndef MX_DW_STAGE_MAX
-#define MX_DW_STAGE_MAX 4
-#endif
-// float4 pairs (dA, d) a thread has in flight per staging chunk: the largest divisor of its share of the tile up to MX_DW_STAGE_MAX
-constexpr int dw_stage_depth(int per, int th) {
+// one component of the BatchNorm-1 data gradient dd of staged element k (both fused kernels): 0 outside the image, see the block comment
+#define DD1(f) dd.f = okf * (C1.f * ((vg[k].f * G.f + AD.f) * swish_gradf_(A1.f * vd[k].f + B1.f)) + C2.f * vd[k].f + C3.f);
+
+// float4 pairs (dA, d) a thread has in flight per staging chunk: the largest divisor of its share of the tile up to 4
+// (8 x 16 at 3 waves per SIMD spills above 4; 6 on the larger tiles measured within 2 % of 4, profiles/r04_knob_sweep.txt)
+constexpr int dw_stage_depth(int per) {
   int best = 1;
-  for (int c = 2; c <= (th == 8 ? 4 : MX_DW_STAGE_MAX); ++c) if (per % c == 0) best = c;   // (8 x 16 at 3 waves per SIMD spills above 4)
+  for (int c = 2; c <= 4; ++c) if (per % c == 0) best = c;
   return best;
 }
 
@@ -509,7 +496,7 @@ __global__ __launch_bounds__(256, (TH == 7) ? 3 : (K == 5 || TH != 8) ? 2 : 3) v
   constexpr bool ROWS = (TW == 28);
   constexpr int IH = TH + K - 1, IW = TW + K - 1, IWP = ROWS ? 32 : IW, TOT = IH * IWP * C4B, PER = (TOT + 255) / 256;
   static_assert(!ROWS || (IW <= 32 && PER == IH && 256 / C4B == 32), "one padded tile row per staging pass");
-  constexpr int CH = (ROWS && TH == 7) ? 4 : dw_stage_depth(PER, TH);     // (7-row tiles: 11 or 9 staged rows in chunks of 4, the last one short)
+  constexpr int CH = (ROWS && TH == 7) ? 4 : dw_stage_depth(PER);     // (7-row tiles: 11 or 9 staged rows in chunks of 4, the last one short)
   static_assert(ROWS || PER % CH == 0, "staging chunks");
   __shared__ float4 td[TOT + C4B];     // dd with halo (+ one pixel of zeros: the masked eighth slot of an odd PX reads past the last row); at the end the per-wave partial rows of dW and of the BN0 sums
   static_assert(TOT * 4 >= 4 * K * K * CB, "the per-wave partial rows reuse the staged tile");
@@ -589,7 +576,6 @@ __global__ __launch_bounds__(256, (TH == 7) ? 3 : (K == 5 || TH != 8) ? 2 : 3) v
     __syncthreads();
     // stage dd, CH float4 pairs in flight per thread; out-of-image / out-of-range elements read a clamped (valid) address and
     // are multiplied by 0
-#define DD1(f) dd.f = okf * (C1.f * ((vg[k].f * G.f + AD.f) * swish_gradf_(A1.f * vd[k].f + B1.f)) + C2.f * vd[k].f + C3.f);
     if constexpr (ROWS) {
       const int col = tid / C4B, ix = ix0 + col;
       const float colf = (col < IW && ix >= 0 && ix < a.W && cok) ? 1.f : 0.f;     // (columns IW..31 of the pitch are stored as zeros)
@@ -643,26 +629,18 @@ __global__ __launch_bounds__(256, (TH == 7) ? 3 : (K == 5 || TH != 8) ? 2 : 3) v
         }
       }
     }
-#undef DD1
     DW_STAMP(1);
     __syncthreads();
     DW_STAMP(2);
     // Compute: a thread owns 2 channels x PX consecutive pixels of one tile row per pass (4 channels x 4 pixels needs 100
     // accumulator VGPRs for K=5 and the allocator then spills; 2 x 8 needs 50 and keeps v_pk_fma_f32 over the channel pair).
     // Row ky of the kernel pairs this pixel row with dd row pyl + K-1-ky of the halo tile, for the weight gradient
-    // (times act(X) of the centre pixel) and for the data gradient (times the flipped weight) alike.  The pixels go in two
-    // halves of QX (each half: taps, then its own epilogue and stores - no accumulator survives a half), both unrolled, so
-    // every register index and every LDS offset is a constant and the odd PX's eighth slot is never computed; scheduling
-    // barriers keep the halves and the kernel rows apart (hoisted together their LDS reads spill).
+    // (times act(X) of the centre pixel) and for the data gradient (times the flipped weight) alike.  All PX pixels of a pass go
+    // in one part (taps, then the epilogue and stores - no accumulator survives a pass), fully unrolled, so every register
+    // index and every LDS offset is a constant and the odd PX's eighth slot is never computed; scheduling barriers keep the
+    // kernel rows apart (hoisted together their LDS reads spill).
     const float2* td2 = reinterpret_cast<const float2*>(td);
     const float2 A0 = *reinterpret_cast<const float2*>(cst + 5 * CB + 2 * c2), B0 = *reinterpret_cast<const float2*>(cst + 6 * CB + 2 * c2);
-#ifndef MX_DW_NH
-#define MX_DW_NH 1
-#endif
-    constexpr int NH = MX_DW_NH;                   // the PX pixels go in NH parts of QX
-    constexpr int QX = (PX + NH - 1) / NH;
-    constexpr bool UNROLL_H = true;
-    constexpr int HU = NH;
 #pragma unroll 1
     for (int gi = 0; gi < NG; ++gi) {
       const int grp = pq + 16 * gi;
@@ -679,26 +657,26 @@ __global__ __launch_bounds__(256, (TH == 7) ? 3 : (K == 5 || TH != 8) ? 2 : 3) v
       const bool rok = gok && cok2 && oy < a.H;
       const float2* tdg = td2 + (pyl * IWP + pxl) * C2B + c2;
       const long rowoff = (((long)n * a.H + min(oy, a.H - 1)) * a.W + ox0 + pxl) * a.C + cc2;
-      float2 cur[QX];                              // the centre pixels of the current half
-#pragma unroll
-      for (int o = 0; o < QX; ++o) cur[o] = xr[o];
       // a wave none of whose lanes has a pixel group in this pass (14 x 28: 56 groups in passes of 16 - waves 2 and 3 of the fourth) leaves
       // its issue slots to the other workgroup's waves instead of running 500 masked instructions
-      const bool wave_has_work = __builtin_amdgcn_ballot_w64(rok) != 0;
-#pragma unroll HU
-      for (int h = 0; h < (wave_has_work ? NH : 0); ++h) {
-        __builtin_amdgcn_sched_barrier(0);
-        const int pxh = h * QX;
-        int wlh = c2;                              // opaque per half: the K*K weight pairs are loop-invariant and would otherwise be
-        asm volatile("" : "+v"(wlh));              // hoisted out of the loops as 2 K*K live registers (an index: ds_read, not flat_load)
-        const float2* tdh = tdg + pxh * C2B;
-        float2 xa[QX], ah[QX], sg[QX];
-        bool img[QX];
+      // The pass body is written as a loop of at most one trip over a copy of the centre pixels, not as `if (wave_has_work)` over xr:
+      // the plain form computes the same values but hipcc then orders the pass differently (48-100 bytes shorter code in every
+      // instantiation, not measured).  The kernel's code is pinned by tools/kernel_code_diff.py; change this form only with a timing.
+      float2 cur[PX];
 #pragma unroll
-        for (int o = 0; o < QX; ++o) {
-          if (UNROLL_H && pxh + o >= PX) continue;
+      for (int o = 0; o < PX; ++o) cur[o] = xr[o];
+      const bool wave_has_work = __builtin_amdgcn_ballot_w64(rok) != 0;
+#pragma unroll 1
+      for (int once = 0; once < (wave_has_work ? 1 : 0); ++once) {
+        __builtin_amdgcn_sched_barrier(0);
+        int wlh = c2;                              // opaque per pass: the K*K weight pairs are loop-invariant and would otherwise be
+        asm volatile("" : "+v"(wlh));              // hoisted out of the loops as 2 K*K live registers (an index: ds_read, not flat_load)
+        float2 xa[PX], ah[PX], sg[PX];
+        bool img[PX];
+#pragma unroll
+        for (int o = 0; o < PX; ++o) {
           const float2 r = cur[o];
-          img[o] = rok && pxh + o < PX && ox0 + pxl + pxh + o < a.W;
+          img[o] = rok && ox0 + pxl + o < a.W;
           float2 v = r, sv = make_float2(0.f, 0.f);
           if (has_bn0) {
             const float zx = A0.x * r.x + B0.x, zy = A0.y * r.y + B0.y;
@@ -711,15 +689,11 @@ __global__ __launch_bounds__(256, (TH == 7) ? 3 : (K == 5 || TH != 8) ? 2 : 3) v
         }
         // the tile row of kernel row ky + 1 is requested before the products of row ky: two rows of reads live, never more
         // (not in the 3-workgroups-per-CU variant: 168 registers)
-#ifndef MX_DW_PIPE
-#define MX_DW_PIPE 1
-#endif
-        constexpr bool PIPE = MX_DW_PIPE && TH != 7 && (K == 5 || TH != 8);
-        float2 inb[PIPE ? 2 : 1][QX - 1 + K];
+        constexpr bool PIPE = TH != 7 && (K == 5 || TH != 8);
+        float2 inb[PIPE ? 2 : 1][PX - 1 + K];
+        if (PIPE) {
 #pragma unroll
-        for (int j = 0; j < QX - 1 + K; ++j) {
-          if (!PIPE || (UNROLL_H && pxh + j - (K - 1) >= PX)) continue;  // (a slot past PX feeds the left-out pixel only)
-          inb[0][j] = tdh[((K - 1) * IWP + j) * C2B];
+          for (int j = 0; j < PX - 1 + K; ++j) inb[0][j] = tdg[((K - 1) * IWP + j) * C2B];
         }
 #pragma unroll
         for (int ky = 0; ky < K; ++ky) {
@@ -727,19 +701,15 @@ __global__ __launch_bounds__(256, (TH == 7) ? 3 : (K == 5 || TH != 8) ? 2 : 3) v
           if (PIPE ? ky + 1 < K : true) {
             const int kr = PIPE ? ky + 1 : ky;
 #pragma unroll
-            for (int j = 0; j < QX - 1 + K; ++j) {
-              if (UNROLL_H && pxh + j - (K - 1) >= PX) continue;
-              inb[PIPE ? (ky + 1) & 1 : 0][j] = tdh[((K - 1 - kr) * IWP + j) * C2B];
-            }
+            for (int j = 0; j < PX - 1 + K; ++j) inb[PIPE ? (ky + 1) & 1 : 0][j] = tdg[((K - 1 - kr) * IWP + j) * C2B];
           }
-          float2 (&in)[QX - 1 + K] = inb[PIPE ? ky & 1 : 0];
+          float2 (&in)[PX - 1 + K] = inb[PIPE ? ky & 1 : 0];
 #pragma unroll
           for (int kx = 0; kx < K; ++kx) {
             const float2 w = reinterpret_cast<const float2*>(wl)[wlh + (ky * K + kx) * C2B];
             float2& p = part[ky * K + kx];
 #pragma unroll
-            for (int o = 0; o < QX; ++o) {
-              if (UNROLL_H && pxh + o >= PX) continue;
+            for (int o = 0; o < PX; ++o) {
               const float2 v = in[o + K - 1 - kx];
               ah[o].x += w.x * v.x; ah[o].y += w.y * v.y;
               p.x += xa[o].x * v.x; p.y += xa[o].y * v.y;
@@ -751,18 +721,14 @@ __global__ __launch_bounds__(256, (TH == 7) ? 3 : (K == 5 || TH != 8) ? 2 : 3) v
           for (int kx = 0; kx < K; ++kx) pin2(part[ky * K + kx]);
         }
         __builtin_amdgcn_sched_barrier(0);
-        // this part's epilogue and stores: no accumulator survives a part.  (The data gradient is pinned here: its only use is
+        // the epilogue and stores: no accumulator survives the pass.  (The data gradient is pinned here: its only use is
         // under `if (img)`, and the optimiser otherwise sinks its K*K products into that branch, after ALL the tile reads.)
 #pragma unroll
-        for (int o = 0; o < QX; ++o) {
-          if (UNROLL_H && pxh + o >= PX) continue;
-          pin2(ah[o]);
-        }
+        for (int o = 0; o < PX; ++o) pin2(ah[o]);
 #pragma unroll
-        for (int o = 0; o < QX; ++o) {
-          if (UNROLL_H && pxh + o >= PX) continue;
+        for (int o = 0; o < PX; ++o) {
           if (img[o]) {
-            const long off = rowoff + (long)(pxh + o) * a.C;
+            const long off = rowoff + (long)o * a.C;
             float2 v = ah[o];
             if (has_bn0) {
               const float2 r = cur[o];
@@ -778,8 +744,6 @@ __global__ __launch_bounds__(256, (TH == 7) ? 3 : (K == 5 || TH != 8) ? 2 : 3) v
             *reinterpret_cast<float2*>(a.gx + off) = v;
           }
         }
-#pragma unroll
-        for (int o = 0; o < QX; ++o) cur[o] = ((h + 1) * QX + o < PX) ? xr[(h + 1) * QX + o] : make_float2(0.f, 0.f);   // (the next part's pixels)
       }
       if (XAHEAD && gi + 1 < NG) {
 #pragma unroll
@@ -824,15 +788,8 @@ __global__ __launch_bounds__(256, (TH == 7) ? 3 : (K == 5 || TH != 8) ? 2 : 3) v
       const int cc = tid % CB;
       if (c0 + cc < a.C) {
         const float v = ((slots[tid] + slots[2 * CB + tid]) + slots[4 * CB + tid]) + slots[6 * CB + tid];
-        float* dst = a.part + (long)grp_id * 2 * a.C + (tid / CB) * a.C + c0 + cc;
-        if (a.fin_counters) mx_st_wt(dst, v); else *dst = v;
+        a.part[(long)grp_id * 2 * a.C + (tid / CB) * a.C + c0 + cc] = v;
       }
-    }
-    if (a.fin_counters) {
-      // every group of this channel chunk has left its row: the last one to arrive adds them in bn_reduce_finalize_kernel's order
-      __shared__ unsigned fin_flag;
-      if (mx_last_arriver(a.fin_counters + chunk_id, gridDim.x, &fin_flag))
-        bn_bwd_reduce_finalize_32(a.part, (int)gridDim.x, a.C, c0, a.fin, reinterpret_cast<double*>(td));
     }
   }
 }
@@ -932,7 +889,6 @@ __global__ __launch_bounds__(256, K == 3 ? 3 : 2) void dw_bwd_fused_s2_kernel(Dw
       const float4 A1 = ld4(cst + 4 * c4), B1 = ld4(cst + CB + 4 * c4), C1 = ld4(cst + 2 * CB + 4 * c4),
                    C2 = ld4(cst + 3 * CB + 4 * c4), C3 = ld4(cst + 4 * CB + 4 * c4),
                    G = ld4(cst + 7 * CB + 4 * c4), AD = ld4(cst + 8 * CB + 4 * c4);
-#define DD1(f) dd.f = okf * (C1.f * ((vg[k].f * G.f + AD.f) * swish_gradf_(A1.f * vd[k].f + B1.f)) + C2.f * vd[k].f + C3.f);
 #pragma unroll
       for (int k = 0; k < PER; ++k) {
         const int i = min(tid + 256 * k, TOT - 1), pix = i / C4B;   // duplicates of the last element rewrite the same value
@@ -941,7 +897,6 @@ __global__ __launch_bounds__(256, K == 3 ? 3 : 2) void dw_bwd_fused_s2_kernel(Dw
         DD1(x) DD1(y) DD1(z) DD1(w)
         td[((pix / OW) * OWP + pix % OW) * C4B + c4] = dd;
       }
-#undef DD1
     }
     __syncthreads();
     const float2 A0 = *reinterpret_cast<const float2*>(cst + 5 * CB + 2 * c2), B0 = *reinterpret_cast<const float2*>(cst + 6 * CB + 2 * c2);
@@ -1282,42 +1237,10 @@ int mx_dwconv_bwd_fused_parts(int N, int H, int Wd, int C, int K) {
 
 // Stride-1 backward of [BN0+SiLU] -> dwconv -> BN1 -> SiLU -> SE gate fused (see dw_bwd_fused_kernel):
 //   gX = dwconv^T(dd) [* swish'(a0*X+b0)] [+ residual];  dW += sum dd*act(X);  part = BN0 backward partial sums (a0 != NULL)
-static int dw_bwd_fused_impl(const float* dA, const float* D, const float* gate, const float* add, const float* a1, const float* b1,
-                            const float* c1, const float* c2, const float* c3, const float* X, const float* a0, const float* b0,
-                            const float* W, const float* residual, float* gX, float* dW, float* dw_scratch, float* part, int N, int H,
-                            int Wd, int C, int K, int pad_lo, void* stream, unsigned* fin_counters, const BnBwdFin* fin);
-
 int mx_dwconv_bwd_fused(const float* dA, const float* D, const float* gate, const float* add, const float* a1, const float* b1,
                         const float* c1, const float* c2, const float* c3, const float* X, const float* a0, const float* b0,
                         const float* W, const float* residual, float* gX, float* dW, float* dw_scratch, float* part, int N, int H,
                         int Wd, int C, int K, int pad_lo, void* stream) {
-  return dw_bwd_fused_impl(dA, D, gate, add, a1, b1, c1, c2, c3, X, a0, b0, W, residual, gX, dW, dw_scratch, part, N, H, Wd, C, K, pad_lo,
-                           stream, nullptr, nullptr);
-}
-
-// The same with the BatchNorm-0 backward statistics FINISHED in the kernel (a0 / b0 / part required): the last workgroup of every
-// 32-channel chunk adds the partial rows in mx_bn_bwd_finalize's order and writes dgamma / dbeta (+=) and the coefficients o1 o2 o3 of
-// dX = o1*g + o2*X + o3 - what a separate mx_bn_bwd_finalize(part, ...) launch would have left, bit for bit.  ws: zeroed scratch whose
-// first 64 KB are arrival counters (left zero), as for mx_pool_sum.  Returns MX_EARG for geometries it does not take (the XCD-grouped
-// grid): call mx_dwconv_bwd_fused + mx_bn_bwd_finalize then.
-int mx_dwconv_bwd_fused_bn0(const float* dA, const float* D, const float* gate, const float* add, const float* a1, const float* b1,
-                            const float* c1, const float* c2, const float* c3, const float* X, const float* a0, const float* b0,
-                            const float* W, float* gX, float* dW, float* dw_scratch, float* part, int N, int H, int Wd, int C, int K,
-                            int pad_lo, void* ws, long ws_bytes, double count, const float* gamma, const float* mean, const float* rstd,
-                            int training, float* dgamma, float* dbeta, float* o1, float* o2, float* o3, void* stream) {
-  MX_CHECK_ARG(a0 && b0 && part, "dwconv_bwd_fused_bn0: the BatchNorm-0 form only (a0, b0, part)");
-  MX_CHECK_ARG(ws && ws_bytes >= MX_WS_COUNTER_BYTES && ((uintptr_t)ws & 15) == 0, "dwconv_bwd_fused_bn0: scratch with %d bytes of counters required", MX_WS_COUNTER_BYTES);
-  MX_CHECK_ARG(gamma && mean && rstd && dgamma && dbeta && o1 && o2 && o3 && count > 0, "dwconv_bwd_fused_bn0: null pointer");
-  MX_CHECK_ARG(cdiv(C, CB) <= MX_WS_COUNTERS, "dwconv_bwd_fused_bn0: too many channel chunks");
-  BnBwdFin fin{count, gamma, mean, rstd, training, dgamma, dbeta, o1, o2, o3};
-  return dw_bwd_fused_impl(dA, D, gate, add, a1, b1, c1, c2, c3, X, a0, b0, W, nullptr, gX, dW, dw_scratch, part, N, H, Wd, C, K, pad_lo,
-                           stream, reinterpret_cast<unsigned*>(ws), &fin);
-}
-
-static int dw_bwd_fused_impl(const float* dA, const float* D, const float* gate, const float* add, const float* a1, const float* b1,
-                            const float* c1, const float* c2, const float* c3, const float* X, const float* a0, const float* b0,
-                            const float* W, const float* residual, float* gX, float* dW, float* dw_scratch, float* part, int N, int H,
-                            int Wd, int C, int K, int pad_lo, void* stream, unsigned* fin_counters, const BnBwdFin* fin) {
   MX_CHECK_ARG(dA && D && gate && add && a1 && b1 && c1 && c2 && c3 && X && W && gX && dw_scratch, "dwconv_bwd_fused: null pointer");
   MX_CHECK_ARG((a0 == nullptr) == (b0 == nullptr), "dwconv_bwd_fused: a0/b0 come together");
   MX_CHECK_ARG(!a0 || part, "dwconv_bwd_fused: BN0 present -> part required");
@@ -1331,7 +1254,6 @@ static int dw_bwd_fused_impl(const float* dA, const float* D, const float* gate,
   dw_fused_geom(N, H, Wd, C, K, &a.tiles_x, &a.tiles_y, &a.tiles_per_block, &groups);
   dim3 grid(groups, cdiv(C, CB), 1);
   a.chunks = grid.y;
-  if (fin_counters) { a.fin_counters = fin_counters; a.fin = *fin; }
   const int shape = dw_fused_shape(H, Wd, K);
   if (shape == 3) {
     hipLaunchKernelGGL((dw_bwd_fused_kernel<3, 8, 28, 7>), grid, dim3(256), 0, (hipStream_t)stream, a);

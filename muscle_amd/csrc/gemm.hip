@@ -411,16 +411,8 @@ static void dispatch(const GemmArgs& g, int zdim, hipStream_t st) {
 // as its second, so a lane's four accumulator registers are four CONSECUTIVE OUTPUT CHANNELS of one pixel row
 // (acc[i][j][r] = C[m = 16 i + l15][n = 16 j + 4 q + r]): bias, residual, relu and the 16-byte non-temporal store need
 // no exchange at all (round-2 first version: through a per-wave LDS patch, 64 ds_write_b32 + 16 ds_read_b128 per lane).
-// Column statistics: per-lane sums over the TM row tiles, then a rotate-and-add over the 16 lanes of a DPP row.
+// Column statistics: per-lane sums over the TM row tiles, then a rotate-and-add over the 16 lanes of a DPP row (row16_sum, common.h).
 // `smem` needs WM*2*BN floats (statistics only); every wave must be out of the main loop.
-static __device__ __forceinline__ float row16_sum(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xf, 0xf, false));   // row_ror:8
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x124, 0xf, 0xf, false));   // row_ror:4
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x122, 0xf, 0xf, false));   // row_ror:2
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x121, 0xf, 0xf, false));   // row_ror:1
-  return v;
-}
-
 template <int WM, int WN, int TM, int TN>
 static __device__ __forceinline__ void nt_epilogue(const GemmArgs& g, float* C, int tile_m, int m0, int n0, f32x4 (&acc)[TM][TN],
                                                    float* smem, int tid) {
@@ -698,16 +690,6 @@ __global__ __launch_bounds__(256, gemm_nt_waves(TM * TN * 4 + (AMODE == MX_BNBWD
 // slab moves from registers to LDS (5.5 operations per value), after the operand prologue.  As in gemm_nt_kernel the
 // weight rows are the MFMA's first operand, so a lane's accumulators are runs of four consecutive output channels.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-static __device__ __forceinline__ void split3_pair(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
-  const unsigned u0 = __float_as_uint(x0) & 0xffff0000u, u1 = __float_as_uint(x1) & 0xffff0000u;
-  const float r0 = x0 - __uint_as_float(u0), r1 = x1 - __uint_as_float(u1);                // exact
-  const unsigned v0 = __float_as_uint(r0) & 0xffff0000u, v1 = __float_as_uint(r1) & 0xffff0000u;
-  const float s0 = r0 - __uint_as_float(v0), s1 = r1 - __uint_as_float(v1);                // exact, <= 8 significant bits
-  h = __builtin_amdgcn_perm(u1, u0, 0x07060302u);     // {bf16(x1), bf16(x0)}: the top halves of both words
-  m = __builtin_amdgcn_perm(v1, v0, 0x07060302u);
-  l = __builtin_amdgcn_perm(__float_as_uint(s1), __float_as_uint(s0), 0x07060302u);
-}
 
 // NJ = 32-column MFMA tiles per wave: tile 128 x (64 NJ).  NJ = 1 doubles the tile count where 128 x 128 leaves CUs idle.
 template <int AMODE, int NJ>

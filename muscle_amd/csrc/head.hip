@@ -8,15 +8,8 @@
 #include "common.h"
 #include <hip/hip_fp16.h>
 
-// align_corners=True source coordinate (torch upsample_bilinear2d): src = dst * (in-1)/(out-1)
-__device__ __forceinline__ void bil_coord(int d, int in, int out, int& i0, int& i1, float& w1) {
-  float scale = (out > 1) ? (float)(in - 1) / (float)(out - 1) : 0.f;
-  float s = scale * d;
-  i0 = (int)s;
-  if (i0 > in - 1) i0 = in - 1;
-  i1 = i0 + ((i0 < in - 1) ? 1 : 0);
-  w1 = s - i0;
-}
+// one component of the bilinear value of the four taps a00 a01 a10 a11 (float4) at the weights wy, wx of bil_coord (common.h), into o
+#define BIL(f) o.f = (1.f - wy) * ((1.f - wx) * a00.f + wx * a01.f) + wy * ((1.f - wx) * a10.f + wx * a11.f)
 
 // dst[n,y,x,coff + c] = [relu] bilinear(src[n,:,:,c])   NHWC -> NHWC (channel slice of a wider tensor)
 __global__ __launch_bounds__(256) void resize_nhwc_kernel(const float* src, float* dst, int N, int Hs, int Ws, int C, int Hd,
@@ -37,9 +30,7 @@ __global__ __launch_bounds__(256) void resize_nhwc_kernel(const float* src, floa
     float4 a00 = ld4(b + ((long)y0 * Ws + x0) * C), a01 = ld4(b + ((long)y0 * Ws + x1) * C);
     float4 a10 = ld4(b + ((long)y1 * Ws + x0) * C), a11 = ld4(b + ((long)y1 * Ws + x1) * C);
     float4 o;
-#define BIL(f) o.f = (1.f - wy) * ((1.f - wx) * a00.f + wx * a01.f) + wy * ((1.f - wx) * a10.f + wx * a11.f)
     BIL(x); BIL(y); BIL(z); BIL(w);
-#undef BIL
     if (relu) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
     st4(dst + p * ldd + coff + c, o);
   }
@@ -288,9 +279,7 @@ __device__ __forceinline__ void seg_softmax_at(const float* src, int h, int w, i
     float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
     if (q * 4 < K) {                         // quad q lies inside the row: K <= lds and lds % 4 == 0
       float4 a00 = ld4(r00 + q * 4), a01 = ld4(r01 + q * 4), a10 = ld4(r10 + q * 4), a11 = ld4(r11 + q * 4);
-#define BIL(f) o.f = (1.f - wy) * ((1.f - wx) * a00.f + wx * a01.f) + wy * ((1.f - wx) * a10.f + wx * a11.f)
       BIL(x); BIL(y); BIL(z); BIL(w);
-#undef BIL
     }
     p[q * 4 + 0] = o.x; p[q * 4 + 1] = o.y; p[q * 4 + 2] = o.z; p[q * 4 + 3] = o.w;
   }

@@ -247,12 +247,6 @@ __global__ __launch_bounds__(256) void gather_s2_kernel(const float* __restrict_
 // =====================================================================================================================
 #define GN_MAX_SLICES 64
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // grid (slices, G, N): fp64 sums of x and x^2 over this slice's rows of the group's C/G channels -> part[n][g][slice][2].
 // Each thread adds its elements in index order, the wave butterfly and the four waves are added in a fixed order.
 __global__ __launch_bounds__(256) void gn_partial_kernel(const float* __restrict__ X, int HW, int C, int ldx, int G, int rows_per,
@@ -293,15 +287,6 @@ __global__ __launch_bounds__(64) void gn_finalize_kernel(const double* __restric
   if (var < 0.0) var = 0.0;
   stat[2 * i] = (float)mean;
   stat[2 * i + 1] = (float)(1.0 / sqrt(var + (double)eps));
-}
-
-// source index of the half-pixel (align_corners=False) bilinear resize: rs = source pixels per destination pixel
-__device__ __forceinline__ void halfpixel_tap(int d, float rs, int n_src, int& i0, int& i1, float& l1) {
-  float s = rs * ((float)d + 0.5f) - 0.5f;
-  s = s < 0.f ? 0.f : s;
-  i0 = min((int)s, n_src - 1);
-  i1 = min(i0 + 1, n_src - 1);
-  l1 = s - (float)i0;
 }
 
 // dst[n,y,x,coff+c] = [relu] bilinear_halfpixel_{x scale}( gamma*(src - mean)*rstd + beta )[y, x]   for y < Hd, x < Wd (the crop)

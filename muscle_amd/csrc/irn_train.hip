@@ -18,12 +18,6 @@
 #define IT_MAX_RF 15
 #define IT_RES 16                                        // doubles in the result block, see mx_irn_loss_fwd in the header
 
-__device__ __forceinline__ double it_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __device__ __forceinline__ double it_sigmoid(float x) { return 1.0 / (1.0 + exp(-(double)x)); }
 
 // 0 = no pair (an end is >= 21), 1 = bg-pos, 2 = fg-pos, 3 = neg
@@ -105,7 +99,7 @@ __global__ __launch_bounds__(256) void it_loss_fwd_kernel(const float* __restric
   }
   __shared__ double sh[4][8];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) a[j] = it_wave_sum(a[j]);
+  for (int j = 0; j < 8; ++j) a[j] = wave_sum_d(a[j]);
   if ((tid & 63) == 0) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) sh[tid >> 6][j] = a[j];
@@ -213,11 +207,11 @@ __global__ __launch_bounds__(256) void it_loss_bwd_kernel(const float* __restric
 // Adjoint of mx_gn_resize: ReLU mask from the stored forward slice, crop, transpose of the half-pixel bilinear up-sample as a
 // gather - every source pixel visits the destination pixels that can have it as a tap, in index order.
 // =====================================================================================================================
+// weight of source index s in destination index d's two taps (halfpixel_tap, common.h: the forward's own)
 __device__ __forceinline__ float it_tap_weight(int d, float rs, int n_src, int s) {
-  float f = rs * ((float)d + 0.5f) - 0.5f;
-  f = f < 0.f ? 0.f : f;
-  const int i0 = min((int)f, n_src - 1), i1 = min(i0 + 1, n_src - 1);
-  const float l1 = f - (float)i0;
+  int i0, i1;
+  float l1;
+  halfpixel_tap(d, rs, n_src, i0, i1, l1);
   return (i0 == s ? 1.f - l1 : 0.f) + (i1 == s ? l1 : 0.f);
 }
 

@@ -202,13 +202,6 @@ __global__ __launch_bounds__(1024) void imc_kernel(const float* emb, const float
 // workspace (floats): E [N][D] | nrm [N] | S [N][N] | F [N][N] | k1 [N] | k2 [N] | block loss, valid [2][4]
 // ---------------------------------------------------------------------------
 typedef float lf32x4 __attribute__((ext_vector_type(4)));
-static __device__ __forceinline__ float imc_row16_sum(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xf, 0xf, false));   // row_ror:8
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x124, 0xf, 0xf, false));   // row_ror:4
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x122, 0xf, 0xf, false));   // row_ror:2
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x121, 0xf, 0xf, false));   // row_ror:1
-  return v;
-}
 
 struct ImcWs { float *E, *nrm, *S, *F, *k1, *k2, *blk; };
 static __host__ __device__ __forceinline__ ImcWs imc_ws(float* ws, int N, int D) {
@@ -281,7 +274,7 @@ __global__ __launch_bounds__(256) void imc_gram_kernel(const float* __restrict__
   }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const float a = imc_row16_sum(sp[r]), b = imc_row16_sum(sn[r]), c = imc_row16_sum(vp[r]), d = imc_row16_sum(vn[r]);
+    const float a = row16_sum(sp[r]), b = row16_sum(sn[r]), c = row16_sum(vp[r]), d = row16_sum(vn[r]);
     if (l15 == 0) { rs[wave][4 * g + r][0] = a; rs[wave][4 * g + r][1] = b; rs[wave][4 * g + r][2] = c; rs[wave][4 * g + r][3] = d; }
   }
   __syncthreads();
@@ -354,7 +347,7 @@ __global__ __launch_bounds__(256) void imc_grad_kernel(int N, int D, float* ws, 
   }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const float a = imc_row16_sum(dot[r]);
+    const float a = row16_sum(dot[r]);
     if (l15 == 0) dg[wave][4 * g + r] = a;
   }
   __syncthreads();
@@ -698,7 +691,7 @@ int mx_adam(float* p, const float* g, float* m, float* v, long n, float lr, floa
 // 64 lanes hitting LDS bin 0 serialised the pass.
 // ---------------------------------------------------------------------------
 // BIT INVARIANT of the low-res family: the forward parks / histograms fabsf(a - b) * m of a pixel and class, and the backward
-// kernels recompute it and compare its BITS with the threshold the select found.  lr_coord and lr_pixel are inlined into
+// kernels recompute it and compare its BITS with the threshold the select found.  bil_coord_rn (common.h) and lr_pixel are inlined into
 // four kernels (runtime K and the 21-class template); under hipcc's default contraction (fast-honor-pragmas; the build
 // passes no -ffp-contract flag) the compiler fused multiplies into different neighbours in each of them (e.g. a[k] * ia
 // into the caller's a[k] - b[k]), the band kernel's value differed from the histogrammed one in the last bit, and the
@@ -707,16 +700,6 @@ int mx_adam(float* p, const float* g, float* m, float* v, long n, float lr, floa
 // by that default: a literal -ffp-contract=fast fuses globally, ignores it and undoes this.
 // The full-resolution pair (er_diff_kernel / er_bwd_kernel through softmaxnorm_px) has the same hazard and no pragma: the
 // two agree today by the compiler's choice, and tests/test_gpu_er.py (tie and constant-region cases) is what watches it.
-__device__ __forceinline__ void lr_coord(int d, int in, int out, int& i0, int& i1, float& w1) {
-#pragma clang fp contract(off)
-  float scale = (out > 1) ? (float)(in - 1) / (float)(out - 1) : 0.f;
-  float s = scale * d;
-  i0 = (int)s;
-  if (i0 > in - 1) i0 = in - 1;
-  i1 = i0 + ((i0 < in - 1) ? 1 : 0);
-  w1 = s - i0;
-}
-
 // v0 * (u00 * p00 + u01 * p01) + v1 * (u00 * p10 + u01 * p11) with its three fused steps spelled out
 __device__ __forceinline__ float lr_lerp(float v0, float v1, float u00, float u01, float p00, float p01, float p10, float p11) {
 #pragma clang fp contract(off)
@@ -727,8 +710,8 @@ __device__ __forceinline__ float lr_lerp(float v0, float v1, float u00, float u0
 __device__ __forceinline__ int lr_pixel(const float* cam, const float* sgc, int n, int Y, int X, int h, int w, int L, int K, int H,
                                         int W, float* a, float* b, float& wy, float& wx, int& y0, int& y1, int& x0, int& x1) {
 #pragma clang fp contract(off)
-  lr_coord(Y, h, H, y0, y1, wy);
-  lr_coord(X, w, W, x0, x1, wx);
+  bil_coord_rn(Y, h, H, y0, y1, wy);
+  bil_coord_rn(X, w, W, x0, x1, wx);
   const long base = (long)n * h * w * L;
   const float* c00 = cam + base + ((long)y0 * w + x0) * L; const float* c01 = cam + base + ((long)y0 * w + x1) * L;
   const float* c10 = cam + base + ((long)y1 * w + x0) * L; const float* c11 = cam + base + ((long)y1 * w + x1) * L;
@@ -907,9 +890,9 @@ __global__ __launch_bounds__(256) void er_lr_bwd_band_kernel(const float* cam, c
   const int Y1 = min(H, Y0 + ty);
   int cb, t1, xb, xe, t2;
   float tw;
-  lr_coord(Y0, h, H, cb, t1, tw);
-  lr_coord(blockIdx.x * 256, w, W, xb, t2, tw);
-  lr_coord(min(W - 1, blockIdx.x * 256 + 255), w, W, t1, xe, tw);
+  bil_coord_rn(Y0, h, H, cb, t1, tw);
+  bil_coord_rn(blockIdx.x * 256, w, W, xb, t2, tw);
+  bil_coord_rn(min(W - 1, blockIdx.x * 256 + 255), w, W, t1, xe, tw);
   const int ncx = xe - xb + 1;
   for (int i = threadIdx.x; i < 3 * ncx * KT; i += 256) lacc[i] = 0ull;
   __syncthreads();

@@ -159,15 +159,6 @@ __global__ __launch_bounds__(256) void chan_l2norm_kernel(const float* x, const 
 // out[off + (r*rw + c), k] = bilinear_align_corners(src[sample, k, y0:y0+lh, x0:x0+lw] -> (rh, rw))
 // (rh == lh and rw == lw is the identity crop used for the second view)
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void bil_coord2(int d, int in, int out, int& i0, int& i1, float& w1) {
-  float scale = (out > 1) ? (float)(in - 1) / (float)(out - 1) : 0.f;
-  float s = scale * d;
-  i0 = (int)s;
-  if (i0 > in - 1) i0 = in - 1;
-  i1 = i0 + ((i0 < in - 1) ? 1 : 0);
-  w1 = s - i0;
-}
-
 // grid (crops, 3): workgroup (crop, channel group of 8) - a crop per workgroup left the chip a third full at ~900 crops
 __global__ __launch_bounds__(256) void crop_resize_kernel(const float* src, const int* table, float* out, int K, int H, int W) {
   const int* t = table + blockIdx.x * 8;
@@ -178,8 +169,8 @@ __global__ __launch_bounds__(256) void crop_resize_kernel(const float* src, cons
     int r = p / rw, c = p % rw;
     int ya, yb, xa, xb;
     float wy, wx;
-    bil_coord2(r, lh, rh, ya, yb, wy);
-    bil_coord2(c, lw, rw, xa, xb, wx);
+    bil_coord(r, lh, rh, ya, yb, wy);
+    bil_coord(c, lw, rw, xa, xb, wx);
     const float* b = src + (long)n * K * HW;
     float* o = out + ((long)off + p) * FP;
     for (int k = kbeg; k < kend; ++k) {
@@ -202,13 +193,6 @@ __global__ __launch_bounds__(256) void crop_resize_kernel(const float* src, cons
 // here: torchutils.py:254-262), weight x gradient for its KG classes; a barrier separates crops.  One adder per element,
 // fixed order: same bits every run.
 constexpr int CROP_KG = 7;     // classes per workgroup (21 = 3 x 7)
-__device__ __forceinline__ void adj_range(int si, int in, int out, int& lo, int& hi) {
-  // output indices d whose bil_coord2(d) can name source index si: scale*d in (si - 1, si + 1); one index of margin each side
-  if (out <= 1 || in <= 1) { lo = 0; hi = out - 1; return; }
-  const float inv = (float)(out - 1) / (float)(in - 1);
-  lo = max(0, (int)floorf((float)(si - 1) * inv) - 1);
-  hi = min(out - 1, (int)ceilf((float)(si + 1) * inv) + 1);
-}
 __global__ __launch_bounds__(256) void crop_resize_bwd_kernel(const float* gout_all, const int* table, int ncrops, float* gsrc, int K,
                                                               int H, int W) {
   const int n = blockIdx.x, k0 = blockIdx.y * CROP_KG;
@@ -227,19 +211,19 @@ __global__ __launch_bounds__(256) void crop_resize_bwd_kernel(const float* gout_
     for (int sp = threadIdx.x; sp < (s_hi - s_lo) * lw; sp += 256) {
       const int sy = s_lo + sp / lw, sx = sp % lw;
       int rlo, rhi, clo, chi;
-      adj_range(sy, lh, rh, rlo, rhi);
-      adj_range(sx, lw, rw, clo, chi);
+      bil_adj_range(sy, lh, rh, rlo, rhi);
+      bil_adj_range(sx, lw, rw, clo, chi);
       float acc[CROP_KG];
 #pragma unroll
       for (int j = 0; j < CROP_KG; ++j) acc[j] = 0.f;
       for (int r = rlo; r <= rhi; ++r) {
         int ya, yb; float wy;
-        bil_coord2(r, lh, rh, ya, yb, wy);
+        bil_coord(r, lh, rh, ya, yb, wy);
         const float wyy = (ya == sy ? 1.f - wy : 0.f) + (yb == sy ? wy : 0.f);     // (both terms when ya == yb, as the forward)
         if (wyy == 0.f) continue;
         for (int c = clo; c <= chi; ++c) {
           int xa, xb; float wx;
-          bil_coord2(c, lw, rw, xa, xb, wx);
+          bil_coord(c, lw, rw, xa, xb, wx);
           const float wxx = (xa == sx ? 1.f - wx : 0.f) + (xb == sx ? wx : 0.f);
           if (wxx == 0.f) continue;
           const float* g = gout + (long)(r * rw + c) * FP + k0;

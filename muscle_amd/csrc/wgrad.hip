@@ -562,16 +562,6 @@ __global__ __launch_bounds__(256, (TE * TF >= 16 && XMODE == MX_BNACT) ? 3 : 4) 
 typedef __bf16 wbf16x8 __attribute__((ext_vector_type(8)));
 typedef float wf32x16 __attribute__((ext_vector_type(16)));
 
-static __device__ __forceinline__ void wsplit3_pair(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
-  const unsigned u0 = __float_as_uint(x0) & 0xffff0000u, u1 = __float_as_uint(x1) & 0xffff0000u;
-  const float r0 = x0 - __uint_as_float(u0), r1 = x1 - __uint_as_float(u1);
-  const unsigned v0 = __float_as_uint(r0) & 0xffff0000u, v1 = __float_as_uint(r1) & 0xffff0000u;
-  const float s0 = r0 - __uint_as_float(v0), s1 = r1 - __uint_as_float(v1);
-  h = __builtin_amdgcn_perm(u1, u0, 0x07060302u);
-  m = __builtin_amdgcn_perm(v1, v0, 0x07060302u);
-  l = __builtin_amdgcn_perm(__float_as_uint(s1), __float_as_uint(s0), 0x07060302u);
-}
-
 // GBN (the G operand as the BatchNorm backward apply c1*G + c2*G2 + c3, formed by the loader threads) is instantiated as false only: the
 // fold into this kernel was measured slower and its entry points are removed.  The GBN branches stay in the source because deleting them,
 // dead as they are, makes the compiler number the scale / shift registers of the <MX_BNACT> and <MX_AFFINE> instantiations differently,
@@ -646,7 +636,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(WtArgs a) {
       for (int q = 0; q < 4; ++q) {
         const float x0 = jc == 0 ? rv[2 * q].x : jc == 1 ? rv[2 * q].y : jc == 2 ? rv[2 * q].z : rv[2 * q].w;
         const float x1 = jc == 0 ? rv[2 * q + 1].x : jc == 1 ? rv[2 * q + 1].y : jc == 2 ? rv[2 * q + 1].z : rv[2 * q + 1].w;
-        wsplit3_pair(x0, x1, h[q], m[q], l[q]);
+        split3_pair(x0, x1, h[q], m[q], l[q]);
       }
       const int off = col * 64 + ((rg ^ ((col >> 2) & 3)) << 4);
       *reinterpret_cast<uint4*>(pl + off) = make_uint4(h[0], h[1], h[2], h[3]);
@@ -720,18 +710,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(WtArgs a) {
 //     pass (16 consecutive columns of one k-group) reads chunks 36 b + a + 4 m (b = col & 3, a = (col >> 2) & 3): 16 different bank groups
 //     either way.  The first kernel's [128 columns][64 bytes] image is conflict-free for the reads only: its plane stores hit 4 bank
 //     groups per pass (4-way), which made the LDS, not the matrix pipe, the busiest unit.
-#ifndef WPIPE_KNOCK
-#define WPIPE_KNOCK 0      // diagnostic builds of tools/hip/gemm_lab only: 1 = no split in the loader waves
-#endif
-
-static __device__ __forceinline__ __amdgpu_buffer_rsrc_t wbuf_rsrc(const float* base, long bytes) {
-  // wave-uniform by construction (blockIdx / wave-id only): the readfirstlanes make that provable, no waterfall loops
-  const unsigned long long p = (unsigned long long)base;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)p), hi = __builtin_amdgcn_readfirstlane((unsigned)(p >> 32));
-  const unsigned n = __builtin_amdgcn_readfirstlane((unsigned)bytes);
-  return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)hi << 32) | lo), 0, n, 0x00020000);
-}
-
 #ifdef WPIPE_STAMPS        // diagnostic builds of tools/hip/gemm_lab only: shader-clock stamps per workgroup (start, loop start, loop end, end, 2 x realtime)
 __device__ unsigned long long* wpipe_stamps;
 #endif
@@ -750,15 +728,10 @@ __device__ unsigned long long* wpipe_stamps;
 #else
 #define WWS_STAMP(slot) do { } while (0)
 #endif
-#ifndef WWS_PF
-#define WWS_PF 3           // raw row sets of a loader wave (slabs requested ahead)
-#endif
-#ifndef WWS_CHAIN
-#define WWS_CHAIN 49       // slabs (32 rows) of one fp32 accumulation chain: 1568 rows
-#endif
-#ifndef WWS_PRIO
-#define WWS_PRIO 1         // s_setprio of the MFMA waves
-#endif
+// (the prefetch depth and the priority were lab sweeps, profiles/r05_wgrad_pipe_lab.txt)
+constexpr int WWS_PF = 3;        // raw row sets of a loader wave (slabs requested ahead)
+constexpr int WWS_CHAIN = 49;    // slabs (32 rows) of one fp32 accumulation chain: 1568 rows
+constexpr int WWS_PRIO = 1;      // s_setprio of the MFMA waves
 __global__ __launch_bounds__(512, 1) void wgrad_split_ws_kernel(WtArgs a) {
   constexpr int PLANE = 4 * 144 * 16, STAGE = 6 * PLANE;    // the LDS image described above wbuf_rsrc
   constexpr int PF = WWS_PF;                                // raw row sets
@@ -791,8 +764,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_split_ws_kernel(WtArgs a) {
     _Pragma("unroll") for (int jc_ = 0; jc_ < 4; ++jc_) {                                                                           \
       unsigned h_[4], m_[4], l_[4];                                                                                                 \
       _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_) {                                                                            \
-        if (WPIPE_KNOCK == 1) { h_[q_] = __float_as_uint(RV[2 * q_][jc_]); m_[q_] = __float_as_uint(RV[2 * q_ + 1][jc_]); l_[q_] = 0; }    \
-        else wsplit3_pair(RV[2 * q_][jc_], RV[2 * q_ + 1][jc_], h_[q_], m_[q_], l_[q_]); }                                          \
+        split3_pair(RV[2 * q_][jc_], RV[2 * q_ + 1][jc_], h_[q_], m_[q_], l_[q_]); }                                               \
       unsigned char* o_ = wb + (STG) * STAGE + jc_ * 576;                                                                           \
       *reinterpret_cast<uint4*>(o_) = make_uint4(h_[0], h_[1], h_[2], h_[3]);                                                       \
       *reinterpret_cast<uint4*>(o_ + PLANE) = make_uint4(m_[0], m_[1], m_[2], m_[3]);                                               \
@@ -968,9 +940,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_split_ws_kernel(WtArgs a) {
 // quadrant each) read 4 fragments (ds_read_b32) per 4 MFMAs of 64 cycles.  LDS image of an operand's slab: [32 rows][128 floats], the 16-byte unit u
 // of an odd row stored at position u ^ 8, so that the two rows one fragment read touches sit in different halves of the 64 banks.  Three stages
 // (96 KB).  Same persistent item loop, row groups, 1568-row chains and partial-tile stores as wgrad_split_ws_kernel.
-#ifndef WF32_NST
-#define WF32_NST 3
-#endif
+constexpr int WF32_NST = 3;
 // E, F: 32-row / 32-column blocks of a wave's quadrant - the workgroup's tile is 64 E x 64 F (128 x 128, 128 x 64 for narrow Ci such as 960 x 160,
 // 64 x 128 for its mirror); the LDS image keeps its 128-float rows, the loader lanes past a 64-wide tile ask for nothing.
 template <int E, int F>

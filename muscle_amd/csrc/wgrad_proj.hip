@@ -31,14 +31,6 @@ struct WpArgs {
   int R, ldg, ldx, ldda, rps, rows_per_wg;      // R, rps and rows_per_wg multiples of 16: every slab is whole and inside one sample
 };
 
-static __device__ __forceinline__ __amdgpu_buffer_rsrc_t wbuf_rsrc(const float* base, long bytes) {
-  // wave-uniform by construction (blockIdx only): the readfirstlanes make that provable, no waterfall loops
-  const unsigned long long p = (unsigned long long)base;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)p), hi = __builtin_amdgcn_readfirstlane((unsigned)(p >> 32));
-  const unsigned n = __builtin_amdgcn_readfirstlane((unsigned)bytes);
-  return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)hi << 32) | lo), 0, n, 0x00020000);
-}
-
 constexpr int wp_pad16(int c) { return ((c + 15) / 16 * 16) % 32 == 16 ? (c + 15) / 16 * 16 : (c + 15) / 16 * 16 + 16; }      // wg_pad16
 
 // CO, CI: the conv's shape; the tiling is wg_plan's for it (four waves; the CO / 16 Co tiles on every wave, Ci tile wave + 4 j on wave)

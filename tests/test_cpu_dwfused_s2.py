@@ -117,7 +117,7 @@ class RecordingOps:
     def _r_bn1_coeffs(self, pooled5, gate, *a):
         return self._e(3, gate.shape[1]), torch.empty_like(gate)
 
-    def _r_dwconv_bwd_fused(self, dA, D, gate, add, st1, c1, X, st0, W, dW, K, pad_lo, *, residual=None, defer=None, bn0=None):
+    def _r_dwconv_bwd_fused(self, dA, D, gate, add, st1, c1, X, st0, W, dW, K, pad_lo, *, residual=None, defer=None):
         if defer is not None:
             defer(self._e(4, W.numel()), dW)
         return torch.empty_like(X), (self._e(4, 2, X.shape[3]) if st0 is not None else None)
