@@ -20,6 +20,7 @@ Per block, backward:
     stride 2: dwconv_bwd_fused_s2[the same fusion over 8 x 32 input-pixel tiles, taps by pixel parity] --> gz
               (DW_S2_FUSED off, or a plain depthwise input: bn_bwd_apply --> dwconv_bwd_weight, dwconv_bwd_data --> ge --BN0 bwd reduce)
     gz --BN0 finalise + apply--> de --pw_wgrad / pw_dgrad (+skip gradient)--> g_in
+Which of these a block takes is decided in one place, block_route, and handed to the stage functions as a BlockRoute.
 With save=False (no backward will follow) every tensor only backward would read is released as the forward goes.
 """
 from __future__ import annotations
@@ -27,7 +28,7 @@ from __future__ import annotations
 import os
 
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional
 
 import torch
 
@@ -83,6 +84,15 @@ MATERIALISE_ABOVE_EVAL = int(os.environ.get("MUSCLE_MATERIALISE_ABOVE_EVAL", str
 # ... where the GEMM has rows to spread the prologue's sigmoid over: the batch-1 multi-scale passes of infer_mcl.py (a few thousand
 # rows in the late stages) keep the materialised input (one 500x375 image, 8 passes: 40.4 ms against 42.4)
 EVAL_PROLOGUE_MIN_ROWS = int(os.environ.get("MUSCLE_EVAL_PROLOGUE_MIN_ROWS", "16384"))
+
+
+def project_materialises(b: BlockCfg, Mo: int, training: bool) -> bool:
+    """Does the project conv of block `b`, Mo output rows, read a materialised a = swish(bn1(d_raw))*gate (else the GEMM forms it in
+    its operand prologue)?  training: the tape-keeping forward, whose weight gradient shares the tensor; False: the folded
+    inference form (_block_forward_eval)."""
+    if training:
+        return b.cout > MATERIALISE_ABOVE
+    return b.cout > MATERIALISE_ABOVE_EVAL or (Mo < EVAL_PROLOGUE_MIN_ROWS and b.cout > MATERIALISE_ABOVE)
 
 
 def _blk(backbone, i):
@@ -181,7 +191,7 @@ def _block_forward_eval(m, b: BlockCfg, f, ident, x, x_st, N, h, w, ho, wo):
                             m._se_expand.weight.view(b.cexp, b.se), m._se_expand.bias)
     d2 = d.view(Mo, b.cexp)
     res = x.view(M, b.cin) if b.skip else None
-    if b.cout > MATERIALISE_ABOVE_EVAL or (Mo < EVAL_PROLOGUE_MIN_ROWS and b.cout > MATERIALISE_ABOVE):
+    if project_materialises(b, Mo, False):
         a = ops.bn_apply(d2, f["bn1"], gate=gate, rows_per_sample=ho * wo, act=True)
         out = ops.pw_fwd(a, f["Wp"], b.cout, bias=f["bp"], residual=res, planes=f.get("Wp_planes"))
     else:
@@ -326,7 +336,7 @@ def backbone_forward(backbone, cfg: NetCfg, img: torch.Tensor, training: bool,
         t.s, t.h, t.gate = ops.se_fwd(pooled, 1.0 / (ho * wo), m._se_reduce.weight.view(b.se, b.cexp), m._se_reduce.bias,
                                       m._se_expand.weight.view(b.cexp, b.se), m._se_expand.bias)
         st2 = None
-        if b.cout > MATERIALISE_ABOVE:
+        if project_materialises(b, Mo, True):              # (the tape path, whatever the BatchNorm mode)
             # With several N tiles the BN+SiLU+gate prologue would be recomputed (and its scale/shift/gate re-loaded
             # through the per-CU load path) once per tile: measured 100 -> 63 TFLOP/s at K=3840, N=640.  One streaming
             # pass writes the activated tensor instead; it is kept for the weight gradient.
@@ -378,29 +388,72 @@ class GradSink:
         return g
 
 
-# BatchNorm-0 backward apply folded into both consumers of dZ = c1*G + c2*X + c3 in stages 1-2 (expand convs 32 -> 192, 48 -> 288 at
-# 0.4-1.6 M rows): there the data gradient (planes kernel) and the weight gradient (wgrad_small_kernel<..., GBN>) are HBM-bound, and
-# forming dZ in their operand loads trades a 3-pass kernel for one more operand stream in two kernels that wait on memory anyway.
-# MUSCLE_FOLD_BN0_EARLY=0 restores the pass.  (The folds that were measured and lost are in DESIGN.md; their kernels are lab code.)
-FOLD_BN0_EARLY = os.environ.get("MUSCLE_FOLD_BN0_EARLY", "1") == "1"
-# The stride-2 blocks hand over BN0 partial sums too since their depthwise backward is fused, so B7's block 4 (1.6 M rows, 192 -> 32)
-# would qualify.  Measured with that block forced onto and off the fold, alternating on one MI355X: 93.41 against 93.44 ms per step,
-# inside either setting's own spread (profiles/dw_s2_fused_ab.txt) - no gain to tell from noise, so the stride-2 blocks keep the plain
-# apply and the fold stays what it was: stride-1 blocks only.
+class BlockRoute(NamedTuple):
+    """Which kernels one block's backward takes, stage by stage (block_route decides, the three stage functions dispatch on it)."""
+    project: str     # "fused" (pw_proj_bwd_fused) | "gemm" (pw_wgrad + pw_dgrad, then se_bn1_pool)
+    depthwise: str   # "fused" (dwconv_bwd_fused) | "fused_s2" (dwconv_bwd_fused_s2) | "unfused" (apply, weight, data: no BN0 partial sums)
+    expand: str      # "none" (no BatchNorm in front of the depthwise conv) | "plain" (bn_backward with act=) | after bn_bwd_coeffs:
+    #                  "apply" (bn_bwd_apply_plain, then the GEMMs) | "fold" (pw_wgrad_bnbwd + pw_dgrad_bnbwd_planes) | "fused" (pw_bwd_fused)
+
+
+# The four schedule switches.  Each reads its environment variable at import and can be flipped at run time (`engine.DW_S2_FUSED =
+# False`); block_route is their only reader.
+#
 # Stride-2 depthwise backward as ONE kernel (ops.dwconv_bwd_fused_s2), as stride 1 has had it since round 1.  MUSCLE_DW_S2_FUSED=0
-# (or flipping `engine.DW_S2_FUSED` at run time) restores bn_bwd_apply + dwconv_bwd_weight + dwconv_bwd_data + the BN0 reduction.
+# restores bn_bwd_apply + dwconv_bwd_weight + dwconv_bwd_data + the BN0 reduction.
 DW_S2_FUSED = os.environ.get("MUSCLE_DW_S2_FUSED", "1") == "1"
-# Expand convs whose data AND weight gradients are HBM-bound (288 x 48 and 192 x 32 of stage 2, either stride): where
-# ops.bnbwd_fold_takes answers "fused", one kernel (ops.pw_bwd_fused) reads (gx, e_raw) once and leaves both gradients; the apply
-# pass, the data-gradient GEMM and the lane's weight-gradient entry are gone for those blocks.  MUSCLE_PW_BWD_FUSED=0 (or flipping
-# `engine.PW_BWD_FUSED` at run time) restores the schedule above.
-PW_BWD_FUSED = os.environ.get("MUSCLE_PW_BWD_FUSED", "1") == "1"
 # Project convs whose data AND weight gradients are HBM-bound (48 x 288 and 48 x 192 of stage 2, read through the BN1 + SiLU + gate
 # prologue): where ops.pw_proj_bwd_fused_takes says so, one kernel (ops.pw_proj_bwd_fused) reads (dp, d_raw) once and leaves dA, the
 # weight gradient's partial matrices and the five sums of se_bn1_pool; the data-gradient GEMM, the lane's weight-gradient entry and the
-# se_bn1_pool pass are gone for those blocks.  MUSCLE_PW_PROJ_BWD_FUSED=0 (or flipping `engine.PW_PROJ_BWD_FUSED` at run time)
-# restores the schedule above.
+# se_bn1_pool pass are gone for those blocks.  MUSCLE_PW_PROJ_BWD_FUSED=0 restores them.
 PW_PROJ_BWD_FUSED = os.environ.get("MUSCLE_PW_PROJ_BWD_FUSED", "1") == "1"
+# Expand convs whose data AND weight gradients are HBM-bound (288 x 48 and 192 x 32 of stage 2, either stride): where
+# ops.pw_bwd_fused_takes says so, one kernel (ops.pw_bwd_fused) reads (gx, e_raw) once and leaves both gradients; the apply pass, the
+# data-gradient GEMM and the lane's weight-gradient entry are gone for those blocks.  MUSCLE_PW_BWD_FUSED=0 restores them.
+PW_BWD_FUSED = os.environ.get("MUSCLE_PW_BWD_FUSED", "1") == "1"
+# Gates EVERY route that forms dZ = c1*G + c2*X + c3 of the BatchNorm-0 backward inside the expand conv's own kernels instead of in a
+# bn_bwd_apply_plain pass: the early fold it is named after AND the fused expand backward above.  The fold: in stages 1-2 (expand
+# convs 32 -> 192, 48 -> 288 at 0.4-1.6 M rows) the data gradient (planes kernel) and the weight gradient (wgrad_small_kernel<..., GBN>)
+# are HBM-bound, and forming dZ in their operand loads trades a 3-pass kernel for one more operand stream in two kernels that wait on
+# memory anyway.  MUSCLE_FOLD_BN0_EARLY=0 restores the apply pass for every block.  (The folds that were measured and lost are in
+# DESIGN.md.)  The fold is for stride-1 blocks only: the stride-2 blocks hand over BN0 partial sums too since their depthwise backward
+# is fused, so B7's block 4 (1.6 M rows, 192 -> 32) would qualify; measured with that block forced onto and off the fold, alternating on
+# one MI355X: 93.41 against 93.44 ms per step, inside either setting's own spread (profiles/dw_s2_fused_ab.txt) - no gain to tell from
+# noise.
+FOLD_BN0_EARLY = os.environ.get("MUSCLE_FOLD_BN0_EARLY", "1") == "1"
+
+
+def block_route(b: BlockCfg, N, H, W, Ho, Wo, *, materialised: bool, wt_planes: bool) -> BlockRoute:
+    """The backward route of block `b` at batch N, H x W in, Ho x Wo out.  materialised: the forward kept the activated project input
+    (BlockTape.a); wt_planes: a pre-split image of the expand weight's transpose is on the tape (Tape.wtp).  Reads the four switches
+    above and asks `ops` which shapes its kernels take; touches no tensor and launches nothing."""
+    M, Mo = N * H * W, N * Ho * Wo
+    project = "fused" if not materialised and PW_PROJ_BWD_FUSED and ops.pw_proj_bwd_fused_takes(Mo, b.cout, b.cexp, Ho * Wo) else "gemm"
+    behind_bn = b.expand or b.index == 0         # the depthwise input is read through BN0 + SiLU, or (block 0) the stem's
+    if b.stride == 1 and b.pad_lo == (b.kernel - 1) // 2:
+        depthwise = "fused"
+    elif DW_S2_FUSED and b.stride == 2 and behind_bn:       # (every stride-2 block of the model family has an expand conv)
+        depthwise = "fused_s2"
+    else:
+        depthwise = "unfused"
+    if not behind_bn:
+        return BlockRoute(project, depthwise, "none")
+    if depthwise == "unfused":
+        return BlockRoute(project, depthwise, "plain")
+    # Two quirks of this rule are KEPT ON PURPOSE (they are what the schedule has always done; changing either is a measured change):
+    #  - FOLD_BN0_EARLY off also switches off the fused expand backward, not only the fold;
+    #  - a stride-1 block is eligible only where a pre-split image of W^T exists, although only the fold reads it and pw_bwd_fused
+    #    never does: in exact-fp32 arithmetic (no images) stride-1 blocks never take the fused kernel, while stride-2 blocks do.
+    eligible = FOLD_BN0_EARLY and b.expand and (wt_planes if b.stride == 1 else PW_BWD_FUSED)
+    if eligible and PW_BWD_FUSED and ops.pw_bwd_fused_takes(M, b.cexp, b.cin):
+        expand = "fused"
+    elif eligible and b.stride == 1 and ops.bnbwd_fold_small_takes(M, b.cexp, b.cin):
+        expand = "fold"
+    else:
+        expand = "apply"
+    return BlockRoute(project, depthwise, expand)
+
+
 # Weight-gradient GEMMs on a second HIP stream (MUSCLE_WGRAD_STREAM=0 turns it off; `engine.WGRAD_SIDE_STREAM` can be
 # flipped at run time).  Nothing in the backward chain consumes them (only the optimizer and the gradient exchange do),
 # they are MFMA-bound, and the chain between two of them (BN backward, SE, depthwise) is HBM-bound.  Measured on
@@ -481,24 +534,21 @@ def _dw_input(t: BlockTape):
     return (t.e_raw, t.bn0) if t.cfg.expand else (t.x, t.x_st)
 
 
-def _project_backward(lane, tape: Tape, t: BlockTape, m, g_out, sink: GradSink):
+def _project_backward(lane, tape: Tape, t: BlockTape, m, g_out, sink: GradSink, route: str):
     """g_out --BN2 bwd--> dp --pw_wgrad / pw_dgrad--> dA = dL/d(act*gate) [Mo, Cexp].  Returns (dA, the five SE / BN1 sums where the
-    fused kernel has formed them, else None)."""
+    fused kernel has formed them, else None).  route: BlockRoute.project."""
     b, hw = t.cfg, t.Ho * t.Wo
     Mo = tape.N * hw
     # BN2 backward (upstream gradient carries the drop_connect scale of the sample)
     dp = ops.bn_backward(g_out.reshape(Mo, b.cout), t.p_raw, m._bn2, t.bn2, sink.of(m._bn2.weight), sink.of(m._bn2.bias), tape.training,
                          row_scale=t.row_scale, rows_per_sample=hw)
-    if t.a is None and PW_PROJ_BWD_FUSED:
-        # (asked outside the call log of a stand-in for `ops`: one that does not know the kernel answers no)
-        takes = getattr(ops, "pw_proj_bwd_fused_takes", None)
-        if takes is not None and takes(Mo, b.cout, b.cexp, hw):
-            # one kernel on the main stream reads (dp, d_raw) once and leaves dA, the partial matrices of dW and the sums of
-            # se_bn1_pool; only the addition of the partial matrices goes to the lane
-            ga, pooled5 = ops.pw_proj_bwd_fused(dp, t.d_raw.view(Mo, b.cexp), t.bn1, t.gate, hw, m._project_conv.weight.view(b.cout, b.cexp),
-                                                sink.of(m._project_conv.weight).view(b.cout, b.cexp), defer=lane.pw_reduce)
-            lane.flush()
-            return ga, pooled5
+    if route == "fused":
+        # one kernel on the main stream reads (dp, d_raw) once and leaves dA, the partial matrices of dW and the sums of
+        # se_bn1_pool; only the addition of the partial matrices goes to the lane
+        ga, pooled5 = ops.pw_proj_bwd_fused(dp, t.d_raw.view(Mo, b.cexp), t.bn1, t.gate, hw, m._project_conv.weight.view(b.cout, b.cexp),
+                                            sink.of(m._project_conv.weight).view(b.cout, b.cexp), defer=lane.pw_reduce)
+        lane.flush()
+        return ga, pooled5
     # project conv: weight gradient against the recomputed activated+gated input, then data gradient
     if t.a is not None:
         lane.wgrad(dp, t.a, sink.of(m._project_conv.weight).view(b.cout, b.cexp))
@@ -529,20 +579,20 @@ def _se_bn1_coeffs(tape: Tape, t: BlockTape, m, ga, pooled5, sink: GradSink):
                           sink.of(m._bn1.weight), sink.of(m._bn1.bias), tape.training)
 
 
-def _depthwise_backward(lane, tape: Tape, t: BlockTape, m, ga, c1, add, skip_res, sink: GradSink):
+def _depthwise_backward(lane, tape: Tape, t: BlockTape, m, ga, c1, add, skip_res, sink: GradSink, route: str):
     """BN1 data gradient + depthwise conv backward.  Returns (gx = gradient at the depthwise input's activation, the BatchNorm
     backward sums of that input where the fused kernel has formed them, else None).  skip_res (the identity branch's gradient)
-    is added here only where the depthwise input is the block input itself."""
+    is added here only where the depthwise input is the block input itself.  route: BlockRoute.depthwise."""
     b, N = t.cfg, tape.N
     dw_in, dw_st = _dw_input(t)
     res = None if dw_st is not None else skip_res
-    if b.stride == 1 and b.pad_lo == (b.kernel - 1) // 2:
+    if route == "fused":
         # stride 1: BN1 data gradient, depthwise weight + data gradients and the BN0 backward sums in one kernel
         return ops.dwconv_bwd_fused(ga.view(N, t.Ho, t.Wo, b.cexp), t.d_raw, t.gate, add, t.bn1, c1, dw_in, dw_st,
                                     m._depthwise_conv.weight, sink.of(m._depthwise_conv.weight), b.kernel, b.pad_lo,
                                     residual=res, defer=lane.dw_reduce)
-    if DW_S2_FUSED and b.stride == 2 and dw_st is not None:
-        # stride 2 behind a BatchNorm (every stride-2 block of the model family has an expand conv): the same fusion
+    if route == "fused_s2":
+        # stride 2 behind a BatchNorm: the same fusion
         return ops.dwconv_bwd_fused_s2(ga.view(N, t.Ho, t.Wo, b.cexp), t.d_raw, t.gate, add, t.bn1, c1, dw_in, dw_st,
                                        m._depthwise_conv.weight, sink.of(m._depthwise_conv.weight), b.kernel, b.pad_lo,
                                        defer=lane.dw_reduce)
@@ -553,34 +603,29 @@ def _depthwise_backward(lane, tape: Tape, t: BlockTape, m, ga, c1, add, skip_res
     return ops.dwconv_bwd_data(dd, m._depthwise_conv.weight, b.kernel, b.stride, b.pad_lo, t.H, t.W, residual=res), None
 
 
-def _bn0_expand_backward(lane, backbone, cfg: NetCfg, tape: Tape, t: BlockTape, m, gx, part0, skip_res, sink: GradSink):
+def _bn0_expand_backward(lane, backbone, cfg: NetCfg, tape: Tape, t: BlockTape, m, gx, part0, skip_res, sink: GradSink, route: str):
     """The depthwise input sits behind a BatchNorm + SiLU (BN0 of an expand block, or the stem's BN for block 0):
-    gx --BN0 bwd--> dz --pw_wgrad / pw_dgrad (+skip gradient)--> g_in [N,H,W,Cin]; block 0 ends in the stem's weight gradient (None)."""
+    gx --BN0 bwd--> dz --pw_wgrad / pw_dgrad (+skip gradient)--> g_in [N,H,W,Cin]; block 0 ends in the stem's weight gradient (None).
+    route: BlockRoute.expand, never "none"; part0: the BN0 backward sums of a fused depthwise backward (every route but "plain")."""
     b, N, training = t.cfg, tape.N, tape.training
     dw_in, dw_st = _dw_input(t)
     bn_mod = m._bn0 if b.expand else backbone._bn0
     M = N * t.H * t.W
     raw2, gx2 = dw_in.view(M, dw_in.shape[3]), gx.view(M, dw_in.shape[3])
     res = skip_res.reshape(M, b.cin) if skip_res is not None else None
-    if part0 is not None:
+    if route != "plain":
         c0 = ops.bn_bwd_coeffs(part0, M, bn_mod, dw_st, sink.of(bn_mod.weight), sink.of(bn_mod.bias), training)
-        wtp = tape.wtp.get(id(m._expand_conv.weight)) if b.expand else None
-        takes = None
-        if FOLD_BN0_EARLY and b.expand and (wtp is not None if b.stride == 1 else PW_BWD_FUSED):
-            takes = ops.bnbwd_fold_takes(M, b.cexp, b.cin)
-            if takes == "fused" and not PW_BWD_FUSED:
-                takes = ops.bnbwd_fold_takes_split(M, b.cexp, b.cin)
-        if takes == "fused":
+        if route == "fused":
             # one kernel on the main stream forms dz slab by slab and leaves both gradients; only the addition of its partial
             # matrices goes to the lane
             g_in = ops.pw_bwd_fused(gx2, raw2, c0, t.x.view(M, b.cin), m._expand_conv.weight.view(b.cexp, b.cin),
                                     sink.of(m._expand_conv.weight).view(b.cexp, b.cin), residual=res, defer=lane.pw_reduce)
             lane.flush()
             return g_in.view(N, t.H, t.W, b.cin)
-        if takes == "small" and b.stride == 1:
+        if route == "fold":
             # the early fold: both GEMMs form dz in their operand loads, it is never written
             lane.wgrad_bnbwd(gx2, raw2, c0, t.x.view(M, b.cin), sink.of(m._expand_conv.weight).view(b.cexp, b.cin))
-            g_in = ops.pw_dgrad_bnbwd_planes(gx2, raw2, c0, wtp, b.cin, residual=res)
+            g_in = ops.pw_dgrad_bnbwd_planes(gx2, raw2, c0, tape.wtp[id(m._expand_conv.weight)], b.cin, residual=res)
             lane.flush()
             return g_in.view(N, t.H, t.W, b.cin)
         dz = ops.bn_bwd_apply_plain(gx2, raw2, c0, gx2)
@@ -614,13 +659,16 @@ def backbone_backward(backbone, cfg: NetCfg, tape: Tape, tap_grads: Dict[int, to
             g_out = tg if g_out is None else g_out + tg
         if g_out is None:
             continue                                   # blocks after the last tap get no gradient
-        ga, pooled5 = _project_backward(lane, tape, t, m, g_out, sink)
+        b = t.cfg
+        route = block_route(b, tape.N, t.H, t.W, t.Ho, t.Wo, materialised=t.a is not None,
+                            wt_planes=b.expand and id(m._expand_conv.weight) in tape.wtp)
+        ga, pooled5 = _project_backward(lane, tape, t, m, g_out, sink, route.project)
         c1, add = _se_bn1_coeffs(tape, t, m, ga, pooled5, sink)
-        skip_res = g_out if t.cfg.skip else None        # d out / d x through the identity branch
-        gx, part0 = _depthwise_backward(lane, tape, t, m, ga, c1, add, skip_res, sink)
+        skip_res = g_out if b.skip else None            # d out / d x through the identity branch
+        gx, part0 = _depthwise_backward(lane, tape, t, m, ga, c1, add, skip_res, sink, route.depthwise)
         del ga
-        if _dw_input(t)[1] is not None:
-            g_out = _bn0_expand_backward(lane, backbone, cfg, tape, t, m, gx, part0, skip_res, sink)
+        if route.expand != "none":
+            g_out = _bn0_expand_backward(lane, backbone, cfg, tape, t, m, gx, part0, skip_res, sink, route.expand)
         else:
             g_out = gx
         if done is not None:

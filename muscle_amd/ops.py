@@ -260,33 +260,32 @@ def pw_dgrad(G, W, N_in, *, residual=None, out=None, wt=None, planes=None):
 
 def pw_dgrad_bnbwd_planes(G, X, coef, planes, N_in, *, residual=None):
     """dX = dZ W with dZ = c1*G + c2*X + c3 formed in the GEMM's operand load (second-generation split kernel, W^T given as its
-    pre-split image); dZ is not materialised - the weight gradient folds the same expression (pw_wgrad_bnbwd)."""
+    pre-split image); dZ is not materialised - the weight gradient folds the same expression (pw_wgrad_bnbwd).  The data-gradient
+    half of bnbwd_fold_small_takes."""
     M, K = G.shape
     out = _f32(M, N_in, device=G.device)
     call("mx_pw_dgrad_bnbwd_planes", ptr(G), ptr(X), ptr(coef), planes, ptr(out), M, K, N_in, G.stride(0), N_in, ptr(residual), stream())
     return out
 
 
-def bnbwd_fold_takes(M, K, N):
-    """Which kernel can fold the BatchNorm backward apply for dZ [M, K] (data gradient against W^T [N, K], weight gradient
-    dW [K, N]) in the current arithmetic: "fused" (pw_bwd_fused: both gradients from one pass, exact fp32 in every arithmetic), or,
-    given that the data gradient takes the planes kernel, "small" (the HBM-bound small-output weight-gradient kernel of stages 1-2),
-    or None."""
-    if lib().mx_pw_bwd_small_fused_ok(M, K, N):
-        return "fused"
-    return bnbwd_fold_takes_split(M, K, N)
+def pw_bwd_fused_takes(M, K, N) -> bool:
+    """True where pw_bwd_fused takes the whole backward of an expand conv with dZ [M, K] and W [K, N] (mx_pw_bwd_small_fused_ok): both
+    gradients from one pass, exact fp32 in every arithmetic."""
+    return bool(lib().mx_pw_bwd_small_fused_ok(M, K, N))
 
 
 @_per_mode
-def bnbwd_fold_takes_split(M, K, N):
-    """bnbwd_fold_takes without the fused kernel: "small" or None (the answer where pw_bwd_fused is switched off)."""
-    if _planes_take(M, K, N) and lib().mx_pw_wgrad_small_bnbwd_ok(M, K, N):
-        return "small"
-    return None
+def bnbwd_fold_small_takes(M, K, N) -> bool:
+    """True where both GEMMs of an expand conv's backward can fold the BatchNorm backward apply for dZ [M, K] in the current
+    arithmetic: the data gradient against W^T [N, K] takes the planes kernel (pw_dgrad_bnbwd_planes) AND the weight gradient dW [K, N]
+    takes the HBM-bound small-output kernel of stages 1-2 (pw_wgrad_bnbwd, mx_pw_wgrad_small_bnbwd_ok).  Which of this and
+    pw_bwd_fused_takes wins is engine.block_route's business."""
+    return bool(_planes_take(M, K, N) and lib().mx_pw_wgrad_small_bnbwd_ok(M, K, N))
 
 
 def pw_wgrad_bnbwd(G, G2, coef, X, dW):
-    """dW[Co, Ci] += (c1*G + c2*G2 + c3)[R, Co]^T X[R, Ci] in the small-output weight-gradient kernel (bnbwd_fold_takes == "small")."""
+    """dW[Co, Ci] += (c1*G + c2*G2 + c3)[R, Co]^T X[R, Ci] in the small-output weight-gradient kernel (the weight-gradient half of
+    bnbwd_fold_small_takes)."""
     R, Co = G.shape
     Ci = X.shape[1]
     if not lib().mx_pw_wgrad_small_bnbwd_ok(R, Co, Ci):
@@ -312,7 +311,7 @@ def pw_parts_reduce(part, dW):
 
 
 def pw_bwd_fused(G, G2, coef, X, W, dW, *, residual=None, defer=None, out=None):
-    """The whole backward of a small expand conv (bnbwd_fold_takes == "fused": 288 x 48 and 192 x 32) in one pass over its wide
+    """The whole backward of a small expand conv (pw_bwd_fused_takes: 288 x 48 and 192 x 32) in one pass over its wide
     operands: dW[Co, Ci] += dZ^T X and dX[R, Ci] = dZ W (+ residual), with dZ = c1*G + c2*G2 + c3 (coef [3, Co]) or dZ = G where
     G2 and coef are None.  Returns dX.  Operands may be row views (leading dimension larger than the width); `out`, if given, is
     dX's buffer and `residual` must share its leading dimension.

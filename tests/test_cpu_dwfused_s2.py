@@ -13,6 +13,7 @@ from muscle_amd import _lib
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "dw_s2_calls_b0.txt")
 ENTRIES = ("mx_dwconv_bwd_fused_s2_parts", "mx_dwconv_bwd_fused_s2")
+QUERY = "bnbwd_fold_takes("             # how the golden log spells the query the engine made through `ops` when it was recorded
 
 
 def test_header_declares_and_library_exports():
@@ -69,7 +70,7 @@ def _describe(v):
 
 class RecordingOps:
     """Every ops.* call logged with the shapes of its tensor arguments and its keyword arguments; results are empty CPU tensors of
-    the shapes the real calls return.  bnbwd_fold_takes answers "small" from 512 rows, else None."""
+    the shapes the real calls return.  It knows neither fused pointwise backward; the small fold takes a shape from 512 rows."""
     PLAIN, BNACT, AFFINE = 0, 1, 2
 
     def __init__(self):
@@ -139,8 +140,15 @@ class RecordingOps:
     def _r_bn_bwd_apply_plain(self, G, X, c, out):
         return out
 
-    def _r_bnbwd_fold_takes(self, M, K, N):
-        return "small" if M >= 512 else None
+    # the queries engine.block_route makes: ordinary methods, not logged
+    def pw_proj_bwd_fused_takes(self, R, Cout, Cexp, rows_per_sample):
+        return False
+
+    def pw_bwd_fused_takes(self, M, K, N):
+        return False
+
+    def bnbwd_fold_small_takes(self, M, K, N):
+        return M >= 512
 
 
 def _b0_tape(N=2, S=32):
@@ -171,7 +179,7 @@ def _b0_tape(N=2, S=32):
             expands += 1
         t.d_raw, t.bn1 = e(N, ho, ho, b.cexp), st(b.cexp)
         t.s, t.h, t.gate = e(N, b.cexp), e(N, b.se), e(N, b.cexp)
-        if b.cout > engine.MATERIALISE_ABOVE:
+        if engine.project_materialises(b, N * ho * ho, True):
             t.a = e(N * ho * ho, b.cexp)
         t.p_raw, t.bn2 = e(N * ho * ho, b.cout), st(b.cout)
         t.out = e(N, ho, ho, b.cout)
@@ -181,6 +189,25 @@ def _b0_tape(N=2, S=32):
     return backbone, cfg, tape, taps
 
 
+def _routes(tape, backbone):
+    """engine.block_route of every block of a fresh tape, asked as backbone_backward asks it (under the switches and the `engine.ops`
+    in force)."""
+    from muscle_amd import engine
+    return [engine.block_route(t.cfg, tape.N, t.H, t.W, t.Ho, t.Wo, materialised=t.a is not None,
+                               wt_planes=t.cfg.expand and id(backbone._blocks[t.cfg.index]._expand_conv.weight) in tape.wtp)
+            for t in tape.blocks]
+
+
+def _golden_calls():
+    """(the kernel calls of tests/golden/dw_s2_calls_b0.txt, the arguments of its query lines).  The file was recorded when the engine
+    asked `ops.bnbwd_fold_takes(M, K, N)` through the call log; queries are no longer `ops` calls the stand-in logs, so those eight
+    lines are dropped before comparing - every other line, and its position among the others, must match exactly."""
+    lines = open(GOLDEN).read().splitlines()
+    asked = [tuple(int(v) for v in c[len(QUERY):-1].split(", ")) for c in lines if c.startswith(QUERY)]
+    assert len(asked) == 8
+    return [c for c in lines if not c.startswith(QUERY)], asked
+
+
 def _record(monkeypatch, fused: bool):
     from muscle_amd import engine
     rec = RecordingOps()
@@ -188,14 +215,29 @@ def _record(monkeypatch, fused: bool):
     monkeypatch.setattr(engine, "WGRAD_SIDE_STREAM", False)
     monkeypatch.setattr(engine, "DW_S2_FUSED", fused)
     backbone, cfg, tape, taps = _b0_tape()
+    routes = _routes(tape, backbone)
     engine.backbone_backward(backbone, cfg, tape, taps, engine.GradSink())
-    return rec.calls, cfg
+    return rec.calls, cfg, tape, backbone, routes
+
+
+def _want_expand(t, tape, backbone, dw_s2: bool):
+    """BlockRoute.expand of the base stand-in (no fused expand backward, the small fold from 512 rows) with the default switches."""
+    b, M = t.cfg, tape.N * t.H * t.W
+    if not b.expand and b.index != 0:
+        return "none"
+    if b.stride == 2 and not dw_s2:
+        return "plain"
+    image = b.expand and id(backbone._blocks[b.index]._expand_conv.weight) in tape.wtp
+    return "fold" if b.stride == 1 and image and M >= 512 else "apply"
 
 
 def test_stride2_blocks_take_the_fused_call(monkeypatch):
-    calls, cfg = _record(monkeypatch, True)
+    calls, cfg, tape, backbone, routes = _record(monkeypatch, True)
     s2 = [b for b in cfg.blocks if b.stride == 2]
     assert len(s2) == 3 and all(b.expand for b in s2)
+    assert [r.depthwise for r in routes] == ["fused_s2" if b.stride == 2 else "fused" for b in cfg.blocks]
+    assert [r.expand for r in routes] == [_want_expand(t, tape, backbone, True) for t in tape.blocks]
+    assert {r.project for r in routes} == {"gemm"}
     names = [c.split("(")[0] for c in calls]
     assert names.count("dwconv_bwd_fused_s2") == 3
     got = sorted(c for c in calls if c.startswith("dwconv_bwd_fused_s2("))
@@ -212,11 +254,23 @@ def test_stride2_blocks_take_the_fused_call(monkeypatch):
 
 
 def test_flag_off_restores_the_previous_schedule(monkeypatch):
-    calls, cfg = _record(monkeypatch, False)
-    want = open(GOLDEN).read().splitlines()
+    """The call log with engine.DW_S2_FUSED off is tests/golden/dw_s2_calls_b0.txt, which stays as it was recorded: its eight
+    `bnbwd_fold_takes(` lines are dropped before the comparison (_golden_calls), every other line and its position must match.  What
+    those eight lines said is asserted on the routes instead: the blocks the engine asked about, in the order it asked, are the
+    stride-1 expand blocks with an image of W^T - exactly the blocks that can take the fold - and each route is the answer's."""
+    calls, cfg, tape, backbone, routes = _record(monkeypatch, False)
+    want, asked = _golden_calls()
     assert calls == want
+    assert [r.depthwise for r in routes] == ["unfused" if b.stride == 2 else "fused" for b in cfg.blocks]
+    assert [r.expand for r in routes] == [_want_expand(t, tape, backbone, False) for t in tape.blocks]
+    assert {r.project for r in routes} == {"gemm"}
+    could_fold = [(tape.N * t.H * t.W, t.cfg.cexp, t.cfg.cin) for t, r in zip(tape.blocks, routes)
+                  if t.cfg.expand and r.expand in ("fold", "apply") and id(backbone._blocks[t.cfg.index]._expand_conv.weight) in tape.wtp]
+    assert could_fold[::-1] == asked                                                            # (the backward walks the blocks in reverse)
+    assert [r.expand for r in routes].count("fold") == sum(M >= 512 for M, _, _ in asked) == 1
     names = [c.split("(")[0] for c in calls]
     assert "dwconv_bwd_fused_s2" not in names
     for back in ("bn_backward_from_coeffs", "dwconv_bwd_weight", "dwconv_bwd_data"):
         assert names.count(back) == 3, back
     assert len([c for c in calls if c.startswith("bn_backward(") and "act=BNState" in c]) == 3
+

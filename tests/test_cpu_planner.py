@@ -45,6 +45,25 @@ def test_planners_reproduce_the_snapshot(restore_settings):
     assert not bad, f"{len(bad)} of {len(snap['rows'])} rows differ, first: {bad[:3]}"
 
 
+def test_backward_routes_reproduce_the_snapshot(restore_settings):
+    """engine.block_route, with the library answering its queries, gives every block of the two training steps bench.py times the
+    route recorded in the snapshot's "backward_routes" section - which was read off the engine's call log before block_route existed."""
+    from muscle_amd import arch
+    L, tool = restore_settings, _tool()
+    runs = json.load(open(os.path.join(ROOT, "tests", "planner_snapshot.json")))["backward_routes"]
+    assert [(r["model"], r["size"], r["batch"], r["gemm_mode"]) for r in runs] == [(*run, g) for run in tool.ROUTE_RUNS for g in tool.ROUTE_MODES]
+    for r in runs:
+        assert len(r["routes"]) == len(arch.net_cfg(r["model"], False).blocks)
+        got = tool.backward_routes(L, r["model"], r["size"], r["batch"], r["gemm_mode"])
+        bad = [(i, g, w) for i, (g, w) in enumerate(zip(got, r["routes"])) if g != w]
+        assert not bad, (r["model"], r["gemm_mode"], bad[:5])
+    # not a table of defaults: B7 takes both fused pointwise backwards, in split arithmetic on more blocks than in exact fp32 (no
+    # images of W^T there: the stride-1 quirk block_route keeps)
+    b7 = {r["gemm_mode"]: r["routes"] for r in runs if r["model"] == "efficientnet-b7"}
+    assert sum(x[0] == "fused" for x in b7[1]) >= 2 and {x[1] for x in b7[1]} == {"fused", "fused_s2"}
+    assert sum(x[2] == "fused" for x in b7[1]) > sum(x[2] == "fused" for x in b7[0]) >= 1
+
+
 def test_the_pipelined_wgrad_kernel_is_gone(restore_settings):
     L = restore_settings
     assert L.mx_set_wgrad_kernel(2, 0) == 0

@@ -1,14 +1,14 @@
 """Host side of the fused expand-conv backward (no kernel is launched): the header declares the entry points and the library exports
 them, argument errors come back as MX_EARG before any launch, the planner queries answer for the two shapes only, and the backward
-schedule of engine.backbone_backward - run against a recording stand-in for muscle_amd.ops whose bnbwd_fold_takes answers "fused" -
-issues exactly one pw_bwd_fused per eligible block of either stride and nothing else for that conv; with engine.PW_BWD_FUSED off
-the call log is the one recorded before the kernel existed."""
+schedule of engine.backbone_backward - run against a recording stand-in for muscle_amd.ops whose pw_bwd_fused_takes answers yes -
+issues exactly one pw_bwd_fused per eligible block of either stride and nothing else for that conv, as engine.block_route says for
+those blocks; with engine.PW_BWD_FUSED off the call log is the one recorded before the kernel existed."""
 import ctypes
 
 import torch
 
 from muscle_amd import _lib
-from test_cpu_dwfused_s2 import GOLDEN, RecordingOps, _b0_tape
+from test_cpu_dwfused_s2 import RecordingOps, _b0_tape, _golden_calls, _routes
 
 
 def test_header_declares_and_library_exports():
@@ -56,16 +56,13 @@ def test_bad_arguments_before_any_launch():
         assert b"pw_parts_reduce" in L.mx_last_error(), args
 
 
-# ---- the backward schedule against a recording stand-in whose bnbwd_fold_takes answers "fused" --------------------------------------
+# ---- the backward schedule against a recording stand-in whose pw_bwd_fused_takes answers yes ----------------------------------------
 class FusedRecordingOps(RecordingOps):
-    """RecordingOps whose bnbwd_fold_takes answers "fused" from 512 rows; its unfused answer (not logged: the engine asks it only with the
-    switch off) is the parent's."""
+    """RecordingOps whose fused expand-conv backward takes a shape from 512 rows - the rows from which the parent's small fold takes it
+    too, so that every block the fused kernel takes is one the fold would take with the switch off."""
 
-    def _r_bnbwd_fold_takes(self, M, K, N):
-        return "fused" if M >= 512 else RecordingOps._r_bnbwd_fold_takes(self, M, K, N)
-
-    def bnbwd_fold_takes_split(self, M, K, N):
-        return RecordingOps._r_bnbwd_fold_takes(self, M, K, N)
+    def pw_bwd_fused_takes(self, M, K, N):
+        return M >= 512
 
     def _r_pw_bwd_fused(self, G, G2, coef, X, W, dW, *, residual=None, defer=None):
         if defer is not None:
@@ -83,12 +80,13 @@ def _record(monkeypatch, rec, *, pw_fused: bool, dw_s2: bool = True):
     monkeypatch.setattr(engine, "DW_S2_FUSED", dw_s2)
     monkeypatch.setattr(engine, "PW_BWD_FUSED", pw_fused)
     backbone, cfg, tape, taps = _b0_tape()
+    routes = _routes(tape, backbone)
     engine.backbone_backward(backbone, cfg, tape, taps, engine.GradSink())
-    return rec.calls, cfg, tape, backbone
+    return rec.calls, cfg, tape, backbone, routes
 
 
 def _eligible(cfg, tape, backbone):
-    """(block, M) of the expand blocks the stand-in answers "fused" for: part0 is there (every expand block with the stride-2 depthwise
+    """(block, M) of the expand blocks the stand-in's fused kernel takes: part0 is there (every expand block with the stride-2 depthwise
     backward fused), 512 rows or more, and - stride 1 only, as before - a pre-split image of W^T."""
     out = []
     for t in tape.blocks:
@@ -100,9 +98,12 @@ def _eligible(cfg, tape, backbone):
 
 
 def test_eligible_blocks_take_exactly_one_fused_call(monkeypatch):
-    calls, cfg, tape, backbone = _record(monkeypatch, FusedRecordingOps(), pw_fused=True)
+    calls, cfg, tape, backbone, routes = _record(monkeypatch, FusedRecordingOps(), pw_fused=True)
     blocks = _eligible(cfg, tape, backbone)
     assert {b.stride for b, _ in blocks} == {1, 2} and any(b.skip for b, _ in blocks) and not all(b.skip for b, _ in blocks)
+    # the route: "fused" for exactly those blocks, and the small fold - which takes the same rows - never ranks above it
+    took = {b.index for b, _ in blocks}
+    assert [r.expand for r in routes] == ["fused" if b.index in took else "apply" if b.expand or b.index == 0 else "none" for b in cfg.blocks]
     fused = [c for c in calls if c.startswith("pw_bwd_fused(")]
     assert len(fused) == len(blocks)
     for b, M in blocks:
@@ -115,20 +116,26 @@ def test_eligible_blocks_take_exactly_one_fused_call(monkeypatch):
             assert not [c for c in calls if c.startswith(f"{gone}(T[{M}, {b.cexp}], ")], (gone, b.index)
     names = [c.split("(")[0] for c in calls]
     assert names.count("pw_parts_reduce") == len(blocks)                          # every partial-matrix sum is added, through the lane
-    assert "bnbwd_fold_takes_split" not in names
+    assert not [n for n in names if n.endswith("_takes")]                         # the queries are not `ops` calls in the log
     # the other expand convs keep their calls
-    others = [t for t in tape.blocks if t.cfg.expand and t.cfg.index not in {b.index for b, _ in blocks}]
+    others = [t for t in tape.blocks if t.cfg.expand and t.cfg.index not in took]
     assert others and names.count("pw_dgrad") + names.count("pw_dgrad_bnbwd_planes") == len(tape.blocks) + len(others)
 
 
 def test_switch_off_restores_todays_log(monkeypatch):
-    """With engine.PW_BWD_FUSED off the stand-in that answers "fused" gives the call log of the one that answers "small" - and, with the
-    stride-2 depthwise fusion off as well, the golden log recorded before either kernel existed."""
-    off, *_ = _record(monkeypatch, FusedRecordingOps(), pw_fused=False)
-    today, *_ = _record(monkeypatch, RecordingOps(), pw_fused=False)
+    """With engine.PW_BWD_FUSED off the stand-in whose fused kernel takes a shape gives the call log - and the routes - of the one that
+    knows only the small fold, and, with the stride-2 depthwise fusion off as well, the golden log recorded before either kernel
+    existed (less its query lines: test_cpu_dwfused_s2._golden_calls)."""
+    off, cfg, tape, backbone, r_off = _record(monkeypatch, FusedRecordingOps(), pw_fused=False)
+    today, *_, r_today = _record(monkeypatch, RecordingOps(), pw_fused=False)
     assert off == today and not [c for c in off if c.startswith("pw_bwd_fused(") or c.startswith("pw_parts_reduce(")]
-    off2, *_ = _record(monkeypatch, FusedRecordingOps(), pw_fused=False, dw_s2=False)
-    assert off2 == open(GOLDEN).read().splitlines()
-    # and the stand-in that knows no "fused" is untouched by the switch
-    on, *_ = _record(monkeypatch, RecordingOps(), pw_fused=True, dw_s2=False)
-    assert on == off2
+    assert r_off == r_today and "fused" not in {r.expand for r in r_off}
+    # the stride-1 blocks the fused kernel took go back to the fold; the stride-2 ones, which never fold, to the plain apply
+    for (b, _) in _eligible(cfg, tape, backbone):
+        assert r_off[b.index].expand == ("fold" if b.stride == 1 else "apply"), b.index
+    off2, *_, r_off2 = _record(monkeypatch, FusedRecordingOps(), pw_fused=False, dw_s2=False)
+    assert off2 == _golden_calls()[0]
+    # and the stand-in that knows no fused kernel is untouched by the switch
+    on, *_, r_on = _record(monkeypatch, RecordingOps(), pw_fused=True, dw_s2=False)
+    assert on == off2 and r_on == r_off2
+

@@ -6,7 +6,7 @@ reduce through the lane; with engine.PW_PROJ_BWD_FUSED off the call log is the p
 import ctypes
 
 from muscle_amd import _lib
-from test_cpu_dwfused_s2 import RecordingOps, _b0_tape
+from test_cpu_dwfused_s2 import RecordingOps, _b0_tape, _routes
 
 ADMITTED = ((48, 288), (48, 192))
 
@@ -79,15 +79,21 @@ def _record(monkeypatch, rec, *, proj_fused: bool):
     monkeypatch.setattr(engine, "WGRAD_SIDE_STREAM", False)
     monkeypatch.setattr(engine, "PW_PROJ_BWD_FUSED", proj_fused)
     backbone, cfg, tape, taps = _b0_tape()
+    routes = _routes(tape, backbone)
+    materialised = [t.a is not None for t in tape.blocks]          # (the backward releases t.a)
     engine.backbone_backward(backbone, cfg, tape, taps, engine.GradSink())
-    return rec.calls, tape
+    return rec.calls, tape, routes, materialised
 
 
 def test_eligible_blocks_take_exactly_one_fused_call(monkeypatch):
-    calls, tape = _record(monkeypatch, ProjRecordingOps(), proj_fused=True)
-    blocks = [(t.cfg, tape.N * t.Ho * t.Wo, t.Ho * t.Wo) for t in tape.blocks if t.a is None and tape.N * t.Ho * t.Wo >= 512]
+    calls, tape, routes, materialised = _record(monkeypatch, ProjRecordingOps(), proj_fused=True)
+    blocks = [(t.cfg, tape.N * t.Ho * t.Wo, t.Ho * t.Wo) for t, mat in zip(tape.blocks, materialised)
+              if not mat and tape.N * t.Ho * t.Wo >= 512]
     others = [t for t in tape.blocks if t.cfg.index not in {b.index for b, _, _ in blocks}]
-    assert blocks and others
+    assert blocks and others and any(materialised)
+    # the route: "fused" for exactly those blocks; the expand and depthwise stages are the base stand-in's
+    assert [t.cfg.index for t, r in zip(tape.blocks, routes) if r.project == "fused"] == [b.index for b, _, _ in blocks]
+    assert {r.project for r in routes} == {"fused", "gemm"} and "fused" not in {r.expand for r in routes}
     fused = [c for c in calls if c.startswith("pw_proj_bwd_fused(")]
     assert len(fused) == len(blocks)
     for b, Mo, hw in blocks:
@@ -99,16 +105,18 @@ def test_eligible_blocks_take_exactly_one_fused_call(monkeypatch):
             assert not [c for c in calls if c.startswith(f"{gone}(T[{Mo}, {b.cout}], ") and f"T[{b.cout}, {b.cexp}]" in c], (gone, b.index)
         assert not [c for c in calls if c.startswith(f"se_bn1_pool(T[{Mo}, {b.cexp}], ")], b.index
     names = [c.split("(")[0] for c in calls]
-    # one partial-matrix sum per fused project conv (the stand-in's fused expand convs add none: it answers "small" for those)
+    # one partial-matrix sum per fused project conv (the stand-in's fused expand convs add none: it knows only the small fold for those)
     assert names.count("pw_parts_reduce") == len(blocks)
     assert names.count("se_bn1_pool") == len(others)
     assert "pw_proj_bwd_fused_takes" not in names
 
 
 def test_switch_off_restores_the_parents_log(monkeypatch):
-    off, _ = _record(monkeypatch, ProjRecordingOps(), proj_fused=False)
-    parent, _ = _record(monkeypatch, RecordingOps(), proj_fused=False)
+    off, _, r_off, _ = _record(monkeypatch, ProjRecordingOps(), proj_fused=False)
+    parent, _, r_parent, _ = _record(monkeypatch, RecordingOps(), proj_fused=False)
     assert off == parent and not [c for c in off if c.startswith("pw_proj_bwd_fused(")]
-    # a stand-in that does not know the kernel is untouched by the switch
-    on, _ = _record(monkeypatch, RecordingOps(), proj_fused=True)
-    assert on == parent
+    assert r_off == r_parent and {r.project for r in r_off} == {"gemm"}
+    # a stand-in whose kernel takes no shape is untouched by the switch
+    on, _, r_on, _ = _record(monkeypatch, RecordingOps(), proj_fused=True)
+    assert on == parent and r_on == r_parent
+

@@ -6,7 +6,10 @@ Only host queries are called (no device is needed).  Shapes: every pointwise con
 448^2 / batch 8 and B7 at 448^2 / batch 32 (muscle_amd/arch.py), plus every (rows, a, b) literal of tests/test_gpu_split.py
 and tests/test_gpu_wgrad.py; each in both orientations (a forward GEMM and its data gradient; a weight gradient and its
 mirror), for mx_set_gemm_mode 0 / 1 / 2 and the plain / BN+activation operand.  The (R, Co, Ci, groups) rows of the
-bit-for-bit test are also asked under mx_set_wgrad_kernel(0 | 2, groups).
+bit-for-bit test are also asked under mx_set_wgrad_kernel(0 | 2, groups).  A second section, "backward_routes", holds
+engine.block_route for every block of the two training steps bench.py times, in both arithmetics (its values in the committed
+snapshot were read off the call log of the commit before block_route existed, with a stand-in for muscle_amd.ops that forwarded the
+queries to the library).
 
     python tools/dump_planner.py > tests/planner_snapshot.json
 """
@@ -42,6 +45,10 @@ QUERIES = {
     "mx_pw_wgrad_small_bnbwd_ok": lambda r, a, b, x: (r, b, a),
 }
 WITH_X_MODE = ("mx_pw_wgrad_small_ws", "mx_pw_wgrad_tile_ws")          # the only queries that take x_mode
+# the "backward_routes" section: the training steps bench.py times (the headline and configs[1]), in exact-fp32 and split arithmetic
+ROUTE_RUNS = (("efficientnet-b7", 448, 32), ("efficientnet-b0", 448, 16))
+ROUTE_MODES = (0, 1)
+ROUTE_SWITCHES = ("FOLD_BN0_EARLY", "DW_S2_FUSED", "PW_BWD_FUSED", "PW_PROJ_BWD_FUSED")
 
 
 def model_shapes():
@@ -117,15 +124,46 @@ def snapshot(L):
     return {"columns": [f"{name}:x_mode={x}" for name, x in columns()], "rows": rows}
 
 
+def backward_routes(L, model, size, batch, gemm_mode):
+    """[project, depthwise, expand] of engine.block_route for every block of `model` (last_pooling off) in a training step at
+    size x size, with the four schedule switches on and the library answering the queries in arithmetic `gemm_mode`.  What
+    block_route is told about the tape is what engine.backbone_forward leaves there: the activated project input where
+    project_materialises says so, an image of the expand weight's transpose where the step's WeightPlan builds one (split arithmetic,
+    Cexp % 4 == 0, mx_pw_planes_bytes > 0)."""
+    from muscle_amd import engine
+    if L.mx_set_gemm_mode(gemm_mode) != 0:
+        raise RuntimeError(f"mx_set_gemm_mode({gemm_mode}) failed")
+    cfg = arch.net_cfg(model, False)
+    was = {name: getattr(engine, name) for name in ROUTE_SWITCHES}
+    try:
+        for name in ROUTE_SWITCHES:
+            setattr(engine, name, True)
+        out, h = [], cfg.stem_out_size(size)
+        for b in cfg.blocks:
+            ho = b.out_size(h)
+            image = b.expand and gemm_mode != 0 and b.cexp % 4 == 0 and L.mx_pw_planes_bytes(b.cin, b.cexp) > 0
+            out.append(list(engine.block_route(b, batch, h, h, ho, ho, materialised=engine.project_materialises(b, batch * ho * ho, True),
+                                               wt_planes=image)))
+            h = ho
+    finally:
+        for name, v in was.items():
+            setattr(engine, name, v)
+    return out
+
+
 def main():
     L = _lib.lib()
     was = L.mx_get_gemm_mode()
     try:
         snap = snapshot(L)
+        routes = [{"model": m, "size": s, "batch": n, "gemm_mode": g, "routes": backward_routes(L, m, s, n, g)}
+                  for m, s, n in ROUTE_RUNS for g in ROUTE_MODES]
     finally:
         L.mx_set_gemm_mode(was)
     print('{"columns": ' + json.dumps(snap["columns"]) + ',\n "rows": [')
     print(",\n".join(json.dumps(r, separators=(",", ":")) for r in snap["rows"]))
+    print('],\n "backward_routes": [')
+    print(",\n".join(json.dumps(r, separators=(",", ":")) for r in routes))
     print("]}")
 
 

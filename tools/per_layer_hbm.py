@@ -3,6 +3,7 @@ MUSCLE_WGRAD_STREAM=0, so durations are standalone).  usage: per_layer_hbm.py <k
 import csv, collections, os, re, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import muscle_amd
+from muscle_amd import engine
 
 model = muscle_amd.MuSCLe(21, "efficientnet-b7", layers=3, last_pooling=False)
 cfg = model.cfg
@@ -18,11 +19,10 @@ dur = lambda r: (int(r['End_Timestamp']) - int(r['Start_Timestamp'])) / 1e3
 fp = [r for r in ph if 'colreduce_kernel<FPool' in r['Kernel_Name']]
 sp = list(reversed([r for r in ph if r['Kernel_Name'].startswith('se_bn1_pool')]))
 dwf = [r for r in ph if 'dw_fwd_kernel' in r['Kernel_Name']]
-# backward: stride-1 blocks run ONE fused kernel (3 reads + 1 write: dA, d, e in, gX out = 2 d + 2 e); stride-2 blocks run
-# dw_bwd_weight (reads e and dd: e + d) and dw_bwd_data (reads dd, writes gX: d + e) behind a bn_bwd_apply pass of their own -
-# round 3 priced the stride-2 rows' dw_bwd_data alone with the fused kernel's 2 d + 2 e (rows above 8 TB/s): each kernel now
-# has its own byte model and its own column entry.  With engine.DW_S2_FUSED (the default) the stride-2 blocks run ONE
-# dw_bwd_fused_s2_kernel too, priced like the stride-1 kernel: 2 d + 2 e
+# backward: which depthwise kernels a block ran is engine.block_route's `depthwise` field (read under the same MUSCLE_* switches as
+# the traced run).  "fused" / "fused_s2": ONE kernel (3 reads + 1 write: dA, d, e in, gX out = 2 d + 2 e); "unfused": dw_bwd_weight
+# (reads e and dd: e + d) and dw_bwd_data (reads dd, writes gX: d + e) behind a bn_bwd_apply pass of their own - round 3 priced those
+# rows' dw_bwd_data alone with the fused kernel's 2 d + 2 e (rows above 8 TB/s): each kernel has its own byte model and column entry
 dwb = list(reversed([r for r in ph if 'dw_bwd_fused_kernel' in r['Kernel_Name']]))
 dwb2 = list(reversed([r for r in ph if 'dw_bwd_fused_s2_kernel' in r['Kernel_Name']]))
 dwbw = list(reversed([r for r in ph if 'dw_bwd_weight' in r['Kernel_Name']]))
@@ -41,13 +41,14 @@ for i, blk in enumerate(cfg.blocks):
             t = dur(lst[i]); cells.append("%7.1f %5.2f" % (t, by / t / 1e6)); tot[nm] += t; ideal[nm] += by / 5e6
         else:
             cells.append("      -     -")
-    if blk.stride == 1 and i1 < len(dwb):
+    route = engine.block_route(blk, N, h, h, ho, ho, materialised=engine.project_materialises(blk, N * ho * ho, True), wt_planes=False)
+    if route.depthwise == "fused" and i1 < len(dwb):
         t = dur(dwb[i1]); i1 += 1
         cells.append("%7.1f %5.2f" % (t, (2 * d + 2 * e) / t / 1e6)); tot["dw_bwd"] += t; ideal["dw_bwd"] += (2 * d + 2 * e) / 5e6
-    elif blk.stride == 2 and i3 < len(dwb2):
+    elif route.depthwise == "fused_s2" and i3 < len(dwb2):
         t = dur(dwb2[i3]); i3 += 1
         cells.append("fused_s2 %6.1f %5.2f" % (t, (2 * d + 2 * e) / t / 1e6)); tot["dw_bwd_s2"] += t; ideal["dw_bwd_s2"] += (2 * d + 2 * e) / 5e6
-    elif blk.stride == 2 and i2 < len(dwbw) and i2 < len(dwbd):
+    elif route.depthwise == "unfused" and i2 < len(dwbw) and i2 < len(dwbd):
         tw, td = dur(dwbw[i2]), dur(dwbd[i2]); i2 += 1
         cells.append("weight %6.1f %5.2f, data %6.1f %5.2f" % (tw, (e + d) / tw / 1e6, td, (d + e) / td / 1e6))
         tot["dw_bwd_s2"] += tw + td; ideal["dw_bwd_s2"] += 2 * (d + e) / 5e6
