@@ -931,6 +931,30 @@ int mx_seg_map(const int* root, const int* rank, const int* marks, const int* or
 int mx_label_pair_counts(const int* a, const unsigned char* b, long n_pix, int A, int B, int* table, int* bad, void* stream);
 int mx_mask_pair_counts(const unsigned char* masks, const unsigned char* b, long n_pix, int n, int B, int* table, int* bad, void* stream);
 
+/* ---- boundary evaluation (DESIGN.md "Boundary evaluation"; csrc/boundary_eval.hip): trimap mIoU (the band curve of the DenseCRF /
+ * DeepLab papers) and Boundary IoU (Cheng et al. 2021) from integer tables.  Integer counts and integer atomic adds only: the result
+ * does not depend on the execution order.  Both entries only enqueue on `stream`.
+ *
+ * mx_label_edge_dist: label uint8 [H,W] (any values; 255 is an ordinary value) -> dist uint8 [H,W],
+ *   dist[p] = min(dmax + 1, min over q with label[q] != label[p] of max(|dy|, |dx|)), the Chebyshev distance to the nearest pixel with
+ * another label; with edge = 1 q also runs over the positions outside the image (a border pixel has distance 1), with edge = 0 over the
+ * image only.  dist lies in 1..dmax+1, dmax+1 = "nothing within dmax".  For every value c and d <= dmax, (label == c) & (dist_edge1 <= d)
+ * is mask_c & ~erode(mask_c, 3x3 ones, d times, zero border): the band Boundary IoU takes.  Exact for every H, W >= 1.  The separable
+ * form inside one workgroup: a 16 x 64 tile with a halo of dmax labels in LDS, a row pass, a column pass; no scratch.
+ * Limits: 1 <= dmax <= 64, edge 0 or 1, H*W < 2^31, H <= 1 048 560 (65 535 tile rows).
+ *
+ * mx_boundary_counts: pred, gt uint8 [H,W]; dt = dist(gt, edge 0), db = dist(gt, edge 1), dp = dist(pred, edge 1), all for this dmax.
+ * Pixels with gt == 255 are skipped (as mx_seg_confusion); with g = gt, p = pred, a value >= K increments nothing.
+ * hist int64 [6][K][dmax+2] += (bin 0 stays unused):
+ *   0 T_tri [g][dt] (g < K)   1 P_tri [p][dt] (p < K)   2 TP_tri [g][dt] (p == g)
+ *   3 T_b   [g][db] (g < K)   4 P_b   [p][dp] (p < K)   5 TP_b   [g][max(db,dp)] (p == g)
+ * so a count "within d" is the sum of bins 1..d, and rows 2, 1, 0 summed over all bins are mx_seg_confusion's (TP, P, T).
+ * ratio int64 [3][K] += (T_b, P_b, TP_b) within this image's own radius d_img (1..dmax; the caller forms it from the image diagonal).
+ * Per-workgroup int32 histograms in LDS, flushed with 64-bit integer atomics.  Limits: 2 <= K <= 32, 1 <= dmax <= 64, H*W < 2^31. */
+int mx_label_edge_dist(const unsigned char* label, int H, int W, int dmax, int edge, unsigned char* dist, void* stream);
+int mx_boundary_counts(const unsigned char* pred, const unsigned char* gt, const unsigned char* dt, const unsigned char* db,
+                       const unsigned char* dp, int K, int H, int W, int dmax, int d_img, long long* hist, long long* ratio, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,10 @@ Batched sweeps (`size_buckets`, `RapidEval.add_batch`, `SegValidation.add_batch`
 the eval-mode forward is per-sample, so images of one size share a forward and one post-processing launch
 (mx_rapid_eval_lr / mx_seg_infer_batch); the tables are integer for integer the per-image ones.  batch=1 is the per-image path.
 
+`BoundaryEval` (new; DESIGN.md "Boundary evaluation") counts what trimap mIoU and Boundary IoU need for the same uint8 maps:
+three mx_label_edge_dist launches and one mx_boundary_counts launch per image; `SegValidation` / `validate_seg` feed it the
+predictions they already hold on the device (`boundary=`), `--type png --boundary 1` prints its two blocks.  Off by default.
+
 `CamDictEval` is do_python_eval(input_type='npy') over the `{class: float32[H,W]}` dicts that infer_mcl writes, for a whole
 list of thresholds at once (one mx_camdict_confusion launch per image); `python -m muscle_amd.evaluation` is the
 reference's src/evaluation.py command line (:105-133) on top of it and of `SegEval`.
@@ -230,6 +234,135 @@ class SegEval:
         return miou_loglist(self.counts.cpu().numpy())
 
 
+def boundary_radius(H: int, W: int, ratio: float, dmax: int) -> int:
+    """The per-image radius of Boundary IoU: round(ratio * diagonal), at least 1 (as the published code chooses it), at most dmax."""
+    import math
+    return min(int(dmax), max(1, int(round(float(ratio) * math.hypot(int(H), int(W))))))
+
+
+class BoundaryEval:
+    """Boundary evaluation of segmentation maps (DESIGN.md "Boundary evaluation"): trimap mIoU - mIoU inside the band of
+    Chebyshev radius d around the ground truth's label changes - and Boundary IoU (Cheng et al. 2021) for every d in 1..dmax
+    from one pass per image.  Per image three mx_label_edge_dist launches (gt without and with the image edge, pred with it)
+    and one mx_boundary_counts launch accumulate two integer tables on the device:
+      hist  int64 [6, num_cls, dmax+2]: rows (T_tri, P_tri, TP_tri, T_b, P_b, TP_b) binned by distance (bin 0 unused,
+            bin dmax+1 = farther than dmax); a count within d is the sum of bins 1..d;
+      ratio int64 [3, num_cls]: (T_b, P_b, TP_b) within each image's own radius `boundary_radius(H, W, ratio, dmax)`.
+    The metrics are float64 on the host, formed as `miou_loglist` forms mIoU: per class TP / (T + P - TP + 1e-10), the mean
+    over all num_cls classes, in per cent."""
+
+    ROWS = ("T_tri", "P_tri", "TP_tri", "T_b", "P_b", "TP_b")
+
+    def __init__(self, device, num_cls: int = 21, dmax: int = 16, ratio: float = 0.02):
+        if not 2 <= int(num_cls) <= 32:
+            raise ValueError(f"BoundaryEval: num_cls {num_cls} outside 2..32")
+        if not 1 <= int(dmax) <= 64:
+            raise ValueError(f"BoundaryEval: dmax {dmax} outside 1..64")
+        if not float(ratio) > 0:
+            raise ValueError(f"BoundaryEval: ratio must be positive (got {ratio})")
+        self.num_cls, self.dmax, self.ratio = int(num_cls), int(dmax), float(ratio)
+        self.hist = torch.zeros(6, self.num_cls, self.dmax + 2, dtype=torch.int64, device=device)
+        self.ratio_counts = torch.zeros(3, self.num_cls, dtype=torch.int64, device=device)
+        self._dist = None                                    # uint8 [3,H,W] of the last size: dt, db, dp
+
+    def reset(self) -> None:
+        self.hist.zero_()
+        self.ratio_counts.zero_()
+
+    def add(self, pred: torch.Tensor, gt: torch.Tensor) -> None:
+        """pred: uint8 [H,W] class indices; gt: uint8 [H,W] SegmentationClass png (255 = ignore)."""
+        if not self.hist.is_cuda:
+            raise MuscleHipError("BoundaryEval.add runs on the HIP kernels only: create it with a ROCm device")
+        if pred.dim() != 2 or pred.dtype != torch.uint8 or gt.dtype != torch.uint8 or tuple(gt.shape) != tuple(pred.shape):
+            raise ValueError(f"pred and gt must be uint8 [H,W] of one shape (got {pred.dtype} {tuple(pred.shape)}, "
+                             f"{gt.dtype} {tuple(gt.shape)})")
+        H, W = pred.shape
+        dev = self.hist.device
+        p, g = pred.to(dev).contiguous(), gt.to(dev).contiguous()
+        if self._dist is None or tuple(self._dist.shape[1:]) != (H, W):
+            self._dist = torch.empty(3, H, W, dtype=torch.uint8, device=dev)
+        d, st = self._dist, stream()
+        call("mx_label_edge_dist", ptr(g), H, W, self.dmax, 0, ptr(d[0]), st)
+        call("mx_label_edge_dist", ptr(g), H, W, self.dmax, 1, ptr(d[1]), st)
+        call("mx_label_edge_dist", ptr(p), H, W, self.dmax, 1, ptr(d[2]), st)
+        call("mx_boundary_counts", ptr(p), ptr(g), ptr(d[0]), ptr(d[1]), ptr(d[2]), self.num_cls, H, W, self.dmax,
+             boundary_radius(H, W, self.ratio, self.dmax), ptr(self.hist), ptr(self.ratio_counts), st)
+
+    def tables(self):
+        """(hist [6,num_cls,dmax+2], ratio [3,num_cls]) as numpy int64."""
+        return self.hist.cpu().numpy(), self.ratio_counts.cpu().numpy()
+
+    def _check_d(self, d) -> int:
+        if not 1 <= int(d) <= self.dmax:
+            raise ValueError(f"d must be in 1..{self.dmax} (got {d})")
+        return int(d)
+
+    @staticmethod
+    def _iou(T, P, TP):
+        return TP / (T + P - TP + 1e-10)
+
+    def _within(self, hist, d):
+        c = hist[:, :, 1:d + 1].sum(axis=2)
+        return c[0], c[1], c[2], c[3], c[4], c[5]
+
+    def trimap_miou(self, d: int) -> float:
+        """mIoU (per cent) over the pixels within Chebyshev distance d of a change of the ground-truth label."""
+        T, P, TP, _, _, _ = self._within(self.tables()[0], self._check_d(d))
+        return float(np.mean(self._iou(T, P, TP)) * 100)
+
+    def trimap_curve(self) -> List[float]:
+        """trimap_miou(d) for d = 1..dmax from one read of the table."""
+        hist = self.tables()[0]
+        out = []
+        for d in range(1, self.dmax + 1):
+            T, P, TP, _, _, _ = self._within(hist, d)
+            out.append(float(np.mean(self._iou(T, P, TP)) * 100))
+        return out
+
+    def boundary_miou(self, d: Optional[int] = None) -> float:
+        """Mean Boundary IoU (per cent) at radius d; None: at every image's own radius (the ratio table)."""
+        hist, ratio = self.tables()
+        if d is None:
+            T, P, TP = ratio[0], ratio[1], ratio[2]
+        else:
+            _, _, _, T, P, TP = self._within(hist, self._check_d(d))
+        return float(np.mean(self._iou(T, P, TP)) * 100)
+
+    def loglist(self) -> Dict[str, float]:
+        """Per-category Boundary IoU in per cent at the per-image radius + 'mIoU', the dict shape of `miou_loglist`."""
+        r = self.tables()[1]
+        return miou_loglist(np.stack([r[2], r[1], r[0]], axis=1))
+
+    def lines(self) -> List[str]:
+        """What the scripts print after the IoU table: the Boundary-IoU table, then the trimap curve, one line per d."""
+        log = self.loglist()
+        out, row = ['Boundary IoU (ratio %g of the diagonal, at most %d px):' % (self.ratio, self.dmax)], ''
+        for i in range(self.num_cls):
+            nm = categories[i] if i < len(categories) else str(i)
+            row += '%11s:%7.3f%%' % (nm, log[nm])
+            if i % 2 == 1 or i == self.num_cls - 1:
+                out.append(row)
+                row = ''
+            else:
+                row += '\t'
+        out.append('%11s:%7.3f%%' % ('mBIoU', log['mIoU']))
+        hist = self.tables()[0]
+        for d in range(1, self.dmax + 1):
+            T, P, TP, Tb, Pb, TPb = self._within(hist, d)
+            out.append('trimap d=%2d\tmIoU: %.3f%%\tBoundary mIoU: %.3f%%' % (d, np.mean(self._iou(T, P, TP)) * 100,
+                                                                             np.mean(self._iou(Tb, Pb, TPb)) * 100))
+        return out
+
+    def logdict(self) -> Dict[str, object]:
+        """What the scripts append to --logfile."""
+        hist = self.tables()[0]
+        bc = []
+        for d in range(1, self.dmax + 1):
+            _, _, _, Tb, Pb, TPb = self._within(hist, d)
+            bc.append(float(np.mean(self._iou(Tb, Pb, TPb)) * 100))
+        return {'boundary': self.loglist(), 'trimap_mIoU': self.trimap_curve(), 'boundary_mIoU': bc}
+
+
 class SegValidation:
     """The per-epoch validation of train_muscle.py:224-283 on the device: per image the single scale-1, un-flipped pass of
     the eval list (`img_list[:1]`), softmax, resize to the ground truth's size, optional class-score scaling (--cls_dir,
@@ -237,14 +370,18 @@ class SegValidation:
     counts of :270-276 in a `SegEval` table.  `miou()` is :278-280: mean over classes of TP / (T + P - TP + 1e-10), a
     fraction (the value ReduceLROnPlateau is stepped with), not a percentage."""
 
-    def __init__(self, device, num_cls: int = 21, cls_dir=None, crf: bool = False, crf_trunc: float = 4.0):
+    def __init__(self, device, num_cls: int = 21, cls_dir=None, crf: bool = False, crf_trunc: float = 4.0,
+                 boundary: Optional[BoundaryEval] = None):
         from .data import MSFStager
         self.dev, self.cls_dir, self.crf, self.crf_trunc = device, cls_dir, bool(crf), crf_trunc
         self.stager = MSFStager(device)
         self.table = SegEval(device, num_cls)
+        self.boundary = boundary                 # optional: fed every prediction the table is fed, where it lies on the device
 
     def reset(self) -> None:
         self.table.counts.zero_()
+        if self.boundary is not None:
+            self.boundary.reset()
 
     def add(self, model, pil_img, gt, name=None) -> torch.Tensor:
         """pil_img: the RGB image; gt: uint8 [H,W] SegmentationClass map (255 = ignore); name: the image's name, needed
@@ -259,7 +396,10 @@ class SegValidation:
         crf_img = np.asarray(pil_img, dtype=np.uint8) if self.crf else None
         pred, _ = infer_seg(model, self.stager(pil_img, (1,))[:1], H, W, cls_label=cls, crf_img=crf_img, crf_t=1,
                             crf_trunc=self.crf_trunc)
-        self.table.add(pred, torch.from_numpy(np.ascontiguousarray(gt, dtype=np.uint8)).to(self.dev))
+        gd = torch.from_numpy(np.ascontiguousarray(gt, dtype=np.uint8)).to(self.dev)
+        self.table.add(pred, gd)
+        if self.boundary is not None:
+            self.boundary.add(pred, gd)
         return pred
 
     def add_batch(self, model, pil_imgs, gts, names=None) -> torch.Tensor:
@@ -285,6 +425,9 @@ class SegValidation:
         if self.crf:
             for b in range(B):
                 self.table.add(pred[b], gd[b])
+        if self.boundary is not None:
+            for b in range(B):
+                self.boundary.add(pred[b], gd[b])
         return pred
 
     def miou(self) -> float:
@@ -292,14 +435,15 @@ class SegValidation:
 
 
 def validate_seg(model, names: Sequence[str], voc12_root: str, device, num_cls: int = 21, cls_dir=None, crf: bool = False,
-                 batch: int = 1) -> float:
+                 batch: int = 1, boundary: Optional[BoundaryEval] = None) -> float:
     """train_muscle.py:224-283 over the images `names` of a VOC tree; leaves the model in eval mode (as the script does
     until the next epoch's model.train()).  batch=1: one image per forward (`SegValidation.add`), in list order.  batch>1:
     images of one size share a forward (`size_buckets`, `SegValidation.add_batch`) and the next batch's files are decoded on
-    host threads meanwhile; the same table."""
+    host threads meanwhile; the same table.  boundary: an optional `BoundaryEval` that is fed the same predictions (it is not
+    reset here: the caller owns it and reads it afterwards)."""
     batch = _check_batch(batch)
     model.eval()
-    val = SegValidation(device, num_cls, cls_dir=cls_dir, crf=crf)
+    val = SegValidation(device, num_cls, cls_dir=cls_dir, crf=crf, boundary=boundary)
     if batch == 1:
         for name in names:
             img, gt = _decode(voc12_root, name)
@@ -415,7 +559,16 @@ def parse_args(argv: Optional[List[str]] = None):
     ap.add_argument("--curve", default=False, type=_flag,
                     help="True/true/1: mIoU at the 60 thresholds 0.00..0.59 from one pass over the files; False/false/0: off "
                          "(the reference's type=bool reads any non-empty string as True)")
+    ap.add_argument("--boundary", default=0, type=int, choices=(0, 1),
+                    help="--type png, 1: after the IoU table, the Boundary-IoU table and the trimap curve (BoundaryEval)")
+    ap.add_argument("--boundary_dmax", default=16, type=int, help="--boundary 1: the largest band radius in pixels (1..64)")
+    ap.add_argument("--boundary_ratio", default=0.02, type=float,
+                    help="--boundary 1: the per-image Boundary-IoU radius as a fraction of the image diagonal")
     args = ap.parse_args(argv)
+    if args.boundary and args.type != "png":
+        ap.error("--boundary 1 evaluates label maps: it needs --type png")
+    if args.boundary and not (1 <= args.boundary_dmax <= 64 and args.boundary_ratio > 0):
+        ap.error("--boundary_dmax must be in 1..64 and --boundary_ratio positive")
     if args.curve and args.type != "npy":
         ap.error("--curve sweeps the background threshold of --type npy")
     if args.type == "npy" and not args.curve and args.t is None:
@@ -435,12 +588,19 @@ def main(argv: Optional[List[str]] = None) -> int:
     gt_of = lambda n: np.array(PIL.Image.open(os.path.join(args.gt_dir, n + ".png")))  # noqa: E731
     if args.type == "png":
         ev = SegEval(dev, 21)
+        bev = BoundaryEval(dev, 21, args.boundary_dmax, args.boundary_ratio) if args.boundary else None
         for n in names:
             pred = np.array(PIL.Image.open(os.path.join(args.predict_dir, n + ".png")))
-            ev.add(torch.from_numpy(pred).to(dev), torch.from_numpy(gt_of(n)).to(dev))
+            p, g = torch.from_numpy(pred).to(dev), torch.from_numpy(gt_of(n)).to(dev)
+            ev.add(p, g)
+            if bev is not None:
+                bev.add(p, g)
         loglist = ev.loglist()
         print_loglist(loglist)
         writelog(args.logfile, loglist, args.comment)
+        if bev is not None:
+            print("\n".join(bev.lines()))
+            writelog(args.logfile, bev.logdict(), args.comment + " (boundary)")
         return 0
     thresholds = [i / 100.0 for i in range(60)] if args.curve else [args.t]
     cev = CamDictEval(dev, thresholds, 21)

@@ -9,6 +9,7 @@ Differences a caller can see:
     runs the same model on permutohedral lattices instead (muscle_amd/lattice.py): pydensecrf's own approximation on the GPU,
     pinned against a numpy restatement of the algorithm, not against pydensecrf itself; the default is window;
   * --gt_dir (new, optional): the SegmentationClass directory; prints do_python_eval's IoU table for the written maps;
+    with --boundary 1 (new, default 0) also the Boundary-IoU table and the trimap curve of evaluation.BoundaryEval;
   * --num_workers and --tblog are accepted and unused (the multi-scale list is built on the device, nothing is logged).
 """
 from __future__ import annotations
@@ -41,7 +42,11 @@ def parse_args(argv: Optional[List[str]] = None):
     ap.add_argument("--pretrained", default="b7", type=str)
     ap.add_argument("--gt_dir", default=None, type=str, help="SegmentationClass directory: print the IoU table")
     ap.add_argument("--scales", default=",".join(str(s) for s in DEFAULT_SCALES), type=str)
+    ap.add_argument("--boundary", default=0, type=int, choices=(0, 1),
+                    help="--gt_dir, 1: after the IoU table, the Boundary-IoU table and the trimap curve (evaluation.BoundaryEval)")
     args = ap.parse_args(argv)
+    if args.boundary and not args.gt_dir:
+        ap.error("--boundary 1 compares against the ground truth: it needs --gt_dir")
     if args.crf not in (0, 2):
         ap.error(f"--crf {args.crf}: pydensecrf's lattice-filter CRF (--crf 1 of the reference, CPU) is not built on the HIP "
                  "path; --crf 2 runs the same CRF model with exact windowed kernels on the GPU (label maps close to, not "
@@ -69,7 +74,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     import torch
     import muscle_amd
     from muscle_amd.data import MSFStager
-    from muscle_amd.evaluation import SegEval, categories
+    from muscle_amd.evaluation import BoundaryEval, SegEval, categories
     from muscle_amd.infer import infer_seg, save_seg_png
 
     dev = torch.device("cuda:0")
@@ -80,6 +85,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     scales = tuple(float(s) for s in args.scales.split(","))
     stager = MSFStager(dev)
     ev = SegEval(dev, args.num_classes) if args.gt_dir else None
+    bev = BoundaryEval(dev, args.num_classes) if args.boundary else None
     if args.out_seg is not None:
         os.makedirs(args.out_seg, exist_ok=True)
     for it, name in enumerate(read_names(args.infer_list)):
@@ -95,7 +101,10 @@ def main(argv: Optional[List[str]] = None) -> int:
             save_seg_png(os.path.join(args.out_seg, name + ".png"), pred)
         if ev is not None:
             gt = np.array(PIL.Image.open(os.path.join(args.gt_dir, name + ".png")))
-            ev.add(pred, torch.from_numpy(gt).to(dev))
+            gd = torch.from_numpy(gt).to(dev)
+            ev.add(pred, gd)
+            if bev is not None:
+                bev.add(pred, gd)
         print(name, it, flush=True)
     if ev is not None:                                    # do_python_eval(printlog=True), src/evaluation.py:72-83
         log = ev.loglist()
@@ -104,6 +113,8 @@ def main(argv: Optional[List[str]] = None) -> int:
             print('%11s:%7.3f%%' % (nm, log[nm]), end='\t' if i % 2 != 1 else '\n')
         print('\n======================================================')
         print('%11s:%7.3f%%' % ('mIoU', log['mIoU']), flush=True)
+    if bev is not None:
+        print("\n".join(bev.lines()), flush=True)
     return 0
 
 

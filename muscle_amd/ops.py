@@ -910,3 +910,14 @@ def gn_bwd(dY, X, stat, gamma):
     dgamma, dbeta = _f32(C, device=X.device), _f32(C, device=X.device)
     call("mx_gn_bwd", ptr(dY), ptr(X), ptr(stat), ptr(gamma), N, H * W, C, G, ptr(ws), nbytes, ptr(dY), ptr(dgamma), ptr(dbeta), stream())
     return dY, dgamma, dbeta
+
+
+def label_edge_dist(label, dmax, edge, out=None):
+    """label uint8 [H,W] -> uint8 [H,W]: the Chebyshev distance to the nearest pixel with another label, cut at dmax + 1; edge=1
+    counts the positions outside the image as another label (mx_label_edge_dist)."""
+    if label.dim() != 2 or label.dtype != torch.uint8:
+        raise ValueError(f"label_edge_dist: label must be uint8 [H,W] (got {label.dtype} {tuple(label.shape)})")
+    H, W = label.shape
+    dist = out if out is not None else torch.empty(H, W, dtype=torch.uint8, device=label.device)
+    call("mx_label_edge_dist", ptr(label), H, W, int(dmax), int(edge), ptr(dist), stream())
+    return dist

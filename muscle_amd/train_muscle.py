@@ -13,6 +13,8 @@ Differences a caller can see:
   * --crf 1 runs the dense CRF of the validation on the GPU with t=1 (the exact windowed CRF of muscle_amd/crf.py, not
     pydensecrf's lattice filter);
   * --val_batch N (new, default 1): images of one size share a forward of the validation; the same table;
+  * --val_boundary 1 (new, default 0): one more line per epoch after the mIoU, the Boundary mIoU and the trimap mIoU at
+    d = 1, 2, 4, 8 of the validation's predictions (evaluation.BoundaryEval); the mIoU and the schedule are untouched;
   * --tblog_dir is created and otherwise unused (the reference opens a tensorboardX writer and never writes to it).
 """
 from __future__ import annotations
@@ -61,6 +63,9 @@ def parse_args(argv: Optional[List[str]] = None):
     ap.add_argument("--val_batch", default=1, type=int,
                     help="images per forward of the validation (1..8): 1 = one image per forward; above 1 images of one size "
                          "share a forward and the files of the next batch are decoded on host threads.  Same table")
+    ap.add_argument("--val_boundary", default=0, type=int, choices=(0, 1),
+                    help="1: after each epoch's mIoU, one line with the Boundary mIoU and the trimap mIoU at d = 1, 2, 4, 8 "
+                         "of the same predictions (evaluation.BoundaryEval)")
     args = ap.parse_args(argv)
     if not 1 <= args.val_batch <= 8:
         ap.error(f"--val_batch {args.val_batch} outside 1..8")
@@ -72,7 +77,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     import torch
     import muscle_amd
     from muscle_amd import edge
-    from muscle_amd.evaluation import validate_seg
+    from muscle_amd.evaluation import BoundaryEval, validate_seg
     from muscle_amd.infer_seg import read_names
     from muscle_amd.segdata import SegLoader, VOC12SegDataset
 
@@ -118,9 +123,13 @@ def main(argv: Optional[List[str]] = None) -> int:
                       "Fin:%s" % (time.ctime(est_finish)), flush=True)
         torch.save(model.state_dict(), os.path.join(args.session_name, "_{}".format(str(ep)) + ".pth"))
         stamp = time.time()                                                                 # :224-283
+        bev = BoundaryEval(dev, args.num_classes) if args.val_boundary else None
         miou = validate_seg(model, val_names, args.voc12_root, dev, args.num_classes, cls_dir=args.cls_dir, crf=bool(args.crf),
-                            batch=args.val_batch)
+                            batch=args.val_batch, boundary=bev)
         print(f"\n Epoch:{ep} val miou:{miou}", f"Time elapse:{time.time() - stamp}s", flush=True)
+        if bev is not None:
+            print(f" Epoch:{ep} val boundary miou:{bev.boundary_miou():.3f}%",
+                  " ".join(f"trimap{d}:{bev.trimap_miou(d):.3f}%" for d in (1, 2, 4, 8)), flush=True)
         scheduler.step(miou)
         stage_start = time.time()
     return 0
