@@ -32,6 +32,33 @@ _PROBES = {}
 @pytest.mark.parametrize("name,n,size,training", [("efficientnet-b0", 3, 64, True), ("efficientnet-b0", 2, 72, False),
                                                    ("efficientnet-b3", 2, 96, True)])
 def test_backbone_forward_backward(name, n, size, training):
+    _run(name, n, size, training)
+
+
+@pytest.mark.parametrize("name,n,size", [("efficientnet-b0", 3, 64), ("efficientnet-b3", 2, 96)])
+def test_backbone_backward_unfused_stride2_depthwise(name, n, size, monkeypatch):
+    """engine.DW_S2_FUSED off (MUSCLE_DW_S2_FUSED=0): every stride-2 block's depthwise backward goes through bn_backward_from_coeffs,
+    dwconv_bwd_weight and dwconv_bwd_data instead of dwconv_bwd_fused_s2, and is held to the same oracle at the same tolerance."""
+    from muscle_amd import engine, ops
+    calls = {"dwconv_bwd_data": 0, "dwconv_bwd_weight": 0, "dwconv_bwd_fused_s2": 0}
+
+    def counted(fname):
+        inner = getattr(ops, fname)
+
+        def wrapper(*a, **k):
+            calls[fname] += 1
+            return inner(*a, **k)
+        return wrapper
+    for fname in calls:
+        monkeypatch.setattr(ops, fname, counted(fname))
+    monkeypatch.setattr(engine, "DW_S2_FUSED", False)
+    cfg = _run(name, n, size, True)
+    s2 = sum(1 for b in cfg.blocks if b.stride == 2)
+    assert s2 > 0
+    assert calls == {"dwconv_bwd_data": s2, "dwconv_bwd_weight": s2, "dwconv_bwd_fused_s2": 0}
+
+
+def _run(name, n, size, training):
     from muscle_amd import engine
     from test_gpu_model import run_case
     dev = torch.device("cuda:0")
@@ -61,3 +88,4 @@ def test_backbone_forward_backward(name, n, size, training):
     torch.cuda.synchronize()
     worst = gu.check_grads_fixture({"backbone." + k: sink.bufs.get(id(p)) for k, p in bb.named_parameters()}, F, 2e-3, cache)
     print("worst grad rel err", worst)
+    return cfg

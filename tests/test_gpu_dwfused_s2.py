@@ -2,10 +2,13 @@
 staged, weight + data gradients from the one staged tile with the taps chosen by pixel parity, swish'(bn0) and the BN0 backward sums
 in the epilogue; reference model.py:76-90 backward with Conv2dStaticSamePadding, utils.py:122-145) against float64 autograd of the
 same chain: even and odd images, both pad_lo of each kernel size, images smaller than a tile or than the kernel, channel counts that
-are not a multiple of the 32-channel chunk, several workgroups per chunk."""
+are not a multiple of the 32-channel chunk, several workgroups per chunk, and (MULTI) several tiles per workgroup: groups that run
+from one sample into the next, and groups that the tile sequence does not reach."""
 import pytest
 import torch
 import torch.nn.functional as F
+
+import dw_geom
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -64,8 +67,7 @@ def _inputs(N, H, W, C, K):
     return (dA, D, gate, add, st1, c1, X, st0, Wt), pad_lo, pads
 
 
-@pytest.mark.parametrize("N,H,W,C,K", CASES)
-def test_fused_s2_depthwise_backward_matches_float64(N, H, W, C, K):
+def _case(N, H, W, C, K):
     from muscle_amd import ops
     (dA, D, gate, add, st1, c1, X, st0, Wt), pad_lo, pads = _inputs(N, H, W, C, K)
     want_gx, want_dw, want_part = _reference(dA, D, gate, add, st1, c1, X, st0, Wt, pads)
@@ -85,6 +87,34 @@ def test_fused_s2_depthwise_backward_matches_float64(N, H, W, C, K):
     assert err_gx <= 2e-5 * float(want_gx.abs().max()) + 1e-6                              # every element
     assert err_dw <= 5e-5 * float(want_dw.abs().max()) + 1e-5
     assert err_part <= 5e-5 * float(want_part.abs().max()) + 1e-5
+    return part, pad_lo
+
+
+@pytest.mark.parametrize("N,H,W,C,K", CASES)
+def test_fused_s2_depthwise_backward_matches_float64(N, H, W, C, K):
+    _case(N, H, W, C, K)
+
+
+# 32 channel chunks leave 4096 / 32 = 128 groups (3x3) or 2048 / 32 = 64 (5x5) for 5 x 33 tiles of the unshifted tiling
+MULTI = [
+    (5, 88, 96, 1024, 3, 0, 33, 2, 83, 83),        # pad_lo 0: the launch's tiling is the counted one, 2 tiles per group
+    (5, 88, 96, 1024, 5, 1, 48, 5, 55, 48),        # pad_lo 1: origins at -1, so 4 x 12 tiles per sample where 3 x 11 were counted; 5 per group, 7 groups never reached
+]
+
+
+@pytest.mark.parametrize("N,H,W,C,K,pad_lo,ntile,tpb,groups,reached", MULTI)
+def test_fused_s2_multi_tile_groups(N, H, W, C, K, pad_lo, ntile, tpb, groups, reached):
+    from muscle_amd import ops
+    geo = dw_geom.fused_s2_geom(N, H, W, C, K, pad_lo)
+    assert (geo.ntile, geo.tpb, geo.groups) == (ntile, tpb, groups)
+    assert geo.groups == ops.lib().mx_dwconv_bwd_fused_s2_parts(N, H, W, C, K)
+    dw_geom.assert_multi_tile(geo)
+    assert dw_geom.cdiv(N * geo.ntile, geo.tpb) == reached
+    part, got_pad = _case(N, H, W, C, K)
+    assert got_pad == pad_lo
+    # a group past the end of the (sample, tile) sequence writes rows of zeros (the finalise adds every row)
+    assert int(part[reached:].count_nonzero()) == 0
+    assert all(int(part[r].count_nonzero()) > 0 for r in (0, reached - 1))
 
 
 def test_fused_s2_model_padding_on_odd_image():
