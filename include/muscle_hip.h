@@ -502,8 +502,8 @@ int mx_irn_walk_snap(const float* x, const float* edge, const float* W, const do
  * 0 and never beats a threshold >= 0); keys int32 [Kp] ascending in 0..K-2; Kp = 0 (rw, keys may be NULL): background
  * everywhere.  gt uint8 [H,W] (255 = ignore, K..254 count towards P only, as mx_seg_confusion); thresholds fp32 [nt] ascending
  * and >= 0, nt <= 64; 2 <= K <= 24; E <= 13; H <= 4h, W <= 4w.  vmax uint32 [E]: the bits of the maximum each rw[e] is divided
- * by - the max_scratch word of mx_irn_up_max / mx_irn_finish run on the full [K-1][h][w] stack (that kernel's rounding depends
- * on its launch geometry, so the word is taken from it, not recomputed), or a stored CompactSoft vmax; 0 gives NaN values:
+ * by - the max_scratch word of mx_irn_up_max / mx_irn_finish run on the full [K-1][h][w] stack (the largest irn_up4 value
+ * of csrc/irn_soft.h, taken from that kernel, not recomputed), or a stored CompactSoft vmax; 0 gives NaN values:
  * background at every threshold.  A tie value == threshold is background.  One launch, snapshot = blockIdx.y; per pixel at
  * most three LDS integer atomics whatever nt (the bin #{t < best value}, as mx_camdict_confusion); no floating-point atomics. */
 int mx_irn_sweep_confusion(const float* rw, int E, int Kp, const int* keys, int h, int w, const unsigned char* gt, int H, int W,

@@ -81,26 +81,16 @@ __global__ __launch_bounds__(256) void irn_col_scale_kernel(float* dense, int n4
 // infer_irn.py:78-94: rw_up = interpolate(rw, x4, bilinear, align_corners=False)[:, :H, :W]; rw_up /= max(rw_up);
 // label = argmax over [bg_thres, rw_up_1 .. rw_up_C] (first maximum wins).
 // irn_up4 and the value / rounding step of the label live in irn_soft.h, shared with mx_soft_expand (softlabel.hip).
-// The maximum keeps the plain expression: hipcc contracts it one way in the unrolled loop of irn_up_max_kernel and another
-// way in its remainder loop, and the value every label is divided by must keep its bits.
-__device__ __forceinline__ float irn_up4_max(const float* m, int h, int w, int Y, int X) {
-  float sy = ((float)Y + 0.5f) * 0.25f - 0.5f, sx = ((float)X + 0.5f) * 0.25f - 0.5f;
-  if (sy < 0.f) sy = 0.f;
-  if (sx < 0.f) sx = 0.f;
-  int y0 = (int)sy, x0 = (int)sx;
-  if (y0 > h - 1) y0 = h - 1;
-  if (x0 > w - 1) x0 = w - 1;
-  const int y1 = y0 + (y0 < h - 1 ? 1 : 0), x1 = x0 + (x0 < w - 1 ? 1 : 0);
-  const float wy = sy - y0, wx = sx - x0;
-  return (1.f - wy) * ((1.f - wx) * m[y0 * w + x0] + wx * m[y0 * w + x1]) + wy * ((1.f - wx) * m[y1 * w + x0] + wx * m[y1 * w + x1]);
-}
-
+// The maximum is formed from irn_up4 as well: it is then the largest of the very values the label kernel divides, so the quotient
+// is exactly 1 at the arg-max pixel and never above it, as in the reference, whatever the launch geometry.  (It used to be the
+// plain expression, which hipcc contracts one way in this kernel's unrolled loop and another way in its remainder loop, not
+// always as lerp_b rounds: the maximum could be one ulp below a value, the quotient 1 + 1 ulp, and such a pixel beat bg_thres = 1.)
 __global__ __launch_bounds__(256) void irn_up_max_kernel(const float* rw, int C, int h, int w, int H, int W, unsigned* mx_bits) {
   float m = 0.f;
   const long total = (long)C * H * W;
   for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const int X = (int)(i % W), Y = (int)((i / W) % H), c = (int)(i / ((long)W * H));
-    m = fmaxf(m, irn_up4_max(rw + (long)c * h * w, h, w, Y, X));
+    m = fmaxf(m, irn_up4(rw + (long)c * h * w, h, w, Y, X));
   }
   m = wave_max(m);
   if ((threadIdx.x & 63) == 0) atomicMax(mx_bits, __float_as_uint(m));      // values are >= 0: bit order == value order

@@ -59,6 +59,7 @@ def _path_table(radius: int, device):
 
 
 WALK_METHODS = ("dense", "stencil")
+_RW_KBLOCK = 128                                  # K block of the dense walk's final product (a multiple of 4)
 
 
 def propagate_to_edge(x: torch.Tensor, edge: torch.Tensor, radius: int = 5, beta: float = 10, exp_times: int = 8,
@@ -99,8 +100,20 @@ def propagate_to_edge(x: torch.Tensor, edge: torch.Tensor, radius: int = 5, beta
     C4 = (C + 3) // 4 * 4
     xp = torch.zeros(C4, n4, dtype=torch.float32, device=dev)
     xp[:C, :n] = xm
-    rw = torch.empty(C4, n4, dtype=torch.float32, device=dev)
-    ops.bgemm(1, xp.view(1, C4, n4), A.view(1, n4, n4), rw.view(1, C4, n4), C4, n4, n4)
+    # The class maps are dense rows, so this product adds n non-zero terms per output where a squaring adds a few hundred: left
+    # as one fp32 chain it is the least accurate step of the walk (tests/test_gpu_irn_dense.py: 1.7e-6 of the maximum after two
+    # squarings, 4.6e-7 of it from the squarings).  K is therefore cut into blocks of _RW_KBLOCK vertices, one batch member each,
+    # and the partial products are added: blocked summation, 0.1 % of the walk's work.
+    kb, kt = n4 // _RW_KBLOCK, n4 % _RW_KBLOCK                # full blocks and the tail (a multiple of 4, as n4 is)
+    part = torch.empty(kb + (1 if kt else 0), C4, n4, dtype=torch.float32, device=dev)
+    if kb:
+        call("mx_bgemm", 1, ptr(xp), ptr(A), ptr(part), C4, n4, _RW_KBLOCK, n4, n4, n4, _RW_KBLOCK, _RW_KBLOCK * n4, C4 * n4, kb, 0,
+             stream())
+    if kt:
+        k0 = kb * _RW_KBLOCK
+        call("mx_bgemm", 1, ptr(xp) + 4 * k0, ptr(A) + 4 * k0 * n4, ptr(part) + 4 * kb * C4 * n4, C4, n4, kt, n4, n4, n4, 0, 0, 0, 1, 0,
+             stream())
+    rw = part.sum(dim=0)
     return rw[:C, :n].reshape(C, 1, h, w)
 
 

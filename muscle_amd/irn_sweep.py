@@ -19,7 +19,7 @@ a pixel is described by its bin #{t_i < best value}: `mx_irn_sweep_confusion` co
 launch with at most three integer atomics per pixel (the bin argument of `evaluation --curve`).  A tie value == threshold is
 background, as in the label kernel; an all-zero walk result (values 0 / 0) is background at every threshold.  The maximum each
 snapshot is divided by comes from the label step's own kernel (`mx_irn_up_max`) run on the full 20-channel stack, as
-`finish_semseg` runs it: that kernel's rounding depends on its launch geometry, so the sweep takes the word from it.
+`finish_semseg` runs it: one kernel forms the word every consumer divides by, so the sweep takes the word from it.
 
 The sweep scores the STENCIL walk (`infer_irn --walk stencil`).  The dense walk (`--walk dense`, exp_times fp32 squarings of
 the matrix) is a different fp32 computation of the same quantity and can differ from it in a few pixels per image.

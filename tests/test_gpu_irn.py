@@ -1,6 +1,9 @@
 """GPU parity of the IRN random-walk propagation (src/indexing.py::propagate_to_edge) against the
 fixture produced by the reference's own functions and, at a larger size, against the oracle.  fp32; the walk is
-exp_times matrix squarings, so the stated tolerance is 2e-4 of the output maximum."""
+exp_times matrix squarings, so the stated tolerance is 2e-4 of the output maximum.
+
+The kernels of the dense path (csrc/irn.hip) are pinned alone, at few squarings and at their edges, in
+tests/test_gpu_irn_dense.py."""
 import os
 
 import numpy as np
