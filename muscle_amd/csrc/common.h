@@ -272,7 +272,7 @@ __device__ __forceinline__ float blend_rows(float r0, float r1, float wy) {
 // mx_upsample_to_nchw (MuSCLe.py:256-257), operation for operation as upsample_to_nchw_kernel has always executed it: the
 // align_corners coordinate from the ROUNDED product scale*d (w1 = rn(scale*d) - i0, no fma), then
 //   value = rn((1-wy) * lerp_a(a00, a01, wx)) + rn(wy * lerp_b(a10, a11, wx))
-// Shared by that kernel and by the kernels that recompute its pixels instead of reading them (mx_rapid_eval_lr).
+// Shared by that kernel (head.hip) and by the kernels that recompute its pixels instead of reading them (mx_rapid_eval_lr, eval.hip).
 __device__ __forceinline__ void bil_coord_rn(int d, int in, int out, int& i0, int& i1, float& w1) {
 #pragma clang fp contract(off)
   float scale = (out > 1) ? (float)(in - 1) / (float)(out - 1) : 0.f;
@@ -316,7 +316,7 @@ __device__ __forceinline__ void halfpixel_tap(int d, float rs, int n_src, int& i
 __device__ __forceinline__ float upsample_ac_value(float a00, float a01, float a10, float a11, float wy, float wx) {
   return blend_rows(lerp_a(a00, a01, wx), lerp_b(a10, a11, wx), wy);
 }
-// cam_maxnorm (train_mcl.py:21-28) of one value from its channel's extremes mn / mx of relu(x), as mx_maxnorm evaluates it:
+// cam_maxnorm (train_mcl.py:21-28) of one value from its channel's extremes mn / mx of relu(x), as mx_maxnorm evaluates it (phase2.hip, eval.hip):
 //   y = relu((relu(x) - mn - 1e-6) * (1 / (mx - mn + 1e-6)))
 __device__ __forceinline__ float maxnorm_inv(float mn, float mx) {
 #pragma clang fp contract(off)

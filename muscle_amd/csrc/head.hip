@@ -6,7 +6,7 @@
 // normalisation, the affinity column normalisation and their adjoints.  Low-resolution head tensors
 // are NHWC with the class dimension padded to a leading dimension that is a multiple of 4.
 #include "common.h"
-#include <hip/hip_fp16.h>
+#include "eval_counts.h"
 
 // one component of the bilinear value of the four taps a00 a01 a10 a11 (float4) at the weights wy, wx of bil_coord (common.h), into o
 #define BIL(f) o.f = (1.f - wy) * ((1.f - wx) * a00.f + wx * a01.f) + wy * ((1.f - wx) * a10.f + wx * a11.f)
@@ -300,8 +300,8 @@ __device__ __forceinline__ void seg_softmax_at(const float* src, int h, int w, i
 // tab: npass x 8 int64 {address of the pass's [h,w,lds] logits, h, w, Hs, Ws, flip, 0, 0}
 // BATCH (mx_seg_infer_batch): blockIdx.y is the image; column 6 of the table is the row's image, rows of other images are
 // skipped, so an image's passes are summed in table order exactly as the single-image launch sums them; the mean divides by
-// the image's own row count; cls / pred / prob are per image; with gt the (TP, P, T) counts of seg_confusion_kernel are
-// taken here, per workgroup in LDS with one flush of integer atomics.
+// the image's own row count; cls / pred / prob are per image; with gt the (TP, P, T) counts of seg_confusion_kernel (eval.hip)
+// are taken here with the same rule and flush (eval_counts.h).
 template <bool BATCH>
 __global__ __launch_bounds__(256) void seg_infer_kernel(const long* tab, int npass, int lds, int K, int H, int W,
                                                         const float* cls, unsigned char* pred, float* prob,
@@ -359,42 +359,14 @@ __global__ __launch_bounds__(256) void seg_infer_kernel(const long* tab, int npa
     pred[i] = (unsigned char)bk;
     if (BATCH && gt) {
       const int g = gt[i];
-      if (g < 255) {
-        atomicAdd(&sc[bk * 3 + 1], 1);
-        if (g < K) {
-          atomicAdd(&sc[g * 3 + 2], 1);
-          if (bk == g) atomicAdd(&sc[g * 3 + 0], 1);
-        }
-      }
+      __builtin_assume(bk < K);                      // a k of the loop above
+      if (g < 255) eval_count(sc, 0, bk, g, K);
     }
   }
   if (BATCH && gt) {
     __syncthreads();
-    for (int i = threadIdx.x; i < K * 3; i += 256)
-      if (sc[i]) atomicAdd((unsigned long long*)&counts[i], (unsigned long long)sc[i]);
+    eval_flush(sc, K * 3, counts);
   }
-}
-
-// src/evaluation.py:36-50 (input_type='png') for one image: over pixels with gt < 255, P[pred]++ (pred < K), T[gt]++ and
-// TP[gt] += (pred == gt) (gt < K).  counts int64 [K][3] = (TP, P, T), accumulated across images; per workgroup in LDS,
-// flushed with one integer atomic per non-zero entry.
-__global__ __launch_bounds__(256) void seg_confusion_kernel(const unsigned char* pred, const unsigned char* gt, int K, long HW,
-                                                            long long* counts) {
-  extern __shared__ int sc[];                   // [K][3]
-  for (int i = threadIdx.x; i < K * 3; i += 256) sc[i] = 0;
-  __syncthreads();
-  for (long p = blockIdx.x * 256L + threadIdx.x; p < HW; p += (long)gridDim.x * 256) {
-    const int g = gt[p], pr = pred[p];
-    if (g >= 255) continue;
-    if (pr < K) atomicAdd(&sc[pr * 3 + 1], 1);
-    if (g < K) {
-      atomicAdd(&sc[g * 3 + 2], 1);
-      if (pr == g) atomicAdd(&sc[g * 3 + 0], 1);
-    }
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < K * 3; i += 256)
-    if (sc[i]) atomicAdd((unsigned long long*)&counts[i], (unsigned long long)sc[i]);
 }
 
 // infer_mcl.py:153-158 per channel (one workgroup each): clamp at 0, min / max over the image, zero what is below
@@ -419,181 +391,6 @@ __global__ __launch_bounds__(256) void infer_norm_kernel(float* acc, long HW) {
     float v = fmaxf(a[i], 0.f);
     if (v < lo) v = 0.f;
     a[i] = (v - mn - 1e-6f) / den;
-  }
-}
-
-
-// ---------------------------------------------------------------------------
-// Per-epoch rapid evaluation (train_mcl.py:286-318 + src/evaluation.py:19-52): for every threshold t,
-//   predict = argmax_k [t, half(pred_1*label_1), ..., half(pred_{K-1}*label_{K-1})]   (first maximum wins, as np.argmax)
-// and, over pixels with gt < 255:  P[predict]++, T[gt]++, TP[gt] += (predict == gt).
-// pred: one image, [K,H,W] fp32 (already cam_maxnorm'ed); label: [K] (entry 0 unused); gt: uint8 [H,W].
-// counts: int64 [nt][K][3] = (TP, P, T), accumulated across images.  The values go through fp16 exactly as the script's
-// np.half files do.  Per workgroup the counts are kept in LDS (nt*K*3 ints) and flushed once.
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void eval_confusion_kernel(const float* pred, const float* label, const unsigned char* gt,
-                                                             const float* thr, int nt, int K, long HW, long long* counts) {
-  extern __shared__ int lc[];                   // [nt][K][3]
-  for (int i = threadIdx.x; i < nt * K * 3; i += 256) lc[i] = 0;
-  __syncthreads();
-  for (long p = blockIdx.x * 256L + threadIdx.x; p < HW; p += (long)gridDim.x * 256) {
-    const int g = gt[p];
-    if (g >= 255) continue;
-    float best = -1.f;                          // values are >= 0; strict > keeps the first maximum
-    int bk = 0;
-    for (int k = 1; k < K; ++k) {
-      float v = __half2float(__float2half_rn(pred[(long)k * HW + p] * label[k]));
-      if (v > best) { best = v; bk = k; }
-    }
-    for (int t = 0; t < nt; ++t) {
-      const int pr = (thr[t] >= best) ? 0 : bk;  // channel 0 holds the threshold and precedes every other channel
-      atomicAdd(&lc[(t * K + pr) * 3 + 1], 1);
-      if (g < K) {
-        atomicAdd(&lc[(t * K + g) * 3 + 2], 1);
-        if (pr == g) atomicAdd(&lc[(t * K + g) * 3 + 0], 1);
-      }
-    }
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < nt * K * 3; i += 256)
-    if (lc[i]) atomicAdd((unsigned long long*)&counts[i], (unsigned long long)lc[i]);
-}
-
-// ---------------------------------------------------------------------------
-// mx_rapid_eval_lr: the rapid evaluation of B images of one size straight from the model's low-resolution SGC maps
-// (cam='cam_lr', NHWC [B,h,w,lds]): train_mcl.py:297-303 + src/evaluation.py:19-52 without any [K,H,W] tensor.  Every
-// full-resolution value is recomputed from its <= 4 low-res neighbours with upsample_ac_value (common.h: the bits of
-// mx_upsample_to_nchw), normalised with maxnorm_apply (the bits of mx_maxnorm) and counted as eval_confusion_kernel counts.
-// Grid: (row bands, images); a workgroup owns `rows` consecutive rows of one image, one thread one pixel at a time with the
-// pixel's coordinates and weights computed once and the channels read 16 bytes at a time.
-// Phase (a), rapid_extremes_kernel: ext[b][k] = {~bits(min), bits(max)} of relu(upsample) over the H x W grid.  The values
-//   are non-negative floats, whose bit patterns order as the floats do, and min / max do not depend on order: wave reduce,
-//   LDS integer atomicMax, one global integer atomicMax per workgroup and entry (the min is kept as the complement, so both
-//   are maxima over a zero-filled scratch).  Exact, the same bits every run.
-// Phase (b), rapid_count_kernel: per pixel with gt < 255 the first maximum over k = 1..K-1 of half(maxnorm * label_k), then
-//   per threshold P[pr]++ and TP[g] += (pr == g) in LDS; T[g] does not depend on the threshold: one LDS counter per class,
-//   added to every threshold's column at the flush.
-// ---------------------------------------------------------------------------
-#define REV_MAXK 24
-#define REV_MAXT 64
-
-struct RevPixel { int o00, o01, o10, o11; float wy, wx; };
-
-__device__ __forceinline__ RevPixel rev_pixel(int y, int x, int h, int w, int lds, int H, int W) {
-  int y0, y1, x0, x1;
-  RevPixel p;
-  bil_coord_rn(y, h, H, y0, y1, p.wy);
-  bil_coord_rn(x, w, W, x0, x1, p.wx);
-  p.o00 = (y0 * w + x0) * lds; p.o01 = (y0 * w + x1) * lds;
-  p.o10 = (y1 * w + x0) * lds; p.o11 = (y1 * w + x1) * lds;
-  return p;
-}
-// channels 4q .. 4q+3 of the upsampled map at the pixel
-__device__ __forceinline__ float4 rev_quad(const float* src, const RevPixel& p, int q) {
-  const float4 a00 = ld4(src + p.o00 + q * 4), a01 = ld4(src + p.o01 + q * 4);
-  const float4 a10 = ld4(src + p.o10 + q * 4), a11 = ld4(src + p.o11 + q * 4);
-  return make_float4(upsample_ac_value(a00.x, a01.x, a10.x, a11.x, p.wy, p.wx), upsample_ac_value(a00.y, a01.y, a10.y, a11.y, p.wy, p.wx),
-                     upsample_ac_value(a00.z, a01.z, a10.z, a11.z, p.wy, p.wx), upsample_ac_value(a00.w, a01.w, a10.w, a11.w, p.wy, p.wx));
-}
-// bit pattern of relu(v) with the sign of a zero dropped (fmaxf(-0, 0) may be either zero; mx_maxnorm's result does not
-// depend on which: the extremes only enter x - mn - 1e-6 and mx - mn + 1e-6)
-__device__ __forceinline__ unsigned rev_bits(float v) { return __float_as_uint(fmaxf(v, 0.f)) & 0x7fffffffu; }
-
-__global__ __launch_bounds__(256) void rapid_extremes_kernel(const float* sgc, int h, int w, int lds, int K, int H, int W, int rows,
-                                                             unsigned* ext) {
-  __shared__ unsigned se[REV_MAXK * 2];
-  const int b = blockIdx.y, yb = blockIdx.x * rows;
-  const int npix = min(rows, H - yb) * W;
-  const float* src = sgc + (long)b * h * w * lds;
-  if (threadIdx.x < REV_MAXK * 2) se[threadIdx.x] = 0u;
-  __syncthreads();
-  unsigned lo[REV_MAXK], hi[REV_MAXK];                 // lo = ~bits of the running minimum: both are running maxima
-#pragma unroll
-  for (int k = 0; k < REV_MAXK; ++k) { lo[k] = 0u; hi[k] = 0u; }
-  for (int p = threadIdx.x; p < npix; p += 256) {
-    const RevPixel px = rev_pixel(yb + p / W, p % W, h, w, lds, H, W);
-#pragma unroll
-    for (int q = 0; q < REV_MAXK / 4; ++q) {
-      if (q * 4 < K) {                                 // quad q lies inside the row: K <= lds and lds % 4 == 0
-        const float4 v = rev_quad(src, px, q);
-        const unsigned u[4] = {rev_bits(v.x), rev_bits(v.y), rev_bits(v.z), rev_bits(v.w)};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { lo[q * 4 + j] = max(lo[q * 4 + j], ~u[j]); hi[q * 4 + j] = max(hi[q * 4 + j], u[j]); }
-      }
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < REV_MAXK; ++k) {                 // (a thread without a pixel still holds 0, the identity of both maxima)
-    if (k < K) {
-      unsigned a = lo[k], c = hi[k];
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) { a = max(a, (unsigned)__shfl_xor((int)a, o, 64)); c = max(c, (unsigned)__shfl_xor((int)c, o, 64)); }
-      if ((threadIdx.x & 63) == 0) { atomicMax(&se[k * 2], a); atomicMax(&se[k * 2 + 1], c); }
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < K * 2) atomicMax(&ext[(long)b * K * 2 + threadIdx.x], se[threadIdx.x]);
-}
-
-__global__ __launch_bounds__(256) void rapid_count_kernel(const float* sgc, const float* label, const unsigned char* gt, const float* thr,
-                                                          int nt, int h, int w, int lds, int K, int H, int W, int rows,
-                                                          const unsigned* ext, long long* counts) {
-  __shared__ int lc[REV_MAXT * REV_MAXK * 2];          // [nt][K][2] = (TP, P)
-  __shared__ int ht[REV_MAXK];                         // T per class
-  __shared__ float smn[REV_MAXK], sinv[REV_MAXK], slab[REV_MAXK], sth[REV_MAXT];
-  const int b = blockIdx.y, yb = blockIdx.x * rows;
-  const int npix = min(rows, H - yb) * W;
-  const float* src = sgc + (long)b * h * w * lds;
-  const unsigned char* g8 = gt + ((long)b * H + yb) * W;
-  for (int i = threadIdx.x; i < nt * K * 2; i += 256) lc[i] = 0;
-  if (threadIdx.x < REV_MAXK) {
-    const int k = threadIdx.x;
-    ht[k] = 0;
-    float mn = 0.f, mx = 0.f, lb = 0.f;
-    if (k < K) {
-      mn = __uint_as_float(~ext[((long)b * K + k) * 2]);
-      mx = __uint_as_float(ext[((long)b * K + k) * 2 + 1]);
-      lb = label[(long)b * K + k];
-    }
-    smn[k] = mn; sinv[k] = maxnorm_inv(mn, mx); slab[k] = lb;
-  }
-  if (threadIdx.x < nt) sth[threadIdx.x] = thr[threadIdx.x];
-  __syncthreads();
-  for (int p = threadIdx.x; p < npix; p += 256) {
-    const int g = g8[p];
-    if (g >= 255) continue;
-    const RevPixel px = rev_pixel(yb + p / W, p % W, h, w, lds, H, W);
-    float best = -1.f;                                 // values are >= 0; strict > keeps the first maximum
-    int bk = 0;
-#pragma unroll
-    for (int q = 0; q < REV_MAXK / 4; ++q) {
-      if (q * 4 < K) {
-        const float4 u = rev_quad(src, px, q);
-        const float v[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int k = q * 4 + j;
-          if (k >= 1 && k < K) {
-            const float m = maxnorm_apply(v[j], smn[k], sinv[k]);
-            const float hv = __half2float(__float2half_rn(m * slab[k]));
-            if (hv > best) { best = hv; bk = k; }
-          }
-        }
-      }
-    }
-    if (g < K) atomicAdd(&ht[g], 1);
-    for (int t = 0; t < nt; ++t) {
-      const int pr = (sth[t] >= best) ? 0 : bk;        // channel 0 holds the threshold and precedes every other channel
-      atomicAdd(&lc[(t * K + pr) * 2 + 1], 1);
-      if (pr == g) atomicAdd(&lc[(t * K + g) * 2], 1);
-    }
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < nt * K; i += 256) {
-    unsigned long long* d = (unsigned long long*)&counts[(long)i * 3];
-    if (lc[i * 2]) atomicAdd(d + 0, (unsigned long long)lc[i * 2]);
-    if (lc[i * 2 + 1]) atomicAdd(d + 1, (unsigned long long)lc[i * 2 + 1]);
-    if (ht[i % K]) atomicAdd(d + 2, (unsigned long long)ht[i % K]);
   }
 }
 
@@ -709,72 +506,6 @@ __global__ __launch_bounds__(256) void cam_infer_kernel(const long* tab, int npa
   }
 }
 
-// ---------------------------------------------------------------------------
-// src/evaluation.py:25-50 (input_type='npy') for one image and ALL thresholds of the curve at once.
-//   predict(t) = argmax_k [t, tensor_1 .. tensor_{K-1}]  (first maximum wins), tensor_{key+1} = the dict's float32 map,
-//   absent channels 0; over pixels with gt < 255: P[predict]++, T[gt]++, TP[gt] += (predict == gt).
-// For t >= 0 an absent channel never beats channel 0, so only the kept maps are compared: (best, bk) = their first
-// maximum, which does not depend on t; predict(t) = (t >= best) ? 0 : bk.  With ascending thresholds the pixel is
-// described by its bin b = #{t_i < best}: thresholds i < b see bk, thresholds i >= b see 0.  Per pixel at most three LDS
-// integer atomics, independent of nt:  hp[b][bk]++;  hq[b][g]++ if g == bk, hq[b][0]++ if g == 0 (a kept class is never 0,
-// so column 0 of hq is free for the "predict = 0 and gt = 0" side);  ht[g]++.  At the flush, per threshold i and class c:
-//   P[i][c>0] = sum_{b>i} hp[b][c]   P[i][0] = sum_{b<=i} sum_c hp[b][c]   TP[i][c>0] = sum_{b>i} hq[b][c]
-//   TP[i][0] = sum_{b<=i} hq[b][0]   T[i][c] = ht[c]
-// maps fp32 [nkeep,H,W]; keys int32 [nkeep] ascending in 0..K-2; thr fp32 [nt] ascending, >= 0; counts int64 [nt][K][3]
-// = (TP, P, T), accumulated with integer atomics: exact.
-// ---------------------------------------------------------------------------
-#define CDC_MAXT 64
-#define CDC_MAXK 24
-__global__ __launch_bounds__(256) void camdict_confusion_kernel(const float* maps, const int* keys, int nkeep,
-                                                                const unsigned char* gt, const float* thr, int nt, int K, long HW,
-                                                                long long* counts) {
-  __shared__ int hp[(CDC_MAXT + 1) * CDC_MAXK], hq[(CDC_MAXT + 1) * CDC_MAXK], ht[CDC_MAXK], hrow[CDC_MAXT + 1];
-  __shared__ float st[CDC_MAXT];
-  __shared__ int sk[CDC_MAXK];
-  for (int i = threadIdx.x; i < (nt + 1) * K; i += 256) { hp[i] = 0; hq[i] = 0; }
-  if (threadIdx.x < K) ht[threadIdx.x] = 0;
-  if (threadIdx.x < nt) st[threadIdx.x] = thr[threadIdx.x];
-  if (threadIdx.x < nkeep) sk[threadIdx.x] = keys[threadIdx.x] + 1;
-  __syncthreads();
-  for (long p = blockIdx.x * 256L + threadIdx.x; p < HW; p += (long)gridDim.x * 256) {
-    const int g = gt[p];
-    if (g >= 255) continue;
-    float best = maps[p];
-    int bk = sk[0];
-    for (int j = 1; j < nkeep; ++j) {
-      const float v = maps[(long)j * HW + p];
-      if (v > best) { best = v; bk = sk[j]; }    // strict: the first maximum wins, as np.argmax
-    }
-    int b = 0;
-    for (int t = 0; t < nt; ++t) b += (st[t] < best) ? 1 : 0;
-    if (bk < K) atomicAdd(&hp[b * K + bk], 1);
-    if (g < K) {
-      atomicAdd(&ht[g], 1);
-      if (g == bk || g == 0) atomicAdd(&hq[b * K + g], 1);
-    }
-  }
-  __syncthreads();
-  for (int b = threadIdx.x; b <= nt; b += 256) {           // pixels per bin, any winner
-    int s = 0;
-    for (int c = 1; c < K; ++c) s += hp[b * K + c];
-    hrow[b] = s;
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < nt * K; i += 256) {
-    const int t = i / K, c = i % K;
-    int P = 0, TP = 0;
-    if (c == 0) {
-      for (int b = 0; b <= t; ++b) { P += hrow[b]; TP += hq[b * K]; }
-    } else {
-      for (int b = t + 1; b <= nt; ++b) { P += hp[b * K + c]; TP += hq[b * K + c]; }
-    }
-    unsigned long long* d = (unsigned long long*)&counts[(long)i * 3];
-    if (TP) atomicAdd(d + 0, (unsigned long long)TP);
-    if (P) atomicAdd(d + 1, (unsigned long long)P);
-    if (ht[c]) atomicAdd(d + 2, (unsigned long long)ht[c]);
-  }
-}
-
 static int gs(long n) { long b = (n + 255) / 256; return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b)); }
 
 // channels per thread of cam_infer_kernel: see the resource note in DESIGN.md (no scratch at 4 x 2 accumulators)
@@ -880,20 +611,6 @@ int mx_infer_norm(float* acc, int channels, long HW, void* stream) {
   return MX_OK;
 }
 
-int mx_eval_confusion(const float* pred, const float* label, const unsigned char* gt, const float* thresholds, int nt, int K, int H,
-                      int W, long long* counts, void* stream) {
-  MX_CHECK_ARG(pred && label && gt && thresholds && counts && nt > 0 && nt <= 64 && K >= 2 && K <= 256 && H > 0 && W > 0,
-               "eval_confusion: bad args");
-  const long HW = (long)H * W;
-  int blocks = (int)((HW + 256 * 8 - 1) / (256 * 8));
-  if (blocks < 1) blocks = 1;
-  if (blocks > 1024) blocks = 1024;
-  hipLaunchKernelGGL(eval_confusion_kernel, dim3(blocks), dim3(256), sizeof(int) * nt * K * 3, (hipStream_t)stream, pred, label, gt,
-                     thresholds, nt, K, HW, counts);
-  MX_LAUNCH_CHECK();
-  return MX_OK;
-}
-
 int mx_seg_infer(const long* passes, int npass, int lds, int K, int H, int W, const float* cls_scale, unsigned char* pred,
                  float* prob, void* stream) {
   MX_CHECK_ARG(passes && pred && npass > 0 && K >= 1 && K <= SEG_MAXK && K <= lds && lds % 4 == 0 && H > 0 && W > 0,
@@ -917,47 +634,6 @@ int mx_seg_infer_batch(const long* rows, int nrow, int B, int lds, int K, int H,
   return MX_OK;
 }
 
-// rows of one image per workgroup of the rapid-evaluation kernels: about 512 workgroups (two per CU) for the batch
-static int rev_rows(int B, int H) {
-  int r = (int)(((long)B * H + 511) / 512);
-  return r < 1 ? 1 : r;
-}
-
-long mx_rapid_eval_lr_ws(int B, int K) { return (B > 0 && K > 0) ? (long)B * K * 2 * (long)sizeof(unsigned) : 0; }
-
-int mx_rapid_eval_lr(const float* sgc, const float* label_with_bg, const unsigned char* gt, const float* thresholds, int nt, int B,
-                     int h, int w, int lds, int K, int H, int W, long long* counts, void* ws, long ws_bytes, void* stream) {
-  MX_CHECK_ARG(sgc && label_with_bg && gt && thresholds && counts && ws, "rapid_eval_lr: NULL argument");
-  MX_CHECK_ARG(nt > 0 && nt <= REV_MAXT && K >= 2 && K <= REV_MAXK && K <= lds && lds % 4 == 0 && B > 0 && B <= 65535 && h > 0 &&
-                   w > 0 && H > 0 && W > 0 && (long)h * w * lds < 0x7fffffffL && (long)H * W < 0x7fffffffL,
-               "rapid_eval_lr: bad args nt=%d B=%d h=%d w=%d lds=%d K=%d H=%d W=%d", nt, B, h, w, lds, K, H, W);
-  MX_CHECK_ARG(ws_bytes >= mx_rapid_eval_lr_ws(B, K), "rapid_eval_lr: ws has %ld bytes, needs %ld", ws_bytes,
-               mx_rapid_eval_lr_ws(B, K));
-  hipStream_t st = (hipStream_t)stream;
-  const int rows = rev_rows(B, H);
-  const dim3 grid((H + rows - 1) / rows, B);
-  hipError_t e = hipMemsetAsync(ws, 0, (size_t)mx_rapid_eval_lr_ws(B, K), st);
-  if (e != hipSuccess) { mx_set_error("rapid_eval_lr: memset failed: %s", hipGetErrorString(e)); return (int)e; }
-  hipLaunchKernelGGL(rapid_extremes_kernel, grid, dim3(256), 0, st, sgc, h, w, lds, K, H, W, rows, (unsigned*)ws);
-  MX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(rapid_count_kernel, grid, dim3(256), 0, st, sgc, label_with_bg, gt, thresholds, nt, h, w, lds, K, H, W, rows,
-                     (const unsigned*)ws, counts);
-  MX_LAUNCH_CHECK();
-  return MX_OK;
-}
-
-int mx_seg_confusion(const unsigned char* pred, const unsigned char* gt, int K, int H, int W, long long* counts, void* stream) {
-  MX_CHECK_ARG(pred && gt && counts && K >= 1 && K <= 255 && H > 0 && W > 0, "seg_confusion: bad args K=%d H=%d W=%d", K, H, W);
-  const long HW = (long)H * W;
-  int blocks = (int)((HW + 256 * 8 - 1) / (256 * 8));
-  if (blocks < 1) blocks = 1;
-  if (blocks > 1024) blocks = 1024;
-  hipLaunchKernelGGL(seg_confusion_kernel, dim3(blocks), dim3(256), sizeof(int) * K * 3, (hipStream_t)stream, pred, gt, K, HW,
-                     counts);
-  MX_LAUNCH_CHECK();
-  return MX_OK;
-}
-
 int mx_cam_infer(const long* passes, int npass, int lds, int K, int H, int W, const int* keep, int nkeep, float* out_cam,
                  float* out_sgc, void* stream) {
   MX_CHECK_ARG(passes && keep && (out_cam || out_sgc), "cam_infer: NULL table, keep list or both outputs NULL");
@@ -968,21 +644,6 @@ int mx_cam_infer(const long* passes, int npass, int lds, int K, int H, int W, co
   else
     cam_infer_launch<1>(passes, npass, lds, H, W, keep, nkeep, out_cam ? 0 : 1, out_cam ? out_cam : out_sgc, nullptr,
                         (hipStream_t)stream);
-  MX_LAUNCH_CHECK();
-  return MX_OK;
-}
-
-int mx_camdict_confusion(const float* maps, const int* keys, int nkeep, const unsigned char* gt, const float* thresholds, int nt,
-                         int K, int H, int W, long long* counts, void* stream) {
-  MX_CHECK_ARG(maps && keys && gt && thresholds && counts, "camdict_confusion: NULL argument");
-  MX_CHECK_ARG(nt > 0 && nt <= CDC_MAXT && K >= 2 && K <= CDC_MAXK && nkeep > 0 && nkeep <= K - 1 && H > 0 && W > 0,
-               "camdict_confusion: bad args nt=%d K=%d nkeep=%d H=%d W=%d", nt, K, nkeep, H, W);
-  const long HW = (long)H * W;
-  int blocks = (int)((HW + 256 * 8 - 1) / (256 * 8));
-  if (blocks < 1) blocks = 1;
-  if (blocks > 1024) blocks = 1024;
-  hipLaunchKernelGGL(camdict_confusion_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, maps, keys, nkeep, gt, thresholds,
-                     nt, K, HW, counts);
   MX_LAUNCH_CHECK();
   return MX_OK;
 }

@@ -58,6 +58,24 @@ def _check_batch(batch: int) -> int:
     return int(batch)
 
 
+def check_thresholds(thresholds, num_cls: int, who: str):
+    """The threshold list of the kernels that count every threshold at once (mx_camdict_confusion, mx_irn_sweep_confusion) as a
+    tuple of floats, or ValueError with `who` as the message's prefix: 1..64 values, finite, >= 0, ascending; num_cls in 2..24
+    (EVAL_MAXT / EVAL_MAXK of csrc/eval_counts.h).  A NaN would sort nowhere and a negative threshold would let the zero of an
+    absent channel win, so neither is a threshold."""
+    import math
+    ts = tuple(float(t) for t in thresholds)
+    if not 1 <= len(ts) <= 64:
+        raise ValueError(f"{who} takes 1..64 thresholds (got {len(ts)})")
+    if any(not math.isfinite(t) or t < 0 for t in ts):
+        raise ValueError(f"{who}: a negative threshold would let the zero of an absent channel win; thresholds must be finite and >= 0")
+    if any(b < a for a, b in zip(ts, ts[1:])):
+        raise ValueError(f"{who}: thresholds must be ascending")
+    if not 2 <= int(num_cls) <= 24:
+        raise ValueError(f"{who}: num_cls {num_cls} outside 2..24")
+    return ts
+
+
 def size_buckets(names_and_sizes, batch: int) -> List[List[str]]:
     """names_and_sizes: (name, (W, H)) pairs, the size as `PIL.Image.open(path).size` gives it.  Groups the names by size and
     cuts every group into batches of at most `batch`; within a group the list order is kept, the groups come in the order
@@ -459,15 +477,7 @@ class CamDictEval:
     int64 (TP, P, T) table [len(thresholds), num_cls, 3] on the device, one mx_camdict_confusion launch per image."""
 
     def __init__(self, device, thresholds: Sequence[float], num_cls: int = 21):
-        self.thresholds = tuple(float(t) for t in thresholds)
-        if not self.thresholds or len(self.thresholds) > 64:
-            raise ValueError(f"CamDictEval takes 1..64 thresholds (got {len(self.thresholds)})")
-        if any(t < 0 for t in self.thresholds):
-            raise ValueError("CamDictEval: a negative threshold would let the zero of an absent channel win; not supported")
-        if any(b < a for a, b in zip(self.thresholds, self.thresholds[1:])):
-            raise ValueError("CamDictEval: thresholds must be ascending")
-        if not 2 <= num_cls <= 24:
-            raise ValueError(f"CamDictEval: num_cls {num_cls} outside 2..24")
+        self.thresholds = check_thresholds(thresholds, num_cls, "CamDictEval")
         self.num_cls = num_cls
         self.dev = torch.device(device)
         self.thr = torch.tensor(self.thresholds, dtype=torch.float32, device=device)

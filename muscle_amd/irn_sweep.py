@@ -49,6 +49,7 @@ RADIUS = 5                                                                      
 def check_grid(betas, exp_times, thresholds, num_cls: int = 21):
     """The grid as tuples, or ValueError (see the module docstring for the ranges).  Touches no device."""
     import math
+    from .evaluation import check_thresholds
     from .indexing import check_exp_times_list
     bs = tuple(float(b) for b in betas)
     if not bs:
@@ -58,16 +59,7 @@ def check_grid(betas, exp_times, thresholds, num_cls: int = 21):
     if len(set(bs)) != len(bs):
         raise ValueError(f"irn_sweep: duplicate beta in {list(bs)}")
     ets = check_exp_times_list(exp_times)
-    ts = tuple(float(t) for t in thresholds)
-    if not 1 <= len(ts) <= 64:
-        raise ValueError(f"irn_sweep: 1..64 thresholds (got {len(ts)})")
-    if any(not math.isfinite(t) or t < 0 for t in ts):
-        raise ValueError("irn_sweep: a negative threshold would let the zero of an absent channel win; thresholds must be finite and >= 0")
-    if any(b < a for a, b in zip(ts, ts[1:])):
-        raise ValueError("irn_sweep: thresholds must be ascending")
-    if not 2 <= int(num_cls) <= 24:
-        raise ValueError(f"irn_sweep: num_cls {num_cls} outside 2..24")
-    return bs, ets, ts
+    return bs, ets, check_thresholds(thresholds, num_cls, "irn_sweep")
 
 
 def best_of(mious: np.ndarray) -> Tuple[int, int, int]:
