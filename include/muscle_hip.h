@@ -742,6 +742,32 @@ int mx_ir_label(const unsigned char* rgb, const float* cams, const int* keys, in
 int mx_crf_label(const unsigned char* rgb, const int* labels, int L, int H, int W, int t, float gt_prob, float sxy_g, float w_g,
                  float sxy_b, float srgb, float w_b, float trunc, void* ws, unsigned char* pred, float* q_out, void* stream);
 
+/* ---- dense-CRF energy loss of decoder training (csrc/crf_loss.hip; the message pass is the stencil-GEMM of the sections above).
+ * OURS, not the reference's: the regularised loss of Tang et al. 2018 ("On Regularized Losses for Weakly-supervised CNN
+ * Segmentation") with the pairwise sums evaluated exactly over a window instead of on a lattice, normalised by the affinity mass. */
+
+/* seg fp32 [N,K,H,W] logits, img fp32 [N,3,H,W] normalised as color_norm leaves it, window int [N,4] = (y0, x0, y1, x1) half-open
+ * per item (NULL: the whole map), pooling factor f in {1, 2, 4, 8} with H % f == 0 and W % f == 0, h = H/f, w = W/f; u, v: cells of
+ * the [h,w] grid, p: pixels.
+ *   P_c(p) = softmax_c(seg[n,:,p]);   in(p) = 1 inside the window of item n, else 0
+ *   rgb(p) = clamp(rint((img * std + mean) * 255), 0, 255),  mean = (0.485, 0.456, 0.406), std = (0.229, 0.224, 0.225)
+ *   r_u = 1/f^2 sum_{p in u} in(p);   S_c(u) = 1/f^2 sum_{p in u} in(p) P_c(p);   I(u) = 1/f^2 sum_{p in u} rgb(p)  (all pixels; exact)
+ *   s = sxy / f;  R = ceil(trunc * s);  trunc <= 0, or R >= max(h, w) - 1: all pairs
+ *   k(u,v) = exp(-(dx^2 + dy^2) / (2 s^2) - |I(u) - I(v)|^2 / (2 srgb^2))   for |dx| <= R and |dy| <= R (v == u included), else 0
+ *   M_c(u) = sum_v k(u,v) S_c(v);   Z(u) = sum_v k(u,v) r_v
+ *   D = sum_n sum_u r_u Z(u);   E = D - sum_n sum_u sum_c S_c(u) M_c(u);   loss = E / D,  0 where D == 0 (every window empty)
+ *   gseg[n,c,p] = g (-2 / (D f^2)) in(p) P_c(p) (M_c(u(p)) - sum_c' P_c'(p) M_c'(u(p)))          (all zeros where D == 0)
+ * fp32 with the two sums of D and E accumulated in double, no atomics, fixed summation order.  2 <= K <= 24, 1 <= N <= 65535,
+ * H <= 65535, H*W <= 2^24.  ws: mx_crf_loss_ws(N, K, H, W, f) bytes, 16-byte aligned, contents need not survive between calls.
+ * Nothing synchronises with the host. */
+long mx_crf_loss_ws(int N, int K, int H, int W, int f);                 /* < 0: bad arguments */
+/* forward: M [N,h,w,32] (16-byte aligned) = [M_0 .. M_{K-1} | Z | 0 ..] per cell, sums [2] = (D, sum S . M) in double, loss [1] */
+int mx_crf_loss_fwd(const float* seg, const float* img, const int* window, int N, int K, int H, int W, int f, float sxy, float srgb,
+                    float trunc, void* ws, float* M, double* sums, float* loss, void* stream);
+/* backward: gseg [N,K,H,W] (every element written) from the forward's M and sums and the upstream scalar g [1], all on the device */
+int mx_crf_loss_bwd(const float* seg, const int* window, const float* M, const double* sums, const float* g, int N, int K, int H, int W,
+                    int f, float* gseg, void* stream);
+
 /* ---- the permutohedral-lattice backend of both CRFs (csrc/lattice.hip): the filter pydensecrf evaluates the models of
  * src/imutils.py:439-456 and src/imutils.py:477-491 on (Adams, Baek & Davis 2010).  A DIFFERENT model from the windowed sums above
  * (its messages differ from the exact ones by up to a quarter of their size on sparse lattices), selectable, never the default; its

@@ -201,6 +201,15 @@ def plan_label_item(pil_img, label, min_scale: float = 0.5, max_scale: float = 1
     return p
 
 
+def plan_window(plan, crop_size: int) -> Tuple[int, int, int, int]:
+    """(y0, x0, y1, x1), half-open: the rectangle of the [crop_size, crop_size] container of a `SegItemPlan` or `LabelItemPlan`
+    that holds image, not padding - `img_crop`'s extent at `place`, mirrored when the container is flipped.  It is where a
+    staged label map differs from 255, and what `crf_loss.DenseEnergyLoss` takes as an item's window."""
+    (_, _, ch, cw), (ct, cl) = plan.img_crop, plan.place
+    x0 = crop_size - cl - cw if plan.flip else cl
+    return int(ct), int(x0), int(ct + ch), int(x0 + cw)
+
+
 class SegStager:
     """Packs the sources, jobs and tables of a batch of `SegItemPlan`s into one pinned buffer (`_stage.StageBuffer`: two
     alternate, they grow to the largest batch seen), copies it once and runs the device half: mx_color_jitter (ColorJitter on
@@ -210,10 +219,12 @@ class SegStager:
     points there.  Dense and compact items may share a batch.
     Returns {"img" [n,3,S,S], "mask" [n,C,S,S]} (+ "label" [n,20]) on the device: the batch `muscle_step` takes.
     A batch of `LabelItemPlan`s (hard label maps) runs the same image half and ONE mx_label_stage instead of the mask
-    kernels: "mask" is then uint8 [n,S,S] with 255 outside the window.  The two kinds of plan cannot share a batch."""
+    kernels: "mask" is then uint8 [n,S,S] with 255 outside the window.  The two kinds of plan cannot share a batch.
+    windows=True adds "window" (int32 [n,4], `plan_window` per item) to the dict, in a small copy of its own; the staging
+    buffer, the launches and the other tensors are the same either way."""
 
-    def __init__(self, device, batch: int, crop_size: int = 448):
-        self.dev, self.n, self.crop = device, batch, crop_size
+    def __init__(self, device, batch: int, crop_size: int = 448, windows: bool = False):
+        self.dev, self.n, self.crop, self.windows = device, batch, crop_size, windows
         self.buf = StageBuffer(device)
 
     @property
@@ -327,6 +338,8 @@ class SegStager:
                 call("mx_soft_expand", base, base + o_sj, nc, st)
             call("mx_mask_stage", base, base + o_mj, base, mask.data_ptr(), n, C, S, int(span_cap), st)
         out = {"img": img, "mask": mask}
+        if self.windows:
+            out["window"] = torch.tensor([plan_window(p, S) for p in plans], dtype=torch.int32).to(self.dev, non_blocking=True)
         if labels is not None:
             out["label"] = labels.to(self.dev, non_blocking=True)
         return out
@@ -416,9 +429,9 @@ class SegLoader:
     Iterating yields `(names, batch)`, `batch` being the dict `muscle_step` takes."""
 
     def __init__(self, dataset: VOC12SegDataset, batch_size: int, device, num_workers: int = 0, shuffle: bool = True,
-                 drop_last: bool = True, generator=None, prefetch_factor: int = 4):
+                 drop_last: bool = True, generator=None, prefetch_factor: int = 4, windows: bool = False):
         from torch.utils.data import DataLoader
-        self.dataset, self.stager = dataset, SegStager(device, batch_size, dataset.crop)
+        self.dataset, self.stager = dataset, SegStager(device, batch_size, dataset.crop, windows=windows)
         self.loader = DataLoader(dataset, batch_size=batch_size, shuffle=shuffle, num_workers=num_workers, drop_last=drop_last,
                                  collate_fn=_keep, generator=generator, persistent_workers=bool(num_workers),
                                  prefetch_factor=prefetch_factor if num_workers else None)

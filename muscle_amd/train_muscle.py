@@ -15,6 +15,9 @@ Differences a caller can see:
   * --val_batch N (new, default 1): images of one size share a forward of the validation; the same table;
   * --val_boundary 1 (new, default 0): one more line per epoch after the mIoU, the Boundary mIoU and the trimap mIoU at
     d = 1, 2, 4, 8 of the validation's predictions (evaluation.BoundaryEval); the mIoU and the schedule are untouched;
+  * --energy_weight W (new, default 0: off) adds W times the dense-CRF energy loss of muscle_amd/crf_loss.py (ours, not the
+    reference's) to the loss, with --energy_sxy / --energy_srgb / --energy_scale / --energy_trunc; the progress line gains
+    loss_energy.  It reaches the pixels a label map ignores (255) inside the crop window;
   * --tblog_dir is created and otherwise unused (the reference opens a tensorboardX writer and never writes to it).
 """
 from __future__ import annotations
@@ -66,9 +69,19 @@ def parse_args(argv: Optional[List[str]] = None):
     ap.add_argument("--val_boundary", default=0, type=int, choices=(0, 1),
                     help="1: after each epoch's mIoU, one line with the Boundary mIoU and the trimap mIoU at d = 1, 2, 4, 8 "
                          "of the same predictions (evaluation.BoundaryEval)")
+    ap.add_argument("--energy_weight", default=0.0, type=float,
+                    help="weight of the dense-CRF energy loss (muscle_amd/crf_loss.py; ours, not the reference's); 0: off")
+    ap.add_argument("--energy_sxy", default=80.0, type=float, help="its spatial width in full-resolution pixels")
+    ap.add_argument("--energy_srgb", default=15.0, type=float, help="its colour width")
+    ap.add_argument("--energy_scale", default=4, type=int, choices=(1, 2, 4, 8), help="its pooling factor (crop_size % scale == 0)")
+    ap.add_argument("--energy_trunc", default=2.0, type=float, help="its window: ceil(trunc * sxy / scale) cells; <= 0: all pairs")
     args = ap.parse_args(argv)
     if not 1 <= args.val_batch <= 8:
         ap.error(f"--val_batch {args.val_batch} outside 1..8")
+    if args.energy_weight < 0:
+        ap.error(f"--energy_weight {args.energy_weight} is negative")
+    if args.energy_weight > 0 and args.crop_size % args.energy_scale:
+        ap.error(f"--crop_size {args.crop_size} is not a multiple of --energy_scale {args.energy_scale}")
     return args
 
 
@@ -97,7 +110,11 @@ def main(argv: Optional[List[str]] = None) -> int:
     if train_dataset.labels is None:
         raise FileNotFoundError("data/cls_labels.npy (the image-level labels, src/data.py:53-56) not found")
     loader = SegLoader(train_dataset, args.batch_size, dev, num_workers=args.num_workers, shuffle=True, drop_last=True,
-                       prefetch_factor=4)                                                   # :128-130
+                       prefetch_factor=4, windows=args.energy_weight > 0)                   # :128-130
+    energy = None
+    if args.energy_weight > 0:
+        from muscle_amd.crf_loss import DenseEnergyLoss
+        energy = DenseEnergyLoss(args.energy_sxy, args.energy_srgb, args.energy_scale, args.energy_trunc)
     val_names = read_names(args.val_list)
     max_step = len(train_dataset) // args.batch_size * args.max_epoches
     if args.weights:
@@ -112,13 +129,15 @@ def main(argv: Optional[List[str]] = None) -> int:
         model.train()
         print("lr: %.6f" % (optimizer.param_groups[0]["lr"]))
         for it, (_names, batch) in enumerate(loader):
-            out = muscle_amd.muscle_step(model, optimizer, batch, lamb=args.lamb, step=args.step, k=args.k, criterion2=criterion2)
+            out = muscle_amd.muscle_step(model, optimizer, batch, lamb=args.lamb, step=args.step, k=args.k, criterion2=criterion2,
+                                         energy=energy, energy_weight=args.energy_weight)
             if it % 25 == 0:                                                                # :210-218
                 elapsed = time.time() - start
                 est_finish = int(start + elapsed / (it / max_step + 1))
                 print("Iter:%5d/%5d" % (it + max_step // args.max_epoches * ep, max_step),
                       "loss_seg:%.4f" % (float(out["loss_seg"])),
                       "loss_beacon:%.4f" % (float(out["loss_beacon"])),
+                      *(("loss_energy:%.4f" % (float(out["loss_energy"])),) if "loss_energy" in out else ()),
                       "imps:%.1f" % ((it + 1) * args.batch_size / (time.time() - stage_start)),
                       "Fin:%s" % (time.ctime(est_finish)), flush=True)
         torch.save(model.state_dict(), os.path.join(args.session_name, "_{}".format(str(ep)) + ".pth"))

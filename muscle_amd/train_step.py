@@ -218,14 +218,17 @@ def mcl_step(model, optimizer, batch: Dict[str, torch.Tensor], ep: int, *, drop_
 
 
 def muscle_step(model, optimizer, batch: Dict[str, torch.Tensor], *, lamb: float = 0.05, step: int = 7, k: int = 128,
-                criterion2=None, drop_u=None, grad_hook=None, fused: bool = True):
+                criterion2=None, drop_u=None, grad_hook=None, fused: bool = True, energy=None, energy_weight: float = 0.0):
     """One iteration of train_muscle.py:171-203 on the HIP path: seg forward of MuSCLe(mode='dec'), cross entropy against the
     arg-max of the soft pseudo-label, lamb * BEACON FieldLoss, backward, clip_grad_norm_(9), optimizer step.
     batch: {"img" [N,3,S,S], "label" [N,20], "mask" [N,21,S,S]} on the GPU.  A uint8 "mask" [N,S,S] is a hard label map
     (mask_type="label" of muscle_amd.segdata, 255 = ignore): cross entropy with that ignore index, and the FieldLoss takes
     the mask rows of its sampled points from the map.
     fused: the FieldLoss samples the decoder's 1/8-resolution features at the chosen points (the [N,256,S,S] dense_ft of
-    MuSCLe.py:285 is never materialised); False goes through the public forward(cam='seg') tensors."""
+    MuSCLe.py:285 is never materialised); False goes through the public forward(cam='seg') tensors.
+    energy (ours, not the reference's): a `crf_loss.DenseEnergyLoss`; with a non-zero energy_weight the loss gains
+    energy_weight * energy(seg_map, img, batch.get("window")) and the returned dict "loss_energy", for either kind of mask.
+    None, or weight 0: the launches and the returned keys are those of the reference's step."""
     from . import edge
     img, label, mask = batch["img"], batch["label"].float(), batch["mask"]
     optimizer.zero_grad()
@@ -244,10 +247,17 @@ def muscle_step(model, optimizer, batch: Dict[str, torch.Tensor], *, lamb: float
         l2, _ = crit(seg_map, ft, mask, label_with_bg, step, dense_is_lowres_nhwc=fused)
         if torch.is_tensor(l2):
             loss = l1 + lamb * l2
+    l3 = None
+    if energy is not None and energy_weight != 0:
+        l3 = energy(seg_map, img, batch.get("window"))
+        loss = loss + energy_weight * l3
     optimizer.zero_grad()
     loss.backward()
     if grad_hook is not None:
         grad_hook(model, 1)
     total = edge.clip_grad_norm_(model, 9)
     optimizer.step()
-    return {"loss_seg": l1, "loss_beacon": l2, "grad_norm": total}
+    out = {"loss_seg": l1, "loss_beacon": l2, "grad_norm": total}
+    if l3 is not None:
+        out["loss_energy"] = l3
+    return out
