@@ -471,6 +471,32 @@ int mx_irn_finish(const float* rw, int C, int h, int w, int H, int W, float bg_t
  * label - channel 0 half(bg), channel keys[i] + 1 half(up4(rw_i, r0 + y, x) / vmax), every other channel +0.
  * H <= 4h, W <= 4w, r0 + rows <= H, channels <= 256.  The job table is trusted device data.  No atomics. */
 int mx_soft_expand(void* base, const int* jobs, int n, void* stream);
+
+/* ---- class-balanced self-training labels (csrc/selflabel.hip; muscle_amd/selflabel.py; CBST, Zou et al., ECCV 2018)
+ * The confidence code.  Per pixel of prob fp32 [K,H,W] (the mean map of mx_seg_infer, or the CRF's Q):
+ *   label (uint8): best = prob[0], label = 0; for c = 1..K-1: if (prob[c] > best) { best = prob[c]; label = c; } - the first
+ *     maximum, as np.argmax on finite data;   conf = best;
+ *   code (uint8): a logarithmic code of the uncertainty u = 1.0f - conf, ONE fp32 subtraction:
+ *     conf is NaN -> 255 (never selected);   u <= 0 (conf >= 1) -> 0;   otherwise clamp((bits(u) >> 20) - 823, 1, 193),
+ *     bits(u) >> 20 = the sign, the 8 exponent bits and the top 3 mantissa bits.  So u = 2^-24 (the smallest uncertainty a
+ *     conf < 1 can give) is code 1, u in [0.5, 1) is 185..192 and u >= 1 is 193; a lower code means more confident, with
+ *     12.5 % relative resolution in 1 - conf at every magnitude; codes 194..254 are unused.
+ * mx_conf_code: label and code uint8 [H,W], fully written; hist int64 [K][256]: hist[label][code]++ for every pixel; with
+ *   gt (uint8 [H,W], 255 = ignore; gt, val and hit come together or all NULL) also val[label][code]++ where gt != 255 and
+ *   hit[label][code]++ where gt == label (int64 [K][256] both).  The tables are ADDED to (accumulated across calls):
+ *   counted per workgroup in LDS, flushed with 64-bit integer atomics; no floating-point atomics, the same integers
+ *   every run.  1 <= K <= 24, H*W < 2^31.  prob is read once.
+ * mx_code_hist: the same three tables from a stored (label, code) pair of n pixels (the same counting function); a
+ *   label >= K is counted nowhere and never used as an index; a stored code in 194..254 is counted as 255.
+ * mx_conf_select: out[i] = (label[i] < K && code[i] <= tcode[label[i]]) ? label[i] : 255; tcode uint8 [K] on the device;
+ *   kept int64 [K][2] += (kept, total) per class.  1 <= n < 2^31.
+ * All three only enqueue on `stream` and return a negative code for bad arguments before any launch. */
+int mx_conf_code(const float* prob, int K, int H, int W, unsigned char* label, unsigned char* code, const unsigned char* gt,
+                 long long* hist, long long* val, long long* hit, void* stream);
+int mx_code_hist(const unsigned char* label, const unsigned char* code, const unsigned char* gt, long n, int K, long long* hist,
+                 long long* val, long long* hit, void* stream);
+int mx_conf_select(const unsigned char* label, const unsigned char* code, const unsigned char* tcode, long n, int K,
+                   unsigned char* out, long long* kept, void* stream);
 /* The same walk without the matrix (csrc/irn_walk.hip): x . T^steps as `steps` stencil applications, O(nd * n) memory.
  * mx_irn_walk_weights (indexing.py:77-93 + :116-118; same path table as mx_irn_affinity, n = h*w):
  *   W[nd][n] fp32, direction-major: W[d][p] = (1 - max of the edge along the straight path p -> p+d)^beta, 0 where p+d lies

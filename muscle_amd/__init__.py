@@ -35,6 +35,9 @@ _INS_EVAL = ("InsSegEval", "voc_instances", "pair_table", "mask_iou", "label_pai
 
 _IRN_SWEEP = ("IrnSweep",)
 
+# class-balanced self-training labels from infer_seg's confidences (script: muscle_amd.selflabel)
+_SELFLABEL = ("conf_code", "ConfStats", "thresholds", "quality_curve", "select", "code_of", "code_interval")
+
 
 def __getattr__(name):
     # instance-segmentation evaluation (script: muscle_amd.ins_eval).  Resolved on first use, so that `python -m muscle_amd.ins_eval`
@@ -45,4 +48,7 @@ def __getattr__(name):
     if name in _IRN_SWEEP:                       # the infer_irn grid sweep (script: muscle_amd.irn_sweep), resolved the same way
         from . import irn_sweep
         return getattr(irn_sweep, name)
+    if name in _SELFLABEL:
+        from . import selflabel
+        return getattr(selflabel, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -10,6 +10,10 @@ Differences a caller can see:
     pinned against a numpy restatement of the algorithm, not against pydensecrf itself; the default is window;
   * --gt_dir (new, optional): the SegmentationClass directory; prints do_python_eval's IoU table for the written maps;
     with --boundary 1 (new, default 0) also the Boundary-IoU table and the trimap curve of evaluation.BoundaryEval;
+  * --out_conf DIR (new, optional, with --out_seg): beside each label map the confidence code of its pixels, DIR/<name>.png
+    (mode L), and DIR/stats.npz, the per-class code histograms - the inputs of `python -m muscle_amd.selflabel select`, which
+    keeps the most confident portion of every class for a self-training round; with --gt_dir also the quality curve.  Refused
+    with --cls_dir unless --crf 2 (a class-scaled mean map is no distribution).  Without it nothing changes;
   * --num_workers and --tblog are accepted and unused (the multi-scale list is built on the device, nothing is logged).
 """
 from __future__ import annotations
@@ -44,7 +48,15 @@ def parse_args(argv: Optional[List[str]] = None):
     ap.add_argument("--scales", default=",".join(str(s) for s in DEFAULT_SCALES), type=str)
     ap.add_argument("--boundary", default=0, type=int, choices=(0, 1),
                     help="--gt_dir, 1: after the IoU table, the Boundary-IoU table and the trimap curve (evaluation.BoundaryEval)")
+    ap.add_argument("--out_conf", default=None, type=str,
+                    help="with --out_seg: also write the confidence-code map <name>.png of every image and stats.npz, the "
+                         "per-class histograms, here (muscle_amd.selflabel select turns them into self-training labels)")
     args = ap.parse_args(argv)
+    if args.out_conf is not None and args.out_seg is None:
+        ap.error("--out_conf writes the confidence of the --out_seg label maps: it needs --out_seg")
+    if args.out_conf is not None and args.cls_dir and args.crf != 2:
+        ap.error("--out_conf with --cls_dir needs --crf 2: a mean map whose channels are scaled by class scores is no "
+                 "distribution, so its maximum is no confidence; the CRF's Q is one")
     if args.boundary and not args.gt_dir:
         ap.error("--boundary 1 compares against the ground truth: it needs --gt_dir")
     if args.crf not in (0, 2):
@@ -88,6 +100,11 @@ def main(argv: Optional[List[str]] = None) -> int:
     bev = BoundaryEval(dev, args.num_classes) if args.boundary else None
     if args.out_seg is not None:
         os.makedirs(args.out_seg, exist_ok=True)
+    stats = None
+    if args.out_conf is not None:
+        from muscle_amd.selflabel import ConfStats, curve_lines, quality_curve
+        os.makedirs(args.out_conf, exist_ok=True)
+        stats = ConfStats(dev, args.num_classes)
     for it, name in enumerate(read_names(args.infer_list)):
         img = PIL.Image.open(os.path.join(args.voc12_root, "JPEGImages", name + ".jpg")).convert("RGB")
         W, H = img.size
@@ -95,13 +112,17 @@ def main(argv: Optional[List[str]] = None) -> int:
         if args.cls_dir:
             cls = np.load(os.path.join(args.cls_dir, name + ".npy"), allow_pickle=True).squeeze()
         crf_img = np.asarray(img, dtype=np.uint8) if args.crf == 2 else None                # infer_seg.py:128-129, t=4
-        pred, _ = infer_seg(model, stager(img, scales), H, W, cls_label=cls, crf_img=crf_img, crf_t=4, crf_trunc=args.crf_trunc,
-                            crf_pairwise=args.crf_pairwise)
+        pred, prob = infer_seg(model, stager(img, scales), H, W, cls_label=cls, crf_img=crf_img, crf_t=4, crf_trunc=args.crf_trunc,
+                               crf_pairwise=args.crf_pairwise, return_prob=stats is not None)
         if args.out_seg is not None:
             save_seg_png(os.path.join(args.out_seg, name + ".png"), pred)
         if ev is not None:
             gt = np.array(PIL.Image.open(os.path.join(args.gt_dir, name + ".png")))
             gd = torch.from_numpy(gt).to(dev)
+        if stats is not None:                             # the code of the map pred is the argmax of: the mean map, or the CRF's Q
+            _, code = stats.add(prob, gd if ev is not None else None)
+            save_seg_png(os.path.join(args.out_conf, name + ".png"), code)
+        if ev is not None:
             ev.add(pred, gd)
             if bev is not None:
                 bev.add(pred, gd)
@@ -115,6 +136,10 @@ def main(argv: Optional[List[str]] = None) -> int:
         print('%11s:%7.3f%%' % ('mIoU', log['mIoU']), flush=True)
     if bev is not None:
         print("\n".join(bev.lines()), flush=True)
+    if stats is not None:
+        stats.save(os.path.join(args.out_conf, "stats.npz"))
+        if args.gt_dir:                                   # what each portion of muscle_amd.selflabel select would keep, and how right it is
+            print("\n".join(curve_lines(quality_curve(*stats.tables(), [i / 10 for i in range(1, 11)]))), flush=True)
     return 0
 
 
