@@ -717,6 +717,43 @@ int mx_field_terms(const float* sim, const float* simm, int nslots, int k, float
 int mx_field_scatter(const float* feat, const float* gfeat, const int* pts, int npts, int mode, int h, int w, const float* gup,
                      float* gdense, float* gpt /* mode 1: npts*CH floats of scratch */, int nsamples, int CH, int H, int W, void* stream);
 
+/* ---- the device sampler of the BEACON boundary points (edge.FieldLoss(sampler="device")) -------------
+ * The sampling rule.
+ *   A slot is a pair (n, f), n in 0..N-1, f in 0..F-1, F = K-1; its index is s = n*F + f, the order of the reference's
+ *   `for b ... for c` loop (src/edge.py:274-282).  A boundary pixel p of a slot is a positive as mx_field_select decides
+ *   it: mag >= 0.8f*m && m > 1.  A positive gives at most one out entry, the target pixel oi(p) when it passes `keep`,
+ *   and at most one in entry, ii(p), likewise.  An entry is identified by its source pixel p: targets may repeat,
+ *   sources cannot.
+ *   Counts.  counts[s] = {n_out, n_in, n_pos} for every slot, the values mx_field_select writes for it; an unlabelled
+ *     slot (lab_fg[n,f] == 0) counts {0,0,0}.  One device function decides positives, oi, ii and keep for all kernels.
+ *   Active slots.  A slot is active iff the sum over all slots of n_pos >= 10 and n_out > k and n_in > k
+ *     (src/edge.py:378 and :297; the elif / else branches of :306-316 both skip the slot).
+ *   Keys (uint64 arithmetic, wrapping).
+ *     mix(z): z ^= z>>30; z *= 0xBF58476D1CE4E5B9; z ^= z>>27; z *= 0x94D049BB133111EB; z ^= z>>31.
+ *     stream = mix(seed + 0x9E3779B97F4A7C15 * (draw + 1)).
+ *     key(s, side, p) = (mix(stream ^ ((uint64)(2*s + side) << 32 | p)) >> 32 << 32) | p, side 0 = out, 1 = in.
+ *     The key is unique per p; ties in the upper half are broken by p.  This requires H*W < 2^32 and 2*N*F < 2^32;
+ *     the entry points refuse H*W >= 2^31 already (pixels are int32) before any launch.
+ *   Draw.  For an active slot and each side, the k entries with the smallest keys: a uniform k-subset, because the
+ *     keys are independent of the data.
+ *   Output.  Point rows {n, target pixel}, [N*F*k, 2] int32 per side; within a slot the rows come in ascending source
+ *     pixel.  The k rows of an inactive slot are {n, (s*k + j) mod H*W}: valid indices spread over distinct pixels,
+ *     whose similarities mx_field_terms_masked ignores and whose gradient is exactly zero.
+ *   Draw counter.  `draw` is a uint64 in device memory; mx_field_sample reads it and increments it exactly once per
+ *     call, on the device, so a replayed hipGraph draws fresh points.
+ * mx_field_count: counts [N*F][3] for all slots in one launch (mag/orient [N,F,H*W], mx [N,F] as mx_field_edges
+ *   leaves them, lab_fg [N,F]); writes no lists. */
+int mx_field_count(const float* mag, const unsigned char* orient, const unsigned* mx, const float* lab_fg, int step, int* counts,
+                   int N, int F, int H, int W, void* stream);
+/* mx_field_sample: active [N*F] (0/1), n_active [1], both point tables, and the counter.  state: two uint64,
+ * {draw counter, stream key of the latest draw (scratch the launch fills for its own workgroups)}; seed is read as uint64. */
+int mx_field_sample(const float* mag, const unsigned char* orient, const unsigned* mx, const int* counts, int step, int k, long seed,
+                    void* state, int* active, int* n_active, int* pts_out, int* pts_in, int N, int F, int H, int W, void* stream);
+/* mx_field_terms with active flags [nslots]: an inactive slot contributes exactly +0 to loss[0], gets slot_loss = 0 and
+ * exact zeros in its gsim rows (its sim / simm rows are not read) */
+int mx_field_terms_masked(const float* sim, const float* simm, const int* active, int nslots, int k, float inv_n, float* loss,
+                          float* gsim, float* slot_loss /* nslots floats of scratch */, void* stream);
+
 /* ---- dense CRF of segmentation inference (src/imutils.py:439-456, crf_inference) ---------------------------------- */
 
 /* Mean-field inference of the fully connected CRF that src/imutils.py:439-456 hands to pydensecrf (Gaussian + bilateral

@@ -332,6 +332,38 @@ __global__ __launch_bounds__(256) void field_edge_kernel(const float* prob, cons
 // stage 2: one workgroup per labelled (sample, class) slot: boundary pixels (mag >= 0.8 max, max > 1) in row-major
 // order -> out / in index lists by FieldLoss.in_out_div (edge.py:196-229, orient+1 in [1,8]) with margins removed.
 // slots rows: {n, f}; lists [S][HW] ints; counts [S][3] = {n_out, n_in, n_pos}
+// The one statement of "boundary pixel" and of its two targets: is pixel p of a plane a positive (mag >= 0.8 max, max > 1), and
+// if so its out / in targets oi / ii (FieldLoss.in_out_div in fp32, as the reference computes them) and whether each survives
+// the margin removal (ko / ki).  field_select_kernel, field_count_kernel and field_sample_kernel all decide through this.
+struct FieldEntry { bool pos, ko, ki; float oi, ii; };
+__device__ __forceinline__ FieldEntry field_entry(const float* mg, const unsigned char* og, long p, long HW, float m, int step, int W) {
+  FieldEntry e;
+  e.pos = false; e.oi = 0.f; e.ii = 0.f;
+  if (p < HW) {
+    e.pos = (mg[p] >= 0.8f * m) && (m > 1.f);
+    if (e.pos) {
+      int o = og[p] + 1;
+      float ind = (float)p;
+      // outs = ind + (-step)^(1+(o<4)) * ((o%4==0)*w) + (-1)^(1+o) * ((o==2)|(o==6))
+      float a = (o % 4 == 0) ? (float)W * ((o < 4) ? (float)(step * step) : (float)(-step)) : 0.f;
+      float b = (o == 2 || o == 6) ? (((1 + o) & 1) ? -1.f : 1.f) : 0.f;
+      e.oi = ind + a + b;
+      // ins = ind + (-step)^(o<4) * ((o%4==0)*w) + (-1)^o * ((o==2)|(o==6))
+      float a2 = (o % 4 == 0) ? (float)W * ((o < 4) ? (float)(-step) : 1.f) : 0.f;
+      float b2 = (o == 2 || o == 6) ? ((o & 1) ? -1.f : 1.f) : 0.f;
+      e.ii = ind + a2 + b2;
+    }
+  }
+  auto keep = [&](float v) {
+    float r = fmodf(v, (float)(W - 1));
+    if (r < 0.f) r += (float)(W - 1);
+    return r != 0.f && r != 1.f && v > 0.f && v < (float)(HW - 1);
+  };
+  e.ko = e.pos && keep(e.oi);
+  e.ki = e.pos && keep(e.ii);
+  return e;
+}
+
 __global__ __launch_bounds__(256) void field_select_kernel(const float* mag, const unsigned char* orient, const unsigned* mx,
                                                            const int* slots, int step, int* out_list, int* in_list, int* counts,
                                                            int F, int H, int W) {
@@ -347,30 +379,9 @@ __global__ __launch_bounds__(256) void field_select_kernel(const float* mag, con
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int npos = 0;
   for (long p0 = 0; p0 < HW; p0 += 256) {
-    long p = p0 + threadIdx.x;
-    bool pos = false;
-    float oi = 0.f, ii = 0.f;
-    if (p < HW) {
-      pos = (mg[p] >= 0.8f * m) && (m > 1.f);
-      if (pos) {
-        int o = og[p] + 1;
-        float ind = (float)p;
-        // outs = ind + (-step)^(1+(o<4)) * ((o%4==0)*w) + (-1)^(1+o) * ((o==2)|(o==6))
-        float a = (o % 4 == 0) ? (float)W * ((o < 4) ? (float)(step * step) : (float)(-step)) : 0.f;
-        float b = (o == 2 || o == 6) ? (((1 + o) & 1) ? -1.f : 1.f) : 0.f;
-        oi = ind + a + b;
-        // ins = ind + (-step)^(o<4) * ((o%4==0)*w) + (-1)^o * ((o==2)|(o==6))
-        float a2 = (o % 4 == 0) ? (float)W * ((o < 4) ? (float)(-step) : 1.f) : 0.f;
-        float b2 = (o == 2 || o == 6) ? ((o & 1) ? -1.f : 1.f) : 0.f;
-        ii = ind + a2 + b2;
-      }
-    }
-    auto keep = [&](float v) {
-      float r = fmodf(v, (float)(W - 1));
-      if (r < 0.f) r += (float)(W - 1);
-      return r != 0.f && r != 1.f && v > 0.f && v < (float)(HW - 1);
-    };
-    bool ko = pos && keep(oi), ki = pos && keep(ii);
+    const FieldEntry e = field_entry(mg, og, p0 + threadIdx.x, HW, m, step, W);
+    const bool pos = e.pos, ko = e.ko, ki = e.ki;
+    const float oi = e.oi, ii = e.ii;
     unsigned long long bo = __ballot(ko), bi = __ballot(ki);
     unsigned long long lower = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
     int po = __popcll(bo & lower), pi = __popcll(bi & lower);
@@ -392,6 +403,151 @@ __global__ __launch_bounds__(256) void field_select_kernel(const float* mag, con
   if (lane == 0) atomicAdd(&base[2], npos);
   __syncthreads();
   if (threadIdx.x == 0) { counts[3 * s] = base[0]; counts[3 * s + 1] = base[1]; counts[3 * s + 2] = base[2]; }
+}
+
+// ---------------------------------------------------------------------------
+// Device sampler of the boundary points (the rule is stated in include/muscle_hip.h).  Slot s = n*F + f over ALL
+// (sample, class) pairs; nothing is read back: counts -> active flags -> the k smallest 64-bit keys per active slot and side.
+// ---------------------------------------------------------------------------
+// counts [N*F][3] = {n_out, n_in, n_pos}, what field_select_kernel writes for the slot; an unlabelled slot counts {0,0,0}.
+// One workgroup per slot, integer sums only.
+__global__ __launch_bounds__(256) void field_count_kernel(const float* mag, const unsigned char* orient, const unsigned* mx,
+                                                          const float* lab_fg, int step, int* counts, int H, int W) {
+  __shared__ int tot[3];
+  const int s = blockIdx.x;
+  const long HW = (long)H * W;
+  if (lab_fg[s] == 0.f) {                               // (uniform)
+    if (threadIdx.x < 3) counts[3 * s + threadIdx.x] = 0;
+    return;
+  }
+  const float m = __uint_as_float(mx[s]);
+  const float* mg = mag + (long)s * HW;
+  const unsigned char* og = orient + (long)s * HW;
+  if (threadIdx.x < 3) tot[threadIdx.x] = 0;
+  __syncthreads();
+  int c0 = 0, c1 = 0, c2 = 0;
+  for (long p = threadIdx.x; p < HW; p += 256) {
+    const FieldEntry e = field_entry(mg, og, p, HW, m, step, W);
+    c0 += e.ko ? 1 : 0; c1 += e.ki ? 1 : 0; c2 += e.pos ? 1 : 0;
+  }
+  atomicAdd(&tot[0], c0); atomicAdd(&tot[1], c1); atomicAdd(&tot[2], c2);
+  __syncthreads();
+  if (threadIdx.x < 3) counts[3 * s + threadIdx.x] = tot[threadIdx.x];
+}
+
+__device__ __forceinline__ unsigned long long field_mix(unsigned long long z) {
+  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull; z ^= z >> 27; z *= 0x94D049BB133111EBull; z ^= z >> 31;
+  return z;
+}
+
+// One workgroup: active[s] = (sum of n_pos >= 10) && n_out > k && n_in > k; n_active; the draw counter state[0] is read and
+// advanced here, once, and the stream key of this draw left in state[1] for field_sample_kernel (which therefore never reads a
+// counter another workgroup may already have advanced).
+__global__ __launch_bounds__(256) void field_active_kernel(const int* counts, int S, int k, unsigned long long seed,
+                                                           unsigned long long* state, int* active, int* n_active) {
+  __shared__ long long tot;
+  __shared__ int nact;
+  if (threadIdx.x == 0) { tot = 0; nact = 0; }
+  __syncthreads();
+  long long t = 0;
+  for (int s = threadIdx.x; s < S; s += 256) t += counts[3 * s + 2];
+  atomicAdd((unsigned long long*)&tot, (unsigned long long)t);
+  __syncthreads();
+  const bool enough = tot >= 10;
+  int a = 0;
+  for (int s = threadIdx.x; s < S; s += 256) {
+    const int on = (enough && counts[3 * s] > k && counts[3 * s + 1] > k) ? 1 : 0;
+    active[s] = on;
+    a += on;
+  }
+  atomicAdd(&nact, a);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    n_active[0] = nact;
+    const unsigned long long draw = state[0];
+    state[1] = field_mix(seed + 0x9E3779B97F4A7C15ull * (draw + 1ull));
+    state[0] = draw + 1ull;
+  }
+}
+
+// grid (N*F, 2): one workgroup per slot and side (0 = out, 1 = in).  An entry is identified by its source pixel p; its key is
+// (upper 32 bits of mix(stream ^ ((2s+side) << 32 | p))) << 32 | p.  The k smallest keys: an MSB-first radix select over the
+// upper halves (four 8-bit digits, LDS histograms, integer atomics whose sum does not depend on arrival), ties on the upper half
+// resolved towards the smaller p; then one ordered sweep writes the chosen rows {n, target} in ascending p.  The plane is re-read
+// per pass (five sweeps of mag) instead of staging up to H*W entries.  An inactive slot writes k filler rows {n, row index mod
+// H*W} - valid and spread over distinct pixels, their gsim is zero - and leaves.
+__global__ __launch_bounds__(256) void field_sample_kernel(const float* mag, const unsigned char* orient, const unsigned* mx,
+                                                           const int* active, const unsigned long long* state, int step, int k,
+                                                           int* pts_out, int* pts_in, int F, int H, int W) {
+  __shared__ int hist[256];
+  __shared__ int sel[2];          // {digit, still needed}
+  __shared__ int wsum[2][4];
+  __shared__ int base[2];
+  const int s = blockIdx.x, side = blockIdx.y, n = s / F, t = threadIdx.x;
+  const long HW = (long)H * W;
+  int* rows = (side ? pts_in : pts_out) + (long)s * k * 2;
+  if (!active[s]) {                                     // (uniform)
+    for (int j = t; j < k; j += 256) { rows[2 * j] = n; rows[2 * j + 1] = (int)(((long)s * k + j) % HW); }
+    return;
+  }
+  const unsigned long long stream = state[1];
+  const unsigned long long tag = (unsigned long long)(2u * (unsigned)s + (unsigned)side) << 32;
+  const float m = __uint_as_float(mx[s]);
+  const float* mg = mag + (long)s * HW;
+  const unsigned char* og = orient + (long)s * HW;
+  auto hi_of = [&](long p) { return (unsigned)(field_mix(stream ^ (tag | (unsigned long long)p)) >> 32); };
+  unsigned prefix = 0u, pmask = 0u;
+  int need = k;
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    hist[t] = 0;
+    __syncthreads();
+    for (long p = t; p < HW; p += 256) {
+      const FieldEntry e = field_entry(mg, og, p, HW, m, step, W);
+      if (side ? e.ki : e.ko) {
+        const unsigned hi = hi_of(p);
+        if ((hi & pmask) == prefix) atomicAdd(&hist[(hi >> shift) & 255u], 1);
+      }
+    }
+    __syncthreads();
+    if (t == 0) {
+      int acc = 0, d = 0;
+      for (; d < 255; ++d) { if (acc + hist[d] >= need) break; acc += hist[d]; }
+      sel[0] = d; sel[1] = need - acc;
+    }
+    __syncthreads();
+    prefix |= (unsigned)sel[0] << shift; pmask |= 255u << shift;
+    need = sel[1];
+    __syncthreads();
+  }
+  // prefix = the upper half of the k-th smallest key; `need` of the entries that share it are taken, smallest p first
+  if (t < 2) base[t] = 0;
+  __syncthreads();
+  const int lane = t & 63, wave = t >> 6;
+  for (long p0 = 0; p0 < HW; p0 += 256) {
+    const long p = p0 + t;
+    const FieldEntry e = field_entry(mg, og, p, HW, m, step, W);
+    const bool on = side ? e.ki : e.ko;
+    const unsigned hi = on ? hi_of(p) : 0u;
+    const bool lt = on && hi < prefix, eq = on && hi == prefix;
+    const unsigned long long bl = __ballot(lt), be = __ballot(eq);
+    const unsigned long long lower = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    if (lane == 0) { wsum[0][wave] = __popcll(bl); wsum[1][wave] = __popcll(be); }
+    __syncthreads();
+    int lt_before = base[0] + __popcll(bl & lower), eq_before = base[1] + __popcll(be & lower);
+    for (int w2 = 0; w2 < wave; ++w2) { lt_before += wsum[0][w2]; eq_before += wsum[1][w2]; }
+    // the ties taken are the first `need` in p order: min(eq_before, need) of them precede this entry
+    const int pos = lt_before + (eq_before < need ? eq_before : need);
+    if ((lt || (eq && eq_before < need)) && pos < k) {
+      rows[2 * pos] = n;
+      rows[2 * pos + 1] = (int)(side ? e.ii : e.oi);
+    }
+    __syncthreads();
+    if (t == 0) {
+      base[0] += wsum[0][0] + wsum[0][1] + wsum[0][2] + wsum[0][3];
+      base[1] += wsum[1][0] + wsum[1][1] + wsum[1][2] + wsum[1][3];
+    }
+    __syncthreads();
+  }
 }
 
 // stage 3: softmax features at the sampled points.  pts rows {n, pixel}; one wave per point.
@@ -440,13 +596,19 @@ __global__ void field_loss_sum_kernel(const float* slot_loss, int nslots, float*
   for (int i = 0; i < nslots; ++i) t += slot_loss[i];
   loss[0] += t;
 }
+// active (may be NULL: every slot): an inactive slot gets slot_loss = 0 and exact zeros in its gsim rows, and reads nothing.
 __global__ __launch_bounds__(256) void field_terms_kernel(const float* sim, const float* simm, int k, float inv_n, float* slot_loss,
-                                                          float* gsim) {
+                                                          float* gsim, const int* active) {
   __shared__ float rm[256], cm[256], rmm[256], cmm[256];
   __shared__ float tot[2];
   __shared__ int cnt[2][4];
   __shared__ float ssum[2][4];
   const int s = blockIdx.x, t = threadIdx.x;
+  if (active && !active[s]) {                    // (uniform)
+    if (t == 0) slot_loss[s] = 0.f;
+    for (int i = t; i < k * k; i += 256) gsim[(long)s * k * k + i] = 0.f;
+    return;
+  }
   const float* S = sim + (long)s * k * k;
   const float* M = simm + (long)s * k * k;
   if (t < k) {
@@ -674,8 +836,46 @@ int mx_field_mask_label(const unsigned char* label, const int* pts, int npts, fl
 int mx_field_terms(const float* sim, const float* simm, int nslots, int k, float inv_n, float* loss, float* gsim, float* slot_loss,
                    void* stream) {
   MX_CHECK_ARG(sim && simm && loss && gsim && slot_loss && nslots > 0 && k > 0 && k <= 256, "field_terms: bad args (k <= 256)");
-  hipLaunchKernelGGL(field_terms_kernel, dim3(nslots), dim3(256), 0, (hipStream_t)stream, sim, simm, k, inv_n, slot_loss, gsim);
+  hipLaunchKernelGGL(field_terms_kernel, dim3(nslots), dim3(256), 0, (hipStream_t)stream, sim, simm, k, inv_n, slot_loss, gsim,
+                     (const int*)nullptr);
   hipLaunchKernelGGL(field_loss_sum_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (const float*)slot_loss, nslots, loss);
+  MX_LAUNCH_CHECK();
+  return MX_OK;
+}
+
+// mx_field_terms with the device sampler's active flags [nslots]: an inactive slot adds exactly +0 to loss[0]
+int mx_field_terms_masked(const float* sim, const float* simm, const int* active, int nslots, int k, float inv_n, float* loss,
+                          float* gsim, float* slot_loss, void* stream) {
+  MX_CHECK_ARG(sim && simm && active && loss && gsim && slot_loss && nslots > 0 && k > 0 && k <= 256, "field_terms_masked: bad args (k <= 256)");
+  hipLaunchKernelGGL(field_terms_kernel, dim3(nslots), dim3(256), 0, (hipStream_t)stream, sim, simm, k, inv_n, slot_loss, gsim, active);
+  hipLaunchKernelGGL(field_loss_sum_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (const float*)slot_loss, nslots, loss);
+  MX_LAUNCH_CHECK();
+  return MX_OK;
+}
+
+// counts [N*F][3] for every (sample, class) slot in one launch; no lists
+int mx_field_count(const float* mag, const unsigned char* orient, const unsigned* mx, const float* lab_fg, int step, int* counts,
+                   int N, int F, int H, int W, void* stream) {
+  MX_CHECK_ARG(mag && orient && mx && lab_fg && counts && N > 0 && F > 0 && H > 0 && W > 2, "field_count: bad args");
+  MX_CHECK_ARG((long)H * W <= 0x7fffffffL && (long)N * F <= 0x3fffffffL, "field_count: H*W and 2*N*F must fit 32 bits");
+  hipLaunchKernelGGL(field_count_kernel, dim3(N * F), dim3(256), 0, (hipStream_t)stream, mag, orient, mx, lab_fg, step, counts, H, W);
+  MX_LAUNCH_CHECK();
+  return MX_OK;
+}
+
+// state: two uint64 {draw counter, stream key of the latest draw}; pts_out / pts_in [N*F*k][2] int32
+int mx_field_sample(const float* mag, const unsigned char* orient, const unsigned* mx, const int* counts, int step, int k, long seed,
+                    void* state, int* active, int* n_active, int* pts_out, int* pts_in, int N, int F, int H, int W, void* stream) {
+  MX_CHECK_ARG(mag && orient && mx && counts && state && active && n_active && pts_out && pts_in && N > 0 && F > 0 && H > 0 && W > 2 &&
+               k > 0, "field_sample: bad args");
+  MX_CHECK_ARG((long)H * W <= 0x7fffffffL && (long)N * F <= 0x3fffffffL, "field_sample: H*W and 2*N*F must fit 32 bits");
+  MX_CHECK_ARG((long)N * F * k <= 0x3fffffffL, "field_sample: N*F*k = %ld point rows do not fit an int", (long)N * F * k);
+  MX_CHECK_ARG(((uintptr_t)state & 7) == 0, "field_sample: the counter must be 8-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(field_active_kernel, dim3(1), dim3(256), 0, st, counts, N * F, k, (unsigned long long)seed,
+                     (unsigned long long*)state, active, n_active);
+  hipLaunchKernelGGL(field_sample_kernel, dim3(N * F, 2), dim3(256), 0, st, mag, orient, mx, (const int*)active,
+                     (const unsigned long long*)state, step, k, pts_out, pts_in, F, H, W);
   MX_LAUNCH_CHECK();
   return MX_OK;
 }

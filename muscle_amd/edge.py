@@ -7,6 +7,11 @@ the class-softmaxed soft mask.  Here stages 1-2 (edges, ordered point lists), 3 
 MFMA), 5 (the eight FP/FN/TP/TN terms and their gradient) and 6 (softmax backward + scatter) are kernels; the host only
 reads the per-class point counts back (the reference synchronises at the same places) and replays Python's `random`
 in the reference's draw order, so a seeded run picks the same points.
+
+FieldLoss(sampler="device") (ours) draws on the GPU instead: mx_field_count and mx_field_sample take the counts of
+all N*F (sample, class) slots, their active flags and a keyed k-subset per active slot and side; every slot then goes through
+stages 3-6 with mx_field_terms_masked zeroing the inactive ones.  Nothing is read back, so the step can be captured
+(muscle_amd.GraphedMuscleStep).
 """
 from __future__ import annotations
 
@@ -47,7 +52,11 @@ class _FieldLossFn(torch.autograd.Function):
         loss = torch.zeros(1, dtype=torch.float32, device=dev)
         gsim = torch.empty_like(sim)
         slot_loss = torch.empty(S, dtype=torch.float32, device=dev)
-        call("mx_field_terms", ptr(sim), ptr(simm), S, k, 1.0 / N, ptr(loss), ptr(gsim), ptr(slot_loss), stream())
+        active = plan.get("active")                                               # the device sampler's flags [S] (all N*F slots)
+        if active is None:
+            call("mx_field_terms", ptr(sim), ptr(simm), S, k, 1.0 / N, ptr(loss), ptr(gsim), ptr(slot_loss), stream())
+        else:
+            call("mx_field_terms_masked", ptr(sim), ptr(simm), ptr(active), S, k, 1.0 / N, ptr(loss), ptr(gsim), ptr(slot_loss), stream())
         ctx.save_for_backward(feat, gsim)
         ctx.plan = plan
         ctx.dshape = dense.shape
@@ -71,8 +80,17 @@ class _FieldLossFn(torch.autograd.Function):
 
 
 class FieldLoss(nn.Module):
-    def __init__(self, num_classes=21, gaussian_size=7, k=100, guassian_sigma=None, sobel_size=5, beta=1e3):
+    def __init__(self, num_classes=21, gaussian_size=7, k=100, guassian_sigma=None, sobel_size=5, beta=1e3, sampler="host", seed=0):
+        """sampler: "host" (the reference's draws: counts read back, Python's `random.sample`) or "device" (ours: counts, the
+        active slots and a keyed k-subset per slot and side all stay on the GPU - DESIGN.md 7a; nothing is read back, the loss
+        is always a 0-dim device tensor, exactly 0 with an all-zero gradient when no slot is active).  seed: the device sampler's
+        seed; its draw counter lives in device memory and advances once per forward (`draws` mirrors it on the host)."""
         super().__init__()
+        if sampler not in ("host", "device"):
+            raise ValueError(f"sampler must be 'host' or 'device' (got {sampler!r})")
+        self.sampler, self.seed, self.draws = sampler, int(seed), 0
+        self._state = None               # uint64 {draw counter, stream key of the latest draw}, on the device (int64 storage)
+        self.last_sample = None          # device sampler: the latest {"counts", "active", "n_active", "pts_out", "pts_in"}
         if sobel_size != 5:
             raise NotImplementedError("the HIP path implements the 5x5 Sobel the reference trains with (train_muscle.py:163)")
         if k % 4 or k > 256:
@@ -85,7 +103,8 @@ class FieldLoss(nn.Module):
 
     def forward(self, seg_map, dense_ft, mask, label_with_bg, step=7, dense_is_lowres_nhwc: bool = False):
         """Returns (loss, edge magnitude [N,H,W]); loss is a tensor, the int 0 when no class has more than k points on
-        both sides, or False when fewer than 10 boundary pixels exist (edge.py:376-383).
+        both sides, or False when fewer than 10 boundary pixels exist (edge.py:376-383).  With sampler="device" the loss is
+        always a 0-dim device tensor (exactly 0 in those two cases) and `last_sample` holds the draw.
         dense_ft: [N,CH,H,W] as MuSCLe.forward(cam='seg') returns it, or — dense_is_lowres_nhwc — the decoder's
         1/8-resolution NHWC map, upsampled on the fly at the sampled points only.
         mask: the soft label [N,K,H,W], or a hard label map [N,H,W] uint8 (mask_type="label"): then the mask row of a sampled
@@ -126,6 +145,30 @@ class FieldLoss(nn.Module):
             else:
                 mode, h, w, CH = 0, 0, 0, dense.shape[1]
             plan = dict(S=S, k=k, CH=CH, seg_shape=(N, K, H, W), mode=mode, h=h, w=w, pts=pts, **mask_kw)
+            return _FieldLossFn.apply(dense, plan), edge_fg
+        if self.sampler == "device":
+            k, S = self.k, N * F_
+            if HW > 2 ** 31 - 1 or S * k > 2 ** 30 - 1:
+                raise ValueError(f"the device sampler needs H*W < 2^31 and N*F*k < 2^30 (got {HW}, {S * k})")
+            if self._state is None or self._state.device != dev:
+                self._state = torch.zeros(2, dtype=torch.int64, device=dev)       # (filled by kernels: no host copy, no sync)
+                self._state[0] += self.draws
+            counts = torch.empty(S, 3, dtype=torch.int32, device=dev)
+            active = torch.empty(S, dtype=torch.int32, device=dev)
+            n_active = torch.empty(1, dtype=torch.int32, device=dev)
+            pts = [torch.empty(S * k, 2, dtype=torch.int32, device=dev) for _ in (0, 1)]
+            call("mx_field_count", ptr(mag), ptr(orient), ptr(mx), ptr(lab), int(step), ptr(counts), N, F_, H, W, stream())
+            seed = self.seed & (2 ** 64 - 1)
+            call("mx_field_sample", ptr(mag), ptr(orient), ptr(mx), ptr(counts), int(step), k, seed - 2 ** 64 if seed >= 2 ** 63 else seed,
+                 ptr(self._state), ptr(active), ptr(n_active), ptr(pts[0]), ptr(pts[1]), N, F_, H, W, stream())
+            self.draws += 1
+            self.last_sample = dict(counts=counts, active=active, n_active=n_active, pts_out=pts[0], pts_in=pts[1])
+            dense = dense_ft.contiguous().float()
+            if dense_is_lowres_nhwc:
+                mode, h, w, CH = 1, dense.shape[1], dense.shape[2], dense.shape[3]
+            else:
+                mode, h, w, CH = 0, 0, 0, dense.shape[1]
+            plan = dict(S=S, k=k, CH=CH, seg_shape=(N, K, H, W), mode=mode, h=h, w=w, pts=pts, active=active, **mask_kw)
             return _FieldLossFn.apply(dense, plan), edge_fg
         lab_h = lab.cpu()
         slots = [(b, c) for b in range(N) for c in range(F_) if lab_h[b, c] != 0]

@@ -12,6 +12,10 @@ which registers its Philox offset with the graph, so every replay draws fresh nu
 
 Phase 2 (ep >= 8: PixPro + EMD) builds its crop geometry on the host from coord1/coord2 and is not captured; a
 `GraphedStep` refuses ep >= 8.  Epoch gate 4 (IMC on/off) changes the captured work: one GraphedStep per gate value.
+
+`GraphedMuscleStep` is the same for the decoder / BEACON step (`muscle_step`), which is graph-safe once the boundary points
+are drawn on the device (`edge.FieldLoss(sampler="device")`): the sampler's draw counter is device memory the
+captured launch advances, so every replay draws fresh points.
 """
 from __future__ import annotations
 
@@ -19,7 +23,7 @@ from typing import Dict, Optional
 
 import torch
 
-from .train_step import mcl_step
+from .train_step import mcl_step, muscle_step
 
 _KEYS = ("img", "label")
 
@@ -91,5 +95,91 @@ class GraphedStep:
         self.opt.sync_lr()
         self.graph.replay()
         self.opt.note_replayed_step()
+        self.replays += 1
+        return self.out
+
+
+class GraphedMuscleStep:
+    """step = GraphedMuscleStep(model, optimizer, criterion2, lamb=..., step=..., k=...); out = step(batch) for every batch of
+    the same shapes: the decoder / BEACON step (`muscle_step`) as a hipGraph, built like `GraphedStep`.
+
+    The step has no data-dependent host decision once the boundary points are taken on the device
+    (`edge.FieldLoss(sampler="device")`: counts, active slots and the keyed k-subsets stay on the GPU, the loss is always a
+    device tensor), so criterion2 must be such a criterion.  Its draw counter is device memory the captured sampling launch
+    advances, so every replay draws fresh points; `criterion2.draws` follows on the host.  batch: "img" [N,3,S,S], "label"
+    [N,20], "mask" soft fp32 [N,K,S,S] or a uint8 label map [N,S,S]; other keys are ignored.  The energy loss and multi-GPU
+    gradient hooks are not captured.  The returned dict (loss_seg, loss_beacon, grad_norm) holds tensors the next replay
+    overwrites."""
+    _KEYS = ("img", "label", "mask")
+
+    def __init__(self, model, optimizer, criterion2, *, lamb: float, step: int, k: int, warmup: int = 2, grad_hook=None,
+                 energy=None):
+        if getattr(criterion2, "sampler", None) != "device":
+            raise ValueError("GraphedMuscleStep needs a FieldLoss(sampler='device'): the host sampler reads the point counts back")
+        if getattr(criterion2, "replay_points", None) is not None:
+            raise ValueError("GraphedMuscleStep draws on the device; a criterion with replay_points is not captured")
+        if grad_hook is not None:
+            raise ValueError("GraphedMuscleStep is the single-GPU path; multi-GPU runs use muscle_step with a grad_hook")
+        if energy is not None:
+            raise ValueError("GraphedMuscleStep does not capture the energy loss; use muscle_step")
+        if warmup < 1:
+            raise ValueError("at least one eager step must precede the capture (it creates the optimizer's device state)")
+        self.model, self.opt, self.crit = model, optimizer, criterion2
+        self.lamb, self.step, self.k, self.warmup = float(lamb), int(step), int(k), int(warmup)
+        optimizer.use_device_scalars(True)
+        self.calls = 0
+        self.graph: Optional[torch.cuda.CUDAGraph] = None
+        self.static: Dict[str, torch.Tensor] = {}
+        self.out = None
+        self.replays = 0
+
+    def _body(self, batch):
+        return muscle_step(self.model, self.opt, batch, lamb=self.lamb, step=self.step, k=self.k, criterion2=self.crit)
+
+    def close(self):
+        """Hand the optimizer back to host-side scalars (after the last replay).  Also what leaving a
+        `with GraphedMuscleStep(...) as step:` block does."""
+        self.opt.use_device_scalars(False)
+        self.graph = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __call__(self, batch: Dict[str, torch.Tensor]):
+        self.calls += 1
+        self.opt.sync_lr()                          # an lr scheduler may have stepped since the last call
+        if self.graph is None and self.calls <= self.warmup:
+            return self._body(batch)
+        if self.graph is None:
+            self.static = {k: batch[k].clone() for k in self._KEYS}
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            g = torch.cuda.CUDAGraph()
+            draws = self.crit.draws
+            with torch.cuda.stream(side):
+                with torch.cuda.graph(g, stream=side):
+                    self.out = self._body(self.static)
+            torch.cuda.current_stream().wait_stream(side)
+            # capture enqueued nothing: undo the host-side counts the captured step advanced (optimizer steps, sampler draws)
+            for group, idx in self.opt._touched:
+                for q in idx:
+                    group["_steps"][q] -= 1
+            self._draws_per_step = self.crit.draws - draws          # 1, or 0 when lamb == 0 leaves the criterion out
+            self.crit.draws = draws
+            self.graph = g
+        else:
+            for k in self._KEYS:
+                if batch[k].shape != self.static[k].shape or batch[k].dtype != self.static[k].dtype:
+                    raise ValueError(f"GraphedMuscleStep was captured for {k} of shape {tuple(self.static[k].shape)} "
+                                     f"{self.static[k].dtype}, got {tuple(batch[k].shape)} {batch[k].dtype}")
+                self.static[k].copy_(batch[k], non_blocking=True)
+        self.opt.sync_lr()
+        self.graph.replay()
+        self.opt.note_replayed_step()
+        self.crit.draws += self._draws_per_step
         self.replays += 1
         return self.out

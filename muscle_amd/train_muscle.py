@@ -18,6 +18,10 @@ Differences a caller can see:
   * --energy_weight W (new, default 0: off) adds W times the dense-CRF energy loss of muscle_amd/crf_loss.py (ours, not the
     reference's) to the loss, with --energy_sxy / --energy_srgb / --energy_scale / --energy_trunc; the progress line gains
     loss_energy.  It reaches the pixels a label map ignores (255) inside the crop window;
+  * --beacon_sampler device (new; default host: the reference's `random.sample` draws on the host) takes BEACON's boundary
+    points on the GPU (edge.FieldLoss(sampler="device"), seeded by --seed): the step then has no host synchronisation, and
+    --graph 1 (new, default 0; needs --beacon_sampler device, refuses --energy_weight > 0) replays it as a hipGraph
+    (muscle_amd.GraphedMuscleStep);
   * --tblog_dir is created and otherwise unused (the reference opens a tensorboardX writer and never writes to it).
 """
 from __future__ import annotations
@@ -75,7 +79,16 @@ def parse_args(argv: Optional[List[str]] = None):
     ap.add_argument("--energy_srgb", default=15.0, type=float, help="its colour width")
     ap.add_argument("--energy_scale", default=4, type=int, choices=(1, 2, 4, 8), help="its pooling factor (crop_size % scale == 0)")
     ap.add_argument("--energy_trunc", default=2.0, type=float, help="its window: ceil(trunc * sxy / scale) cells; <= 0: all pairs")
+    ap.add_argument("--beacon_sampler", default="host", choices=("host", "device"),
+                    help="host: BEACON's boundary points by Python's random.sample, as the reference draws them; device: a keyed "
+                         "k-subset taken on the GPU (seed: --seed), no host synchronisation in the step")
+    ap.add_argument("--graph", default=0, type=int, choices=(0, 1),
+                    help="1: replay the training step as a hipGraph (needs --beacon_sampler device; not with --energy_weight > 0)")
     args = ap.parse_args(argv)
+    if args.graph and args.beacon_sampler != "device":
+        ap.error("--graph 1 needs --beacon_sampler device (the host sampler reads the point counts back every step)")
+    if args.graph and args.energy_weight > 0:
+        ap.error("--graph 1 does not capture the energy loss (--energy_weight must be 0)")
     if not 1 <= args.val_batch <= 8:
         ap.error(f"--val_batch {args.val_batch} outside 1..8")
     if args.energy_weight < 0:
@@ -122,15 +135,21 @@ def main(argv: Optional[List[str]] = None) -> int:
     model = model.to(dev)
     optimizer = muscle_amd.FusedAdam(model.parameters(), lr=args.lr, weight_decay=args.wt_dec)
     scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(optimizer, "max", patience=0, cooldown=0, factor=0.5, min_lr=5e-6)
-    criterion2 = edge.FieldLoss(sobel_size=5, beta=1e2, k=args.k)
+    criterion2 = edge.FieldLoss(sobel_size=5, beta=1e2, k=args.k, sampler=args.beacon_sampler, seed=args.seed)
+    graphed = None
+    if args.graph:
+        graphed = muscle_amd.GraphedMuscleStep(model, optimizer, criterion2, lamb=args.lamb, step=args.step, k=args.k)
     start = stage_start = time.time()
     print("Session started: ", time.ctime(start))
     for ep in range(args.max_epoches):
         model.train()
         print("lr: %.6f" % (optimizer.param_groups[0]["lr"]))
         for it, (_names, batch) in enumerate(loader):
-            out = muscle_amd.muscle_step(model, optimizer, batch, lamb=args.lamb, step=args.step, k=args.k, criterion2=criterion2,
-                                         energy=energy, energy_weight=args.energy_weight)
+            if graphed is not None:
+                out = graphed(batch)
+            else:
+                out = muscle_amd.muscle_step(model, optimizer, batch, lamb=args.lamb, step=args.step, k=args.k, criterion2=criterion2,
+                                             energy=energy, energy_weight=args.energy_weight)
             if it % 25 == 0:                                                                # :210-218
                 elapsed = time.time() - start
                 est_finish = int(start + elapsed / (it / max_step + 1))

@@ -228,7 +228,9 @@ def muscle_step(model, optimizer, batch: Dict[str, torch.Tensor], *, lamb: float
     MuSCLe.py:285 is never materialised); False goes through the public forward(cam='seg') tensors.
     energy (ours, not the reference's): a `crf_loss.DenseEnergyLoss`; with a non-zero energy_weight the loss gains
     energy_weight * energy(seg_map, img, batch.get("window")) and the returned dict "loss_energy", for either kind of mask.
-    None, or weight 0: the launches and the returned keys are those of the reference's step."""
+    None, or weight 0: the launches and the returned keys are those of the reference's step.
+    criterion2: with an `edge.FieldLoss(sampler="device")` the step has no host synchronisation ("loss_beacon" is always a
+    device tensor) and can be captured: `muscle_amd.GraphedMuscleStep`."""
     from . import edge
     img, label, mask = batch["img"], batch["label"].float(), batch["mask"]
     optimizer.zero_grad()
