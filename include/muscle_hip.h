@@ -831,6 +831,56 @@ int mx_crf_loss_fwd(const float* seg, const float* img, const int* window, int N
 int mx_crf_loss_bwd(const float* seg, const int* window, const float* M, const double* sums, const float* g, int N, int K, int H, int W,
                     int f, float* gseg, void* stream);
 
+/* ---- Lovasz-softmax loss of decoder training on a segmented device radix sort (csrc/lovasz.hip).  OURS, not the reference's:
+ * the loss of Berman, Triki & Blaschko, "The Lovasz-Softmax loss" (CVPR 2018), for hard label maps.
+ *
+ * Input.  seg fp32 [N,K,HW] logits, label uint8 [N,HW].  A pixel is VALID when label != ignore and label < K; any other value is
+ *   ignored and never used as an index.  p = softmax_k(seg) per pixel, fp32.
+ * Groups.  per_image == 0: one group of all N*HW pixels; per_image != 0: N groups of HW pixels.  A segment is a (group, class) pair,
+ *   s = group*K + c; S = groups*K segments of P elements each (N*HW or HW).  The flat index j of an element is its pixel order inside
+ *   the group (n*HW + hw, or hw).
+ * Per segment (group, c), over the valid pixels of the group:  fg_j = (label_j == c);  e_j = |fg_j - p_c(j)| in fp32;  G = sum fg_j;
+ *   V = the number of valid pixels.
+ * Order.  Descending in e, ties by ascending j: np.argsort(-e, kind="stable") over the valid elements.  rank_j in 0..V-1 is the
+ *   element's position in that order; an ignored element has rank -1 and coefficient 0.
+ * Jaccard increments.  i = rank + 1, F_i = the foreground count among the first i elements, I_i = G - F_i, U_i = G + i - F_i:
+ *     the element at i is foreground:  g_i = 1 / U_i
+ *     background and G > 0:            g_i = I_i / (U_i (U_i - 1))
+ *     G == 0:                          g_1 = 1, every other g_i = 0
+ *   formed in fp64 from the integer counts and rounded to fp32 once (never as a difference of two Jaccard values).
+ * Segment loss.  L = sum_j e_j g_{rank_j}: products and sums in fp64, a fixed order.
+ * Counted segments.  classes_all == 0 ("present"): G > 0 and V > 0; classes_all != 0 ("all"): V > 0.  C_grp = the number of counted
+ *   segments of a group.  loss = (1/groups) sum_grp (1/C_grp) sum_counted L; a group with C_grp == 0 adds 0; nothing counted: the
+ *   loss is exactly 0 and the gradient all zeros (the mx_ce_label convention).
+ * Gradient.  coef_c(j) = w s g_{rank_j}, w = 1 / (groups C_grp) for a counted segment, else 0; s = -1 for a foreground element with
+ *   p_c < 1, +1 for a background element with p_c > 0, else 0 (torch's abs subgradient: 0 at e == 0).
+ *   gseg_k = gup p_k (coef_k - sum_c coef_c p_c) at valid pixels, exactly 0 at ignored ones.
+ * Sort key.  e in [0,1], so bits(e) <= 0x3F800000 and key = 0x3F800000 - bits(|e|) sorts ascending; a value outside [0,1] (NaN, from
+ *   non-finite logits) takes key 0 and sorts as e = 1 (results are then unspecified, but rank stays a permutation and nothing
+ *   indexes out of range); an ignored element takes 0x40000000, above every valid key.  Inside the sort bit 31 carries fg and is
+ *   no part of any digit.
+ * The sort is a stable LSD radix sort of (key, j) pairs, 8-bit digits, 4 passes of three launches (per-block digit histogram,
+ *   exclusive scan over (segment, digit, block), stable scatter by wave ballots), S independent segments; F_i is a segmented
+ *   scan of the same structure.  Integer atomics for counts only; no workgroup waits for another; the same bits every run.
+ * Limits: 1 <= K <= 24, P < 2^31, S * P < 2^32.  ws: mx_lovasz_ws(S, P) bytes, 16-byte aligned, contents need not survive between
+ * calls.  Nothing synchronises with the host. */
+long mx_lovasz_ws(int S, long P);                                       /* < 0: bad arguments */
+/* stage 1: err fp32 [S,P] = e and flag uint8 [S,P] (bit 0: foreground, bit 1: valid; an ignored element has err 0, flag 0) */
+int mx_lovasz_errors(const float* seg, const unsigned char* label, int ignore, int N, int K, long HW, int per_image, float* err,
+                     unsigned char* flag, void* stream);
+/* stages 2 and 3 on GIVEN errors: rank int32 [S,P] (may be NULL), coef_g fp32 [S,P] = g at each element in the original order (0 at
+ * an ignored one), seg_loss fp64 [S] = L, seg_counts int32 [S][2] = (G, V) */
+int mx_lovasz_core(const float* err, const unsigned char* flag, int S, long P, int* rank, float* coef_g, double* seg_loss,
+                   int* seg_counts, void* ws, long ws_bytes, void* stream);
+/* the loss: stages 1-3 and the class weighting.  err, flag, coef_g [S,P], seg_loss [S], seg_counts [S][2] as above (all written);
+ * segw fp32 [S] = w of each segment; loss fp32 [1] (written, not added) */
+int mx_lovasz_fwd(const float* seg, const unsigned char* label, int ignore, int N, int K, long HW, int per_image, int classes_all,
+                  float* err, unsigned char* flag, float* coef_g, double* seg_loss, int* seg_counts, float* segw, float* loss, void* ws,
+                  long ws_bytes, void* stream);
+/* backward: gseg [N,K,HW] (every element written) from the forward's coef_g and segw and the upstream scalar gup [1] */
+int mx_lovasz_bwd(const float* seg, const unsigned char* label, int ignore, const float* coef_g, const float* segw, const float* gup,
+                  int N, int K, long HW, int per_image, float* gseg, void* stream);
+
 /* ---- the permutohedral-lattice backend of both CRFs (csrc/lattice.hip): the filter pydensecrf evaluates the models of
  * src/imutils.py:439-456 and src/imutils.py:477-491 on (Adams, Baek & Davis 2010).  A DIFFERENT model from the windowed sums above
  * (its messages differ from the exact ones by up to a quarter of their size on sparse lattices), selectable, never the default; its

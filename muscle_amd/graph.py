@@ -107,13 +107,13 @@ class GraphedMuscleStep:
     (`edge.FieldLoss(sampler="device")`: counts, active slots and the keyed k-subsets stay on the GPU, the loss is always a
     device tensor), so criterion2 must be such a criterion.  Its draw counter is device memory the captured sampling launch
     advances, so every replay draws fresh points; `criterion2.draws` follows on the host.  batch: "img" [N,3,S,S], "label"
-    [N,20], "mask" soft fp32 [N,K,S,S] or a uint8 label map [N,S,S]; other keys are ignored.  The energy loss and multi-GPU
+    [N,20], "mask" soft fp32 [N,K,S,S] or a uint8 label map [N,S,S]; other keys are ignored.  The energy loss, the Lovasz-softmax loss and multi-GPU
     gradient hooks are not captured.  The returned dict (loss_seg, loss_beacon, grad_norm) holds tensors the next replay
     overwrites."""
     _KEYS = ("img", "label", "mask")
 
     def __init__(self, model, optimizer, criterion2, *, lamb: float, step: int, k: int, warmup: int = 2, grad_hook=None,
-                 energy=None):
+                 energy=None, lovasz=None):
         if getattr(criterion2, "sampler", None) != "device":
             raise ValueError("GraphedMuscleStep needs a FieldLoss(sampler='device'): the host sampler reads the point counts back")
         if getattr(criterion2, "replay_points", None) is not None:
@@ -122,6 +122,8 @@ class GraphedMuscleStep:
             raise ValueError("GraphedMuscleStep is the single-GPU path; multi-GPU runs use muscle_step with a grad_hook")
         if energy is not None:
             raise ValueError("GraphedMuscleStep does not capture the energy loss; use muscle_step")
+        if lovasz is not None:
+            raise ValueError("GraphedMuscleStep does not capture the Lovasz-softmax loss; use muscle_step")
         if warmup < 1:
             raise ValueError("at least one eager step must precede the capture (it creates the optimizer's device state)")
         self.model, self.opt, self.crit = model, optimizer, criterion2

@@ -20,8 +20,11 @@ Differences a caller can see:
     loss_energy.  It reaches the pixels a label map ignores (255) inside the crop window;
   * --beacon_sampler device (new; default host: the reference's `random.sample` draws on the host) takes BEACON's boundary
     points on the GPU (edge.FieldLoss(sampler="device"), seeded by --seed): the step then has no host synchronisation, and
-    --graph 1 (new, default 0; needs --beacon_sampler device, refuses --energy_weight > 0) replays it as a hipGraph
-    (muscle_amd.GraphedMuscleStep);
+    --graph 1 (new, default 0; needs --beacon_sampler device, refuses --energy_weight > 0 and --lovasz_weight > 0) replays it
+    as a hipGraph (muscle_amd.GraphedMuscleStep);
+  * --lovasz_weight W (new, default 0: off; needs --mask_type label, refuses --graph 1) adds W times the Lovasz-softmax loss of
+    muscle_amd/lovasz.py (ours, not the reference's: Berman et al. 2018, a surrogate of the mIoU the validation reports) to the
+    loss, with --lovasz_classes present|all and --lovasz_per_image 0|1; the progress line gains loss_lovasz;
   * --tblog_dir is created and otherwise unused (the reference opens a tensorboardX writer and never writes to it).
 """
 from __future__ import annotations
@@ -79,16 +82,29 @@ def parse_args(argv: Optional[List[str]] = None):
     ap.add_argument("--energy_srgb", default=15.0, type=float, help="its colour width")
     ap.add_argument("--energy_scale", default=4, type=int, choices=(1, 2, 4, 8), help="its pooling factor (crop_size % scale == 0)")
     ap.add_argument("--energy_trunc", default=2.0, type=float, help="its window: ceil(trunc * sxy / scale) cells; <= 0: all pairs")
+    ap.add_argument("--lovasz_weight", default=0.0, type=float,
+                    help="weight of the Lovasz-softmax loss (muscle_amd/lovasz.py; ours, not the reference's); 0: off; needs "
+                         "--mask_type label")
+    ap.add_argument("--lovasz_classes", default="present", choices=("present", "all"),
+                    help="present: average over the classes that occur among the labelled pixels; all: over every class")
+    ap.add_argument("--lovasz_per_image", default=0, type=int, choices=(0, 1), help="1: one Lovasz term per image, averaged")
     ap.add_argument("--beacon_sampler", default="host", choices=("host", "device"),
                     help="host: BEACON's boundary points by Python's random.sample, as the reference draws them; device: a keyed "
                          "k-subset taken on the GPU (seed: --seed), no host synchronisation in the step")
     ap.add_argument("--graph", default=0, type=int, choices=(0, 1),
-                    help="1: replay the training step as a hipGraph (needs --beacon_sampler device; not with --energy_weight > 0)")
+                    help="1: replay the training step as a hipGraph (needs --beacon_sampler device; not with --energy_weight > 0 or "
+                         "--lovasz_weight > 0)")
     args = ap.parse_args(argv)
     if args.graph and args.beacon_sampler != "device":
         ap.error("--graph 1 needs --beacon_sampler device (the host sampler reads the point counts back every step)")
     if args.graph and args.energy_weight > 0:
         ap.error("--graph 1 does not capture the energy loss (--energy_weight must be 0)")
+    if args.lovasz_weight < 0:
+        ap.error(f"--lovasz_weight {args.lovasz_weight} is negative")
+    if args.lovasz_weight > 0 and args.mask_type != "label":
+        ap.error("--lovasz_weight > 0 needs --mask_type label (the Lovasz-softmax loss is defined on label maps)")
+    if args.graph and args.lovasz_weight > 0:
+        ap.error("--graph 1 does not capture the Lovasz-softmax loss (--lovasz_weight must be 0)")
     if not 1 <= args.val_batch <= 8:
         ap.error(f"--val_batch {args.val_batch} outside 1..8")
     if args.energy_weight < 0:
@@ -128,6 +144,9 @@ def main(argv: Optional[List[str]] = None) -> int:
     if args.energy_weight > 0:
         from muscle_amd.crf_loss import DenseEnergyLoss
         energy = DenseEnergyLoss(args.energy_sxy, args.energy_srgb, args.energy_scale, args.energy_trunc)
+    lovasz = None
+    if args.lovasz_weight > 0:
+        lovasz = muscle_amd.LovaszSoftmaxLoss(args.lovasz_classes, bool(args.lovasz_per_image))
     val_names = read_names(args.val_list)
     max_step = len(train_dataset) // args.batch_size * args.max_epoches
     if args.weights:
@@ -149,7 +168,8 @@ def main(argv: Optional[List[str]] = None) -> int:
                 out = graphed(batch)
             else:
                 out = muscle_amd.muscle_step(model, optimizer, batch, lamb=args.lamb, step=args.step, k=args.k, criterion2=criterion2,
-                                             energy=energy, energy_weight=args.energy_weight)
+                                             energy=energy, energy_weight=args.energy_weight, lovasz=lovasz,
+                                             lovasz_weight=args.lovasz_weight)
             if it % 25 == 0:                                                                # :210-218
                 elapsed = time.time() - start
                 est_finish = int(start + elapsed / (it / max_step + 1))
@@ -157,6 +177,7 @@ def main(argv: Optional[List[str]] = None) -> int:
                       "loss_seg:%.4f" % (float(out["loss_seg"])),
                       "loss_beacon:%.4f" % (float(out["loss_beacon"])),
                       *(("loss_energy:%.4f" % (float(out["loss_energy"])),) if "loss_energy" in out else ()),
+                      *(("loss_lovasz:%.4f" % (float(out["loss_lovasz"])),) if "loss_lovasz" in out else ()),
                       "imps:%.1f" % ((it + 1) * args.batch_size / (time.time() - stage_start)),
                       "Fin:%s" % (time.ctime(est_finish)), flush=True)
         torch.save(model.state_dict(), os.path.join(args.session_name, "_{}".format(str(ep)) + ".pth"))

@@ -218,7 +218,8 @@ def mcl_step(model, optimizer, batch: Dict[str, torch.Tensor], ep: int, *, drop_
 
 
 def muscle_step(model, optimizer, batch: Dict[str, torch.Tensor], *, lamb: float = 0.05, step: int = 7, k: int = 128,
-                criterion2=None, drop_u=None, grad_hook=None, fused: bool = True, energy=None, energy_weight: float = 0.0):
+                criterion2=None, drop_u=None, grad_hook=None, fused: bool = True, energy=None, energy_weight: float = 0.0,
+                lovasz=None, lovasz_weight: float = 0.0):
     """One iteration of train_muscle.py:171-203 on the HIP path: seg forward of MuSCLe(mode='dec'), cross entropy against the
     arg-max of the soft pseudo-label, lamb * BEACON FieldLoss, backward, clip_grad_norm_(9), optimizer step.
     batch: {"img" [N,3,S,S], "label" [N,20], "mask" [N,21,S,S]} on the GPU.  A uint8 "mask" [N,S,S] is a hard label map
@@ -229,10 +230,17 @@ def muscle_step(model, optimizer, batch: Dict[str, torch.Tensor], *, lamb: float
     energy (ours, not the reference's): a `crf_loss.DenseEnergyLoss`; with a non-zero energy_weight the loss gains
     energy_weight * energy(seg_map, img, batch.get("window")) and the returned dict "loss_energy", for either kind of mask.
     None, or weight 0: the launches and the returned keys are those of the reference's step.
+    lovasz (ours, not the reference's): a `lovasz.LovaszSoftmaxLoss`; with a non-zero lovasz_weight the loss gains
+    lovasz_weight * lovasz(seg_map, mask) and the returned dict "loss_lovasz".  The loss is defined on label maps only: a soft
+    mask raises ValueError.  None, or weight 0: nothing new is launched and the returned keys are unchanged.
     criterion2: with an `edge.FieldLoss(sampler="device")` the step has no host synchronisation ("loss_beacon" is always a
     device tensor) and can be captured: `muscle_amd.GraphedMuscleStep`."""
     from . import edge
     img, label, mask = batch["img"], batch["label"].float(), batch["mask"]
+    use_lovasz = lovasz is not None and lovasz_weight != 0
+    if use_lovasz and not (mask.dtype == torch.uint8 and mask.dim() == 3):
+        raise ValueError(f"the Lovasz-softmax loss takes a label map [N,S,S] uint8 (mask_type='label'), not a soft mask "
+                         f"({mask.dtype} {tuple(mask.shape)})")
     optimizer.zero_grad()
     if not model.training:             # (walking ~150 submodules costs 0.65 ms of host time per call)
         model.train()
@@ -253,6 +261,10 @@ def muscle_step(model, optimizer, batch: Dict[str, torch.Tensor], *, lamb: float
     if energy is not None and energy_weight != 0:
         l3 = energy(seg_map, img, batch.get("window"))
         loss = loss + energy_weight * l3
+    l4 = None
+    if use_lovasz:
+        l4 = lovasz(seg_map, mask)
+        loss = loss + lovasz_weight * l4
     optimizer.zero_grad()
     loss.backward()
     if grad_hook is not None:
@@ -262,4 +274,6 @@ def muscle_step(model, optimizer, batch: Dict[str, torch.Tensor], *, lamb: float
     out = {"loss_seg": l1, "loss_beacon": l2, "grad_norm": total}
     if l3 is not None:
         out["loss_energy"] = l3
+    if l4 is not None:
+        out["loss_lovasz"] = l4
     return out
