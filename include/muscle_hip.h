@@ -1094,6 +1094,46 @@ int mx_label_edge_dist(const unsigned char* label, int H, int W, int dmax, int e
 int mx_boundary_counts(const unsigned char* pred, const unsigned char* gt, const unsigned char* dt, const unsigned char* db,
                        const unsigned char* dp, int K, int H, int W, int dmax, int d_img, long long* hist, long long* ratio, void* stream);
 
+/* ---- pixel-adaptive mask refinement (PAMR; Araslanov & Roth, "Single-Stage Semantic Segmentation from Image Labels", CVPR 2020;
+ * csrc/pamr.hip, muscle_amd/pamr.py, DESIGN.md "PAMR").  A local affinity from the image, once per image, then a few fixed-point
+ * iterations of a convex 8 D-neighbour stencil on every channel of a mask.  The reference does not ship it; what is pinned is the
+ * model below against its numpy restatement (tests/pamr_ref.py); parity with the published PAMR code unpinned.
+ *
+ * Inputs.  An image I with 3 channels, H x W; a mask m fp32 [C,H,W]; dilations d_0..d_{D-1} (the published default: 1,2,4,8,12,24);
+ *   num_iter (default 10).  The published module resizes the mask bilinearly to the image size first; here both have the same H x W.
+ * Neighbours.  Offsets o_0..o_7 = (-1,-1),(-1,0),(-1,1),(0,-1),(0,1),(1,-1),(1,0),(1,1) as (dy,dx).  Neighbour p = 8 j + k, P = 8 D in
+ *   all, of the pixel (y,x) is the pixel (clamp(y + d_j dy_k, 0, H-1), clamp(x + d_j dx_k, 0, W-1)): replicate padding.
+ * std_c(y,x) = the unbiased standard deviation (divide by 9 D - 1) of the 9 D values of channel c at the 9 positions, centre
+ *   included, of every dilation: all dilations pooled into one sample (mean first, then the squared deviations; j-major, rows top to
+ *   bottom, left to right).
+ * a_p(y,x) = (1/3) sum_c -|I_c(y,x) - I_c(nbr_p)| / (1e-8 + 0.1 std_c(y,x))
+ * w_p(y,x) = softmax over p of a_p(y,x), the maximum subtracted first; where std = 0 every a_p is 0 and w_p = 1/P.
+ * m_{s+1}[c,y,x] = sum_p w_p(y,x) m_s[c, nbr_p],  s = 0..num_iter-1; the sum runs p = 0..P-1 in this order, starting from 0.
+ * The result is m_{num_iter}; num_iter = 0 returns the input bits.
+ * Arithmetic.  Every stored value (w, every m_s) and every operation of std_c, a_p and exp is fp32.  Two sums are ACCUMULATED in
+ *   fp64 and rounded to fp32 once: the softmax normaliser sum_p exp(..), so that the fp32 weights of a pixel sum to 1 within 5e-8, and
+ *   the stencil sum (exact products of two fp32 values, an fp64 chain in the order above).  A constant mask repeats the same
+ *   roundings at a pixel in every iteration; an fp32 chain moved a constant 1.0 by 3.4e-6 .. 5.2e-6 in 10 iterations (the float32
+ *   restatement does the same), this one stays within 6e-7 (the bound asked of it is 1e-6).
+ * No atomics: the same inputs give the same bits in every run.  Nothing synchronises with the host.
+ * Limits (argument errors, a negative return before any launch): 1 <= D <= 8, every dilation in 1..64, N, C, H, W >= 1,
+ *   N max(C,P) H W < 2^31.  There is no cap on C. */
+/* w fp32 [N,P,H,W] (planar, every element written) from img: img_kind 0 = uint8 [N,H,W,3] (what the CRFs take), img_kind 1 = fp32
+ * [N,3,H,W]; equal values give equal bits.  dil: D ints in HOST memory. */
+int mx_pamr_affinity(const void* img, int img_kind, int N, int H, int W, const int* dil, int D, float* w, void* stream);
+/* one iteration: m_out [N,C,H,W] from m_in and w.  One thread owns a pixel, holds its P weights in registers and walks the C
+ * channels; the gathers are served by the caches.  m_in must not overlap m_out. */
+int mx_pamr_step(const float* w, const float* m_in, float* m_out, int N, int C, int H, int W, const int* dil, int D, void* stream);
+long mx_pamr_ws(int N, int C, int H, int W, int D);                     /* < 0: bad arguments */
+/* the affinity and num_iter iterations: out [N,C,H,W] = m_{num_iter} for odd and even counts alike (the iterations alternate between
+ * out and one buffer of the workspace; num_iter = 0 is a device copy); mask is only read and must not overlap out.  The same bits as
+ * mx_pamr_affinity followed by num_iter calls of mx_pamr_step.  ws: mx_pamr_ws(N, C, H, W, D) bytes, 16-byte aligned, contents need
+ * not survive between calls. */
+int mx_pamr(const void* img, int img_kind, const float* mask, float* out, int N, int C, int H, int W, const int* dil, int D, int num_iter,
+            void* ws, long ws_bytes, void* stream);
+/* pred uint8 [N,H,W] = argmax_c m[n,c,y,x], first maximum wins (np.argmax on finite data); 1 <= C <= 256 */
+int mx_planar_argmax(const float* m, int N, int C, int H, int W, unsigned char* pred, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

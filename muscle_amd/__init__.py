@@ -29,6 +29,7 @@ from .ir_label import cam_to_ir_label, combine_conf  # noqa: F401,E402  (IR labe
 from .lattice import PermutohedralLattice  # noqa: F401,E402  (the lattice filter; pairwise="lattice" of the CRFs)
 from .crf_loss import DenseEnergyLoss  # noqa: F401,E402  (dense-CRF energy loss of decoder training; train_muscle --energy_weight)
 from .lovasz import LovaszSoftmaxLoss, lovasz_softmax  # noqa: F401,E402  (Lovasz-softmax loss on label maps; train_muscle --lovasz_weight)
+from .pamr import PAMR, pamr_affinity, pamr_apply  # noqa: F401,E402  (pixel-adaptive mask refinement; infer_mcl / infer_seg --pamr_iters)
 from .ins_seg import (InstanceLabels, cluster_centroids, connected_components, find_centroids,  # noqa: F401,E402
                       infer_irn_instances)  # (instance pseudo-labels from the displacement field; infer_irn --ins_seg_out_dir)
 

@@ -84,13 +84,20 @@ def infer_cam(model, img_list: List[torch.Tensor], label: torch.Tensor, H: int, 
 
 
 def infer_cam_fused(model, img_list: List[torch.Tensor], label: torch.Tensor, H: int, W: int, want_cam: bool = True,
-                    want_sgc: bool = True) -> Tuple[Dict[int, np.ndarray], Dict[int, np.ndarray], torch.Tensor]:
+                    want_sgc: bool = True, pamr=None, pamr_img=None
+                    ) -> Tuple[Dict[int, np.ndarray], Dict[int, np.ndarray], torch.Tensor]:
     """`infer_cam` with the post-processing in one launch: the same batch-2 forwards of a scale and its flip, then ONE
     mx_cam_infer over all passes, both maps and only the channels of the image's labels (the sum and the min-max are per
     channel, so the other 17-19 of 20 never need to exist), one mx_infer_norm per requested map on the compact
     [nkeep,H,W] buffer and one device->host copy of it.  Same bits as `infer_cam`.  want_cam / want_sgc = False: that map
     is neither read nor computed and its dict is empty.  An image without labels: empty dicts, nothing launched after the
-    forwards."""
+    forwards.
+    pamr: a muscle_amd.PAMR, with pamr_img the original uint8 image [H,W,3] (numpy or device tensor).  Each requested map is then
+    refined on the device after its mx_infer_norm (muscle_amd/pamr.py states the model; one affinity per image, shared by both
+    maps) and normalised once more, so a saved map still spans [0,1].  With pamr=None nothing of it runs: the launches and the
+    bits of before."""
+    from .pamr import check_pamr_args
+    pimg = check_pamr_args(pamr, pamr_img, H, W)
     if label.dim() != 2 or label.shape[0] != 1:
         raise ValueError("infer_cam_fused handles one image per call (infer_mcl.py's DataLoader has batch_size 1)")
     if not img_list:
@@ -129,10 +136,17 @@ def infer_cam_fused(model, img_list: List[torch.Tensor], label: torch.Tensor, H:
         out_cam = torch.empty(nk, H, W, dtype=torch.float32, device=dev) if want_cam else None
         out_sgc = torch.empty(nk, H, W, dtype=torch.float32, device=dev) if want_sgc else None
         call("mx_cam_infer", ptr(tab), len(rows), lds, K, H, W, ptr(idx), nk, ptr(out_cam), ptr(out_sgc), stream())
+        aff = None
+        if pimg is not None:
+            with torch.cuda.device(dev):
+                aff = pamr.affinity(pamr_img)             # once per image, shared by both maps
         for out, d in ((out_cam, cam_dict), (out_sgc, sgc_dict)):
             if out is None:
                 continue
             call("mx_infer_norm", ptr(out), nk, H * W, stream())
+            if aff is not None:
+                out = pamr.apply(aff, out)
+                call("mx_infer_norm", ptr(out), nk, H * W, stream())
             host = out.cpu().numpy()
             for j, k in enumerate(keep):
                 d[k] = host[j]
@@ -150,7 +164,8 @@ def load_cam_dict(path: str) -> Dict[int, np.ndarray]:
 
 
 def infer_seg(model, img_list: List[torch.Tensor], H: int, W: int, cls_label=None, return_prob: bool = False, crf_img=None,
-              crf_t: int = 4, crf_trunc: float = 4.0, crf_pairwise: str = "window") -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+              crf_t: int = 4, crf_trunc: float = 4.0, crf_pairwise: str = "window", pamr=None, pamr_img=None
+              ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """infer_seg.py:88-133.  model: MuSCLe(mode='dec'); img_list: [1,3,Hs,Ws] device tensors in the order
     of VOC12ClsDatasetMSF (scale-major, plain then flipped; data.MSFStager builds it); cls_label: optional [K] class scores
     (entry 0, the background, is not used: :125).  Returns (pred uint8 [H,W], the fp32 mean probability map [K,H,W] if
@@ -159,9 +174,17 @@ def infer_seg(model, img_list: List[torch.Tensor], H: int, W: int, cls_label=Non
     (crf.crf_inference with crf_t iterations, scale_factor 1.5, window crf_trunc): pred is argmax Q and the returned map
     is Q.  Without it nothing of the CRF runs and the result is what it was before the CRF existed, bit for bit.
     crf_pairwise: "window" (the exact windowed sums, the default) or "lattice" (the permutohedral lattice of muscle_amd.lattice:
-    pydensecrf's own approximation, a different model; crf_trunc is ignored)."""
+    pydensecrf's own approximation, a different model; crf_trunc is ignored).
+    pamr: a muscle_amd.PAMR, with pamr_img the original uint8 image [H,W,3]: the mean map is refined by PAMR instead
+    (muscle_amd/pamr.py states the model): the returned map is the refined one, still a distribution where the mean map is one
+    (every row of weights sums to 1), and pred its argmax, first maximum wins.  Refused together with crf_img.  pamr=None: nothing
+    of it runs."""
     from .lattice import check_pairwise
+    from .pamr import check_pamr_args
     check_pairwise(crf_pairwise)
+    pimg = check_pamr_args(pamr, pamr_img, H, W)
+    if pimg is not None and crf_img is not None:
+        raise ValueError("pamr and crf_img are two refinements of the same map: give one of them")
     if not img_list:
         raise ValueError("infer_seg needs at least one pass")
     model.eval()
@@ -193,8 +216,16 @@ def infer_seg(model, img_list: List[torch.Tensor], H: int, W: int, cls_label=Non
             if cls.numel() != K:
                 raise ValueError(f"cls_label has {cls.numel()} entries, the model {K} classes")
         pred = torch.empty(H, W, dtype=torch.uint8, device=dev)
-        prob = torch.empty(K, H, W, dtype=torch.float32, device=dev) if return_prob or crf_img is not None else None
+        want_map = return_prob or crf_img is not None or pimg is not None
+        prob = torch.empty(K, H, W, dtype=torch.float32, device=dev) if want_map else None
         call("mx_seg_infer", ptr(tab), len(rows), lds, K, H, W, ptr(cls), ptr(pred), ptr(prob), stream())
+        if pimg is not None:
+            from .pamr import planar_argmax
+            with torch.cuda.device(dev):
+                prob = pamr(pamr_img, prob)
+                pred = planar_argmax(prob)
+            if not return_prob:
+                prob = None
         if crf_img is not None:
             from .crf import crf_run
             prob, pred = crf_run(crf_img, prob, crf_t, 1.5, K, 0.5, crf_trunc, want_q=return_prob, want_pred=True,

@@ -7,6 +7,10 @@ Differences a caller can see:
   * --out_cam_npy DIR (new, optional): also writes the raw-CAM dicts the reference has commented out at :181.  Without it
     the CAM map is not computed at all;
   * --pretrained (new, default b3: the backbone hard-coded at :75);
+  * --pamr_iters N [--pamr_dilations 1 2 4 8 12 24] (new, default 0 = off): every saved map is refined on the device by N
+    iterations of pixel-adaptive mask refinement against the image (muscle_amd/pamr.py) and min-max normalised once more, so it
+    still spans [0,1]; the affinity is computed once per image.  Parity with the published PAMR code unpinned, effect on mIoU
+    unmeasured;
   * the files are written by one writer thread behind a bounded queue, so np.save does not hold up the next image's
     forwards; the queue is drained, and a write error re-raised, before the script exits;
   * --num_workers and --tblog are accepted and unused (no tensorboardX overlays, no tqdm bar; `name iter` is printed).
@@ -34,7 +38,28 @@ def parse_args(argv: Optional[List[str]] = None):
     ap.add_argument("--out_npy", default=None, type=str, help="the SGC dicts go to <out_npy>_sgc/<name>.npy")
     ap.add_argument("--out_cam_npy", default=None, type=str, help="directory for the raw-CAM dicts (not computed without it)")
     ap.add_argument("--pretrained", default="b3", type=str)
-    return ap.parse_args(argv)
+    add_pamr_arguments(ap, "every saved map")
+    args = ap.parse_args(argv)
+    check_pamr_arguments(ap, args)
+    return args
+
+
+def add_pamr_arguments(ap: argparse.ArgumentParser, what: str) -> None:
+    """--pamr_iters / --pamr_dilations, shared with muscle_amd.infer_seg."""
+    ap.add_argument("--pamr_iters", default=0, type=int,
+                    help=f"pixel-adaptive mask refinement (muscle_amd/pamr.py) of {what} against the image: iterations (0: off)")
+    ap.add_argument("--pamr_dilations", default=[1, 2, 4, 8, 12, 24], type=int, nargs="+",
+                    help="--pamr_iters > 0: the dilations of the 8-neighbour stencil (1..8 values in 1..64)")
+
+
+def check_pamr_arguments(ap: argparse.ArgumentParser, args) -> None:
+    from muscle_amd.pamr import check_dilations
+    if args.pamr_iters < 0:
+        ap.error(f"--pamr_iters {args.pamr_iters}: the number of PAMR iterations cannot be negative (0 runs none)")
+    try:
+        args.pamr_dilations = list(check_dilations(args.pamr_dilations))
+    except ValueError as e:
+        ap.error(f"--pamr_dilations: {e}")
 
 
 class NpyWriter:
@@ -98,6 +123,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     if args.out_cam_npy is not None:
         os.makedirs(args.out_cam_npy, exist_ok=True)
     want_cam, want_sgc = args.out_cam_npy is not None, args.out_npy is not None
+    pamr = muscle_amd.PAMR(args.pamr_iters, args.pamr_dilations) if args.pamr_iters > 0 else None
     writer = NpyWriter()
     try:
         for it, name in enumerate(read_names(args.infer_list)):
@@ -105,7 +131,8 @@ def main(argv: Optional[List[str]] = None) -> int:
             W, H = img.size
             label = torch.from_numpy(np.asarray(labels[name], dtype=np.float32)).view(1, -1)
             cam_dict, sgc_dict, _score = infer_cam_fused(model, stager(img, DEFAULT_SCALES), label, H, W, want_cam=want_cam,
-                                                         want_sgc=want_sgc)
+                                                         want_sgc=want_sgc, pamr=pamr,
+                                                         pamr_img=np.asarray(img, dtype=np.uint8) if pamr is not None else None)
             if want_cam:
                 writer.put(os.path.join(args.out_cam_npy, name + ".npy"), cam_dict)
             if want_sgc:

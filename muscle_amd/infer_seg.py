@@ -14,6 +14,10 @@ Differences a caller can see:
     (mode L), and DIR/stats.npz, the per-class code histograms - the inputs of `python -m muscle_amd.selflabel select`, which
     keeps the most confident portion of every class for a self-training round; with --gt_dir also the quality curve.  Refused
     with --cls_dir unless --crf 2 (a class-scaled mean map is no distribution).  Without it nothing changes;
+  * --pamr_iters N [--pamr_dilations 1 2 4 8 12 24] (new, default 0 = off): the mean probability map is refined on the device by
+    N iterations of pixel-adaptive mask refinement against the image (muscle_amd/pamr.py), the label map is the refined map's
+    argmax and --out_conf sees the refined map.  An edge-aware option at a fraction of the CRF's cost; refused together with
+    --crf 2.  Parity with the published PAMR code unpinned, effect on mIoU unmeasured;
   * --num_workers and --tblog are accepted and unused (the multi-scale list is built on the device, nothing is logged).
 """
 from __future__ import annotations
@@ -51,7 +55,12 @@ def parse_args(argv: Optional[List[str]] = None):
     ap.add_argument("--out_conf", default=None, type=str,
                     help="with --out_seg: also write the confidence-code map <name>.png of every image and stats.npz, the "
                          "per-class histograms, here (muscle_amd.selflabel select turns them into self-training labels)")
+    from muscle_amd.infer_mcl import add_pamr_arguments, check_pamr_arguments
+    add_pamr_arguments(ap, "the mean probability map")
     args = ap.parse_args(argv)
+    check_pamr_arguments(ap, args)
+    if args.pamr_iters > 0 and args.crf != 0:
+        ap.error("--pamr_iters with --crf: PAMR and the dense CRF are two refinements of the same map; choose one")
     if args.out_conf is not None and args.out_seg is None:
         ap.error("--out_conf writes the confidence of the --out_seg label maps: it needs --out_seg")
     if args.out_conf is not None and args.cls_dir and args.crf != 2:
@@ -96,6 +105,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     model = model.to(dev).eval()
     scales = tuple(float(s) for s in args.scales.split(","))
     stager = MSFStager(dev)
+    pamr = muscle_amd.PAMR(args.pamr_iters, args.pamr_dilations) if args.pamr_iters > 0 else None
     ev = SegEval(dev, args.num_classes) if args.gt_dir else None
     bev = BoundaryEval(dev, args.num_classes) if args.boundary else None
     if args.out_seg is not None:
@@ -112,8 +122,9 @@ def main(argv: Optional[List[str]] = None) -> int:
         if args.cls_dir:
             cls = np.load(os.path.join(args.cls_dir, name + ".npy"), allow_pickle=True).squeeze()
         crf_img = np.asarray(img, dtype=np.uint8) if args.crf == 2 else None                # infer_seg.py:128-129, t=4
+        pamr_img = np.asarray(img, dtype=np.uint8) if pamr is not None else None
         pred, prob = infer_seg(model, stager(img, scales), H, W, cls_label=cls, crf_img=crf_img, crf_t=4, crf_trunc=args.crf_trunc,
-                               crf_pairwise=args.crf_pairwise, return_prob=stats is not None)
+                               crf_pairwise=args.crf_pairwise, return_prob=stats is not None, pamr=pamr, pamr_img=pamr_img)
         if args.out_seg is not None:
             save_seg_png(os.path.join(args.out_seg, name + ".png"), pred)
         if ev is not None:
